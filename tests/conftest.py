@@ -76,6 +76,19 @@ def have_reference():
 
 needs_reference = pytest.mark.skipif(not have_reference(), reason="/root/reference not mounted (GPU box)")
 
+# the reference's scene files, byte for byte (xz-compressed data fixtures; octree_kat.json pins each one's sha256)
+VOX_FIXTURES = os.path.join(GOLDEN, "vox")
+
+
+def reference_vox_names():
+    return sorted(f[:-len(".vox.xz")] for f in os.listdir(VOX_FIXTURES) if f.endswith(".vox.xz"))
+
+
+def reference_vox(name):
+    import lzma
+    with lzma.open(os.path.join(VOX_FIXTURES, name + ".vox.xz")) as f:
+        return f.read()
+
 
 def bits(a):
     return np.ascontiguousarray(a, np.float32).view(np.uint32)

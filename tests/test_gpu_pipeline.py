@@ -537,6 +537,42 @@ def test_tolerant_denoise_mode_at_4k_radius_8(O, H, scenes, noise):
     assert (tolerant[..., 3] == 1).all() and np.isfinite(tolerant).all()
 
 
+def test_bench_dumps_what_its_last_timed_step_computed(tmp_path):
+    """`--steps K --dump-outputs DIR`: K timed steps (one block, ms_per_step = its time / K), then the three trace images of the last
+    one on disk — frame warmup + K (the untimed block) + K of the benchmark's scene, camera and noise, as a context rendering those
+    frames one by one gives them, cut to bench.py's documented pixel sample."""
+    import importlib.util
+    import json
+    import subprocess
+    import sys
+    from conftest import ROOT
+    from gpu_voxel_raytracer_amd import ALBEDO_NODE, NORMAL_DEPTH, SAMPLED_COLOR, TRACE, Camera, Context, scenes
+    steps, warmup = 24, 4
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(steps), "--warmup", str(warmup), "--no-extras", "--no-cpu-baseline",
+                          "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stderr[-2000:]
+    d = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
+    assert d["steps"] == steps and d["timing"]["blocks"] == 1 and d["timing"]["steps_per_block"] == steps
+    assert d["ms_per_step"] > 0 and abs(d["ms_per_step"] - d["timing"]["block_ms"]["median"] / steps) < 1e-3
+    spec = importlib.util.spec_from_file_location("bench", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    names = {"sampled_color": SAMPLED_COLOR, "normal_depth": NORMAL_DEPTH, "albedo_node": ALBEDO_NODE}
+    assert sorted(os.listdir(tmp_path)) == sorted(n + ".npy" for n in names) and d["outputs_dumped"]["images"] == sorted(names)
+    assert sum(os.path.getsize(tmp_path / f) for f in os.listdir(tmp_path)) <= 64e6
+    pos, mrgb, size = scenes.load_scene(bench.SCENE)
+    with Context(bench.WIDTH, bench.HEIGHT, device=0, max_bounces=bench.BOUNCES) as ctx:
+        ctx.recreate_octree(pos, mrgb)
+        ctx.camera = Camera(*scenes.bench_camera(size))
+        ctx.render_frames(TRACE, warmup + 2 * steps)
+        for name, which in names.items():
+            full = ctx.read(which).reshape(-1, 4)
+            idx = np.sort(np.random.default_rng(bench.DUMP_SEED).choice(len(full), bench.DUMP_PIXELS, replace=False))
+            got = np.load(tmp_path / (name + ".npy"))
+            assert got.dtype == np.float32 and got.shape == (bench.DUMP_PIXELS, 4)
+            assert_bits_equal(got, full[idx], name)
+
+
 def test_bench_quotes_recorded_counters_when_it_does_not_measure_them():
     """`--no-extras` (or a box without rocprofv3) skips the profiler child passes: the line then quotes the RECORDED counters of the newest
     profiles/rNN/ and says so — never a bare number of unknown origin."""

@@ -7,7 +7,7 @@ import struct
 import numpy as np
 import pytest
 
-from conftest import REFERENCE, needs_reference
+from conftest import reference_vox, reference_vox_names
 from test_oracle_scene import KAT, chunk, make_vox, matl
 
 
@@ -65,10 +65,10 @@ def test_vox_decoder_error_codes(H):
     assert code(evil) == H.E_VOX_EOF
 
 
-@needs_reference
 def test_vox_decoder_equals_oracle_on_every_reference_scene(O, H):
-    for f in sorted(os.listdir(os.path.join(REFERENCE, "vox"))):
-        data = open(os.path.join(REFERENCE, "vox", f), "rb").read()
+    assert len(reference_vox_names()) == 15
+    for f in reference_vox_names():
+        data = reference_vox(f)
         p1, m1, s1 = H.vox_to_voxels(data)
         p2, m2, s2 = O.voxels_from_vox(data)
         assert s1 == s2 and np.array_equal(p1, p2) and np.array_equal(m1, m2), f
@@ -160,6 +160,40 @@ def test_bench_schedule_choice():
     assert bench.pick_deal(8, 20) == (4, 1) and bench.pick_deal(4, 20) == (8, 0) and bench.pick_deal(1, 20) == (8, 0)
     assert bench.pick_deal(8, 1000) == (4, 0) and bench.pick_deal(8, 20, inflight=2, batch=10) == (4, 0) and bench.pick_deal(4, 1000) == (8, 0)
     assert bench.algorithmic_bytes(1920 * 1080, 4, 359016 + 640000) == 48 * 1920 * 1080 + 999016 + 32 * 65536
+
+
+def test_bench_dump_outputs_sample(tmp_path):
+    """bench.py --dump-outputs (pure host logic, a stand-in context): float32 [pixels, 4] per image, the same seeded pixel sample in
+    every image and in every run, at most 64 MB in all; a small image is written whole; with N ranks each writes its own files."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench", os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+
+    class Ctx:
+        def __init__(self, h, w):
+            self.h, self.w = h, w
+
+        def read(self, which):
+            return np.arange(self.h * self.w * 4, dtype=np.float32).reshape(self.h, self.w, 4) + 1e7 * which
+
+    images = {"sampled_color": 0, "normal_depth": 1, "albedo_node": 2}
+    info = bench.dump_outputs(str(tmp_path / "a"), Ctx(1080, 1920), images)
+    assert info["pixels_per_image"] == bench.DUMP_PIXELS and info["of_pixels"] == 1920 * 1080
+    got = {n: np.load(tmp_path / "a" / (n + ".npy")) for n in images}
+    assert sum(os.path.getsize(tmp_path / "a" / (n + ".npy")) for n in images) <= 64e6
+    idx = got["sampled_color"][:, 0] / 4
+    assert (np.diff(idx) > 0).all() and idx.max() < 1920 * 1080
+    for n, which in images.items():
+        assert got[n].dtype == np.float32 and got[n].shape == (bench.DUMP_PIXELS, 4)
+        assert np.array_equal(got[n], Ctx(1080, 1920).read(which).reshape(-1, 4)[idx.astype(np.int64)])
+    bench.dump_outputs(str(tmp_path / "b"), Ctx(1080, 1920), images)
+    for n in images:
+        assert np.array_equal(np.load(tmp_path / "b" / (n + ".npy")), got[n])
+    info = bench.dump_outputs(str(tmp_path / "c"), Ctx(112, 192), {"denoised": 4})
+    assert info["sample"] is None and np.array_equal(np.load(tmp_path / "c" / "denoised.npy"), Ctx(112, 192).read(4).reshape(-1, 4))
+    info = bench.dump_outputs(str(tmp_path / "d"), Ctx(540, 1920), images, rank=1, world=2)
+    assert info["pixels_per_image"] == bench.DUMP_PIXELS // 2 and sorted(os.listdir(tmp_path / "d")) == sorted(n + "_rank1.npy" for n in images)
 
 
 def decode_wide(wide, leaves, depth):

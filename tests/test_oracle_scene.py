@@ -1,18 +1,18 @@
 """CPU: the oracle's scene preparation (oracle/ovox.cpp) against the known answers the repo holds.
 
 The reference ships NO tests or golden vectors: these pins are the node-count table of
-SURVEY.md Appendix C (tests/golden/octree_kat.json), the reference's own scene files when mounted, and
+SURVEY.md Appendix C (tests/golden/octree_kat.json), the reference's own scene files (tests/golden/vox/), a fingerprint of its
+default palette, and
 hand-made .vox byte strings for the parser's error paths (src/vox.rs)."""
 import hashlib
 import json
 import os
-import re
 import struct
 
 import numpy as np
 import pytest
 
-from conftest import GOLDEN, REFERENCE, needs_reference
+from conftest import GOLDEN, reference_vox
 
 KAT = json.load(open(os.path.join(GOLDEN, "octree_kat.json")))
 
@@ -132,13 +132,13 @@ def test_vox_default_palette_when_no_rgba(O):
     assert mrgb[:, 1:].tolist() == [[0xff, 0xff, 0xff], [0xff, 0xff, 0xcc], [0x11, 0x11, 0x11]]
 
 
-@needs_reference
+# sha256 of the reference's DEFAULT_PALETTE (src/vox.rs: 256 u32 words), as little-endian words
+DEFAULT_PALETTE_SHA256 = "cc9800abac4eea5f0dc2b29399d7d6440165026723622ca30ffd77dd71653605"
+
+
 def test_default_palette_equals_reference_table(O):
-    text = open(os.path.join(REFERENCE, "src/vox.rs")).read()
-    table = text[text.index("DEFAULT_PALETTE: [u32; 256]"):]
-    table = table[:table.index("];")]
-    words = [int(w, 16) for w in re.findall(r"0x([0-9a-fA-F]{8})", table)]
-    assert len(words) == 256 and O.default_palette().tolist() == words
+    words = O.default_palette()
+    assert words.shape == (256,) and hashlib.sha256(np.asarray(words, "<u4").tobytes()).hexdigest() == DEFAULT_PALETTE_SHA256
 
 
 def test_vox_pack_uses_model_zero_and_skips_unknown_chunks(O):
@@ -169,23 +169,21 @@ def test_vox_errors(O):
     assert code(make_vox(matls=())) == -7                                  # colour without MATL: reference panics
 
 
-@needs_reference
 @pytest.mark.parametrize("name", sorted(KAT))
 def test_reference_vox_files_reproduce_fixtures(O, scenes, name):
-    data = open(os.path.join(REFERENCE, "vox", name + ".vox"), "rb").read()
+    data = reference_vox(name)
     assert hashlib.sha256(data).hexdigest() == KAT[name]["vox_sha256"]
     pos, mrgb, size = O.voxels_from_vox(data)
     fpos, fmrgb, fsize = scenes.load_scene(name)
     assert size == fsize and np.array_equal(pos, fpos) and np.array_equal(mrgb, fmrgb)
 
 
-@needs_reference
 def test_every_reference_scene_parses(O):
     # SURVEY.md Appendix C "other files": voxel counts
     want = {"chr_knight": 398, "chr_sword": 334, "custom": 13382, "doom": 3894, "monu1": 156942, "monu9": 32832,
             "nature": 75835, "room": 82536, "shelf": 1602, "teapot": 28411}
     for name, n in want.items():
-        pos, mrgb, _ = O.voxels_from_vox(open(os.path.join(REFERENCE, "vox", name + ".vox"), "rb").read())
+        pos, mrgb, _ = O.voxels_from_vox(reference_vox(name))
         assert len(pos) == n, name
 
 

@@ -8,7 +8,7 @@ import zipfile
 
 import numpy as np
 import pytest
-from conftest import REFERENCE, needs_reference
+from conftest import reference_vox, reference_vox_names
 from test_oracle_scene import chunk, make_vox, matl, vstr
 
 
@@ -163,13 +163,13 @@ def test_flags_zero_is_the_reference_adapter(H):
     assert (a[0] == b[0]).all() and (a[1] == b[1]).all() and b[2] == ((0, 0, 0), (3, 5, 4))
 
 
-@needs_reference
 def test_reference_files_through_their_scene_graph(H):
     """Every file in the reference's vox/ is one model under root -> group -> transform(_t, no rotation) -> shape (mostly
     _t = (0, 0, size_z / 2): centred in x / y, standing on z = 0); re-based it is the reference's own list."""
     import re
-    for f in sorted(os.listdir(os.path.join(REFERENCE, "vox"))):
-        data = open(os.path.join(REFERENCE, "vox", f), "rb").read()
+    assert len(reference_vox_names()) == 15
+    for f in reference_vox_names():
+        data = reference_vox(f)
         pos, mrgb, size = H.vox_to_voxels(data)
         gpos, gmrgb, (lo, hi) = H.vox_scene_to_voxels(data, H.VOX_ALL_MODELS)
         assert (gmrgb == mrgb).all(), f
