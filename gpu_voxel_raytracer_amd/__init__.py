@@ -2,4 +2,5 @@
 nolanderc/gpu-voxel-raytracer behind a C ABI (include/vxrt.h, libvxrt.so)."""
 from . import _build  # noqa: F401
 from .host import (ALL, DENOISE, DENOISE_EDGE, DENOISE_INTERIOR, TEMPORAL, TIMED, TRACE, ACCUM_COLOR, ALBEDO_NODE, DENOISED, NORMAL_DEPTH,  # noqa: F401
-                   SAMPLED_COLOR, Camera, Context, DenoiseUniforms, TemporalUniforms, Uniforms, VxrtError)
+                   SAMPLED_COLOR, DISPLAY_BGRA8_SRGB, DISPLAY_RGBA8_SRGB, Camera, Context, DenoiseUniforms, TemporalUniforms, Uniforms,
+                   VxrtError)

@@ -8,6 +8,8 @@
 namespace vxrt {
 
 size_t image_bytes(const vxrt_ctx* c) { return size_t(c->band.local_rows) * c->band.width * sizeof(float4); }
+size_t display_bytes(const vxrt_ctx* c) { return size_t(c->band.local_rows) * c->band.width * 4u; }
+bool is_display(vxrt_image which) { return which == VXRT_DISPLAY_BGRA8_SRGB || which == VXRT_DISPLAY_RGBA8_SRGB; }
 
 int count_local_rows(const BandMap& b) {
     int rows = 0;
@@ -37,6 +39,8 @@ void free_images(vxrt_ctx* c) {
         if (*p) (void)hipFree(*p);
         *p = nullptr;
     }
+    if (c->display) (void)hipFree(c->display);   // sized for the old frame: made again on its next use
+    c->display = nullptr;
     for (vxrt_ctx::TileSchedule& t : c->schedules)
     {
         for (uint32_t** p : {&t.cost, &t.order, &t.last_cost, &t.scratch}) { if (*p) (void)hipFree(*p); *p = nullptr; }
@@ -260,6 +264,22 @@ bool valid_ctx(const vxrt_ctx* c) {
     return true;
 }
 
+// The displayed frame: VXRT_DENOISED as the stages enqueued so far leave it, encoded on the context's stream into `dst`
+// (display_bytes(c); display.hip holds the rule).
+static int encode_display(vxrt_ctx* c, vxrt_image which, uint32_t* dst) {
+    HIP_TRY(launch_display_encode(c->denoised, dst, size_t(c->band.local_rows) * c->band.width, which == VXRT_DISPLAY_BGRA8_SRGB, c->stream));
+    return VXRT_OK;
+}
+
+// the context's own display buffer (vxrt_device_image, vxrt_read), with the current frame encoded into it on the context's stream
+static int encode_display_buffer(vxrt_ctx* c, vxrt_image which) {
+    if (c->display == nullptr) {
+        const size_t bytes = display_bytes(c);
+        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->display), bytes ? bytes : 16u));
+    }
+    return encode_display(c, which, c->display);
+}
+
 float4* image_ptr(vxrt_ctx* c, vxrt_image which) {
     switch (which) {
         case VXRT_SAMPLED_COLOR: return c->ring[size_t(c->slot)].sampled_color;
@@ -404,7 +424,8 @@ int apply_option(vxrt_ctx* c, uint32_t option, uint32_t value, bool at_create) {
 
 extern "C" {
 
-uint32_t vxrt_abi_version(void) { return 6; }   // 6: vxrt_read_async / vxrt_read_wait / vxrt_host_alloc / vxrt_host_free, vxrt_stats.split_launches; the header in three
+uint32_t vxrt_abi_version(void) { return 6; }   // 6: vxrt_read_async / vxrt_read_wait / vxrt_host_alloc / vxrt_host_free, vxrt_stats.split_launches; the header in three;
+                                                 // the display images VXRT_DISPLAY_* (additive, no new entry point: still 6)
 uint32_t vxrt_build_features(void) { return VXRT_VARIANTS ? uint32_t(VXRT_FEATURE_VARIANTS) : 0u; }
 
 const char* vxrt_last_error(void) { return vxrt::last_error().c_str(); }
@@ -658,6 +679,17 @@ int vxrt_sync(vxrt_ctx* c) try {
 
 int vxrt_read(vxrt_ctx* c, vxrt_image which, float* dst, size_t bytes) try {
     if (!valid_ctx(c)) return VXRT_E_INVALID;
+    if (is_display(which)) {   // 4 bytes per pixel: encoded into the context's display buffer, then copied
+        if (!dst) { set_error("null destination"); return VXRT_E_INVALID; }
+        if (bytes != display_bytes(c)) { set_error("vxrt_read: bytes must equal local_rows*width*4 for a display image"); return VXRT_E_INVALID; }
+        HIP_TRY(hipSetDevice(c->cfg.device));
+        if (int rc = sync_all(c)) return rc;
+        if (bytes == 0) return VXRT_OK;
+        if (int rc = encode_display_buffer(c, which)) return rc;
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        HIP_TRY(hipMemcpy(dst, c->display, bytes, hipMemcpyDeviceToHost));
+        return VXRT_OK;
+    }
     float4* src = image_ptr(c, which);
     if (!src || !dst) { set_error("bad image or null destination"); return VXRT_E_INVALID; }
     if (bytes != image_bytes(c)) { set_error("vxrt_read: bytes must equal local_rows*width*16"); return VXRT_E_INVALID; }
@@ -668,16 +700,19 @@ int vxrt_read(vxrt_ctx* c, vxrt_image which, float* dst, size_t bytes) try {
 } VXRT_CATCH
 
 // The non-blocking read-back (vxrt.h).  Order of events for slot k:
-//   context stream:  [wait arrived_k of the slot's previous use] [wait the trace launch, for a trace image] D2D image -> stage_k, record snap_k
+//   context stream:  [wait arrived_k of the slot's previous use] [wait the trace launch, for a trace image] D2D image -> stage_k
+//                    (a display image: the sRGB encode of the denoised image -> stage_k, in place of the copy), record snap_k
 //   copy stream:     wait snap_k, D2H stage_k -> dst, record arrived_k
 // The image itself is free for the next frame as soon as the context stream has passed the D2D copy (33 MB at 1080p: ~0.03 ms of HBM
 // time), the stage is not reused before its transfer has arrived, and the host only ever waits in vxrt_read_wait.
 int vxrt_read_async(vxrt_ctx* c, vxrt_image which, float* dst, size_t bytes, uint32_t slot) try {
     if (!valid_ctx(c)) return VXRT_E_INVALID;
-    float4* src = image_ptr(c, which);
+    const bool display = is_display(which);
+    float4* src = display ? c->denoised : image_ptr(c, which);
     if (!src || !dst) { set_error("bad image or null destination"); return VXRT_E_INVALID; }
     if (slot > 1) { set_error("vxrt_read_async: slot must be 0 or 1"); return VXRT_E_INVALID; }
-    if (bytes != image_bytes(c)) { set_error("vxrt_read_async: bytes must equal local_rows*width*16"); return VXRT_E_INVALID; }
+    if (display && bytes != display_bytes(c)) { set_error("vxrt_read_async: bytes must equal local_rows*width*4 for a display image"); return VXRT_E_INVALID; }
+    if (!display && bytes != image_bytes(c)) { set_error("vxrt_read_async: bytes must equal local_rows*width*16"); return VXRT_E_INVALID; }
     HIP_TRY(hipSetDevice(c->cfg.device));
     vxrt_ctx::ReadSlot& rs = c->read_slots[slot];
     if (c->copy_stream == nullptr) HIP_TRY(hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
@@ -699,7 +734,11 @@ int vxrt_read_async(vxrt_ctx* c, vxrt_image which, float* dst, size_t bytes, uin
     const bool trace_image = which == VXRT_SAMPLED_COLOR || which == VXRT_NORMAL_DEPTH || which == VXRT_ALBEDO_NODE || (which == VXRT_ACCUM_COLOR && c->accum_is_sampled);
     vxrt_ctx::Slot& cur = c->ring[size_t(c->slot)];
     if (trace_image && cur.trace_done != nullptr) HIP_TRY(hipStreamWaitEvent(c->stream, cur.trace_done, 0));
-    HIP_TRY(hipMemcpyAsync(rs.stage, src, bytes, hipMemcpyDeviceToDevice, c->stream));
+    if (display) {   // the encode IS the snapshot: it writes the 4-byte pixels straight into the stage
+        if (int rc = encode_display(c, which, reinterpret_cast<uint32_t*>(rs.stage))) return rc;
+    } else {
+        HIP_TRY(hipMemcpyAsync(rs.stage, src, bytes, hipMemcpyDeviceToDevice, c->stream));
+    }
     HIP_TRY(hipEventRecord(rs.snap, c->stream));
     if (trace_image) {   // the ring slot may be traced into again only after the snapshot has read it
         HIP_TRY(hipEventRecord(cur.own, c->stream));
@@ -739,6 +778,13 @@ int vxrt_host_free(void* p) try {
 
 int vxrt_device_image(vxrt_ctx* c, vxrt_image which, void** device_ptr, size_t* bytes) try {
     if (!valid_ctx(c) || !device_ptr) { set_error("null argument"); return VXRT_E_INVALID; }
+    if (is_display(which)) {   // encoded on the context's stream now: a consumer orders itself after it (vxrt_stream_wait_context)
+        HIP_TRY(hipSetDevice(c->cfg.device));
+        if (int rc = encode_display_buffer(c, which)) return rc;
+        *device_ptr = c->display;
+        if (bytes) *bytes = display_bytes(c);
+        return VXRT_OK;
+    }
     float4* src = image_ptr(c, which);
     if (!src) { set_error("bad image"); return VXRT_E_INVALID; }
     *device_ptr = src;

@@ -347,6 +347,21 @@ int vxrt_debug_fused_profile(vxrt_ctx* c, uint64_t out[8]) try {
 } VXRT_CATCH
 
 // device-vs-host bit equality probe of include/vxrt_detmath.h (test hook; host arrays in and out)
+int vxrt_debug_display_encode(int32_t device, const float* rgba, size_t n_pixels, uint32_t format, uint8_t* out) try {
+    if (!rgba || !out) { set_error("null argument"); return VXRT_E_INVALID; }
+    if (!is_display(vxrt_image(format))) { set_error("format must be VXRT_DISPLAY_BGRA8_SRGB or VXRT_DISPLAY_RGBA8_SRGB"); return VXRT_E_INVALID; }
+    if (n_pixels == 0) return VXRT_OK;
+    HIP_TRY(hipSetDevice(device));
+    ScratchBuffer bin, bout;
+    HIP_TRY(bin.alloc(n_pixels * 16));
+    HIP_TRY(bout.alloc(n_pixels * 4));
+    HIP_TRY(hipMemcpy(bin.p, rgba, n_pixels * 16, hipMemcpyHostToDevice));
+    HIP_TRY(launch_display_encode(bin.as<float4>(), bout.as<uint32_t>(), n_pixels, format == VXRT_DISPLAY_BGRA8_SRGB, nullptr));
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(out, bout.p, n_pixels * 4, hipMemcpyDeviceToHost));
+    return VXRT_OK;
+} VXRT_CATCH
+
 int vxrt_detmath_probe(int32_t device, int32_t fn, const float* x, const float* y, float* out, size_t n) try {
     if (!x || !y || !out) { set_error("null argument"); return VXRT_E_INVALID; }
     HIP_TRY(hipSetDevice(device));

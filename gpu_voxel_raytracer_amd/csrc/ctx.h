@@ -229,6 +229,8 @@ struct vxrt_ctx {
     };
     hipStream_t copy_stream = nullptr;
     ReadSlot read_slots[2];
+    // the displayed frame (vxrt_device_image / vxrt_read of VXRT_DISPLAY_*): 4 bytes per pixel, allocated on first use, freed with the images
+    uint32_t* display = nullptr;
 
     // VXRT_OPT_TRACE_PRIORITY (round 6's experiment): the trace streams at the device's highest priority, the tiles that only store
     // sky as a grid of their own on a low-priority stream per trace stream
@@ -268,6 +270,8 @@ EventPair take_pair(vxrt_ctx* c, int stage);
 int resolve_events(vxrt_ctx* c);
 bool valid_ctx(const vxrt_ctx* c);
 float4* image_ptr(vxrt_ctx* c, vxrt_image which);
+bool is_display(vxrt_image which);                    // VXRT_DISPLAY_BGRA8_SRGB / VXRT_DISPLAY_RGBA8_SRGB
+size_t display_bytes(const vxrt_ctx* c);              // local_rows * width * 4
 // ---- api_scene.hip
 bool use_wide(const vxrt_ctx* c);
 // the smallest box of cells of tree level min(depth, 7) that holds every voxel; recs: the first records of the tree, breadth first,

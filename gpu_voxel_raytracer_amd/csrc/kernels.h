@@ -296,5 +296,9 @@ hipError_t launch_noise_fill(float* dst, uint32_t seed, size_t n, hipStream_t s)
 hipError_t launch_blue_noise(float* dst, uint32_t seed, uint32_t first_layer, uint32_t layers, int size, hipStream_t s);
 // detmath probe for the device-vs-host bit-equality test (tests/test_detmath_gpu.py)
 hipError_t launch_detmath_probe(int fn, const float* x, const float* y, float* out, size_t n, hipStream_t s);
+// the displayed frame (display.hip): n pixels of rgba32f -> 4 bytes each by the library's sRGB rule (vxrt.h: VXRT_DISPLAY_*), in
+// B, G, R, A order (bgra) or R, G, B, A; the 255 thresholds go to the kernel by value (slot 255: padding, never compared)
+struct DisplayTable { float t[256]; };
+hipError_t launch_display_encode(const float4* src, uint32_t* dst, size_t n, bool bgra, hipStream_t s);
 
 }  // namespace vxrt

@@ -8,13 +8,15 @@ Scenes: a fixture name (tests/golden/scenes/*.npz), a .vox file (`--whole-scene`
 (src/context.rs:838-910, 618-622).  `--noise blue` generates the blue-noise table on the GPU, `--noise <file.zip>` loads
 one in the reference's resource format.
 The reference shows `denoised_color` through an sRGB swap chain without tone mapping (shaders/display.frag,
-src/context.rs:1352-1403); the PNGs are written the same way (clamp to [0,1], sRGB encode)."""
+src/context.rs:1352-1403); the PNGs are written the same way (clamp to [0,1], sRGB encode) — by `srgb8` on the CPU (`--encode cpu`,
+the default) or by the library on the GPU (`--encode gpu`: the display image DISPLAY_RGBA8_SRGB, alpha dropped).  Both give the library's
+exact displayed byte (include/vxrt.h), so the PNGs are the same."""
 import argparse
 import os
 
 import numpy as np
 
-from . import ALL, DENOISED, Camera, Context, scenes
+from . import ALL, DENOISED, DISPLAY_RGBA8_SRGB, Camera, Context, scenes
 
 
 def orbit_camera(size_xyz, t, radius_scale=1.5, height=0.6, fov=scenes.FOV_70):
@@ -29,8 +31,9 @@ def orbit_camera(size_xyz, t, radius_scale=1.5, height=0.6, fov=scenes.FOV_70):
 
 
 def srgb8(rgb):
-    """Linear -> 8-bit sRGB, as a Bgra8UnormSrgb swap chain stores it (src/context.rs:696-706)."""
-    x = np.clip(np.nan_to_num(rgb, nan=0.0, posinf=1.0, neginf=0.0), 0.0, 1.0)
+    """Linear -> 8-bit sRGB, as a Bgra8UnormSrgb swap chain stores it (src/context.rs:696-706), evaluated in binary64: for every
+    binary32 input that is the correctly rounded byte of the display images' rule (include/vxrt.h)."""
+    x = np.clip(np.nan_to_num(np.asarray(rgb, np.float64), nan=0.0, posinf=1.0, neginf=0.0), 0.0, 1.0)
     y = np.where(x <= 0.0031308, 12.92 * x, 1.055 * np.power(x, 1 / 2.4) - 0.055)
     return (y * 255.0 + 0.5).astype(np.uint8)
 
@@ -63,11 +66,21 @@ def load_into(ctx, scene, whole_scene=False):
 
 
 def run(scene="menger", width=1280, height=720, frames=16, bounces=3, radius=0, moving=False, out=None, device=0,
-        frames_in_flight=1, dump_every=0, noise="white", spp=1, whole_scene=False, float_dump=False):
+        frames_in_flight=1, dump_every=0, noise="white", spp=1, whole_scene=False, float_dump=False, encode="cpu"):
     """Renders `frames` frames; returns the last denoised frame (float32 [h, w, 4]) and the context statistics.
     float_dump: also write the frame losslessly as <out>.exr (OpenEXR, 32-bit float, save_exr) and <out>.npy (float32 [h, w, 4]):
-    linear radiance as denoise.comp stores it — the lossless counterparts of the 8-bit sRGB PNG (PNG / EXR)."""
+    linear radiance as denoise.comp stores it — the lossless counterparts of the 8-bit sRGB PNG (PNG / EXR).
+    encode: "cpu" (srgb8 of the denoised frame) or "gpu" (the library's display image) makes the PNGs' bytes."""
     from . import host
+    if encode not in ("cpu", "gpu"):
+        raise ValueError("encode must be cpu or gpu")
+
+    def png(ctx, path):
+        if encode == "gpu":
+            save_png_bytes(ctx.read(DISPLAY_RGBA8_SRGB)[..., :3], path)
+        else:
+            save_png(ctx.read(DENOISED), path)
+    shown = None
     with Context(width, height, device=device, max_bounces=bounces, frames_in_flight=frames_in_flight,
                  frames_per_launch=min(max(spp, 1), 32) if spp > 1 else min(max(frames, 1), 16)) as ctx:
         if noise == "blue":
@@ -92,11 +105,16 @@ def run(scene="menger", width=1280, height=720, frames=16, bounces=3, radius=0, 
             else:
                 ctx.render(ALL)
             if out and dump_every and (f + 1) % dump_every == 0:
-                save_png(ctx.read(DENOISED), f"{out}_{f + 1:04d}.png")
+                png(ctx, f"{out}_{f + 1:04d}.png")
         img = ctx.read(DENOISED)
+        if out and encode == "gpu":
+            shown = ctx.read(DISPLAY_RGBA8_SRGB)[..., :3]
         st = ctx.stats()
     if out:
-        save_png(img, out + ".png")
+        if shown is not None:
+            save_png_bytes(shown, out + ".png")
+        else:
+            save_png(img, out + ".png")
         if float_dump:
             np.save(out + ".npy", np.ascontiguousarray(img, np.float32))
             save_exr(img, out + ".exr")
@@ -133,9 +151,14 @@ def save_exr(img, path):
 
 
 def save_png(img, path):
+    save_png_bytes(srgb8(img[..., :3]), path)
+
+
+def save_png_bytes(rgb8, path):
+    """uint8 [h, w, 3] sRGB bytes -> PNG."""
     from PIL import Image
     os.makedirs(os.path.dirname(os.path.abspath(path)) or ".", exist_ok=True)
-    Image.fromarray(srgb8(img[..., :3])).save(path)
+    Image.fromarray(np.ascontiguousarray(rgb8, np.uint8)).save(path)
 
 
 def main():
@@ -152,10 +175,13 @@ def main():
     ap.add_argument("--spp", type=int, default=1, help="samples per pixel per displayed frame (vxrt_render_spp)")
     ap.add_argument("--whole-scene", action="store_true", help="place every model of a .vox file's scene graph")
     ap.add_argument("--float-dump", action="store_true", help="also write <out>.exr (OpenEXR, float32) and <out>.npy: the frame as linear radiance, lossless")
+    ap.add_argument("--encode", choices=("cpu", "gpu"), default="cpu",
+                    help="who makes the PNGs' sRGB bytes: srgb8 on the CPU, or the library's display image on the GPU (same bytes)")
     ap.add_argument("--out", default="gpurun_out/frame")
     args = ap.parse_args()
     img, st = run(args.scene, args.width, args.height, args.frames, args.bounces, args.radius, args.moving, args.out,
-                  dump_every=args.dump_every, noise=args.noise, spp=args.spp, whole_scene=args.whole_scene, float_dump=args.float_dump)
+                  dump_every=args.dump_every, noise=args.noise, spp=args.spp, whole_scene=args.whole_scene, float_dump=args.float_dump,
+                  encode=args.encode)
     print(f"{args.scene}: {st.frames} frames, {st.rays} rays, image {img.shape[1]}x{img.shape[0]} -> {args.out}.png, "
           f"mean radiance {float(np.nanmean(img[..., :3])):.4f}")
 

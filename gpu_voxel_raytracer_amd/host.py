@@ -41,6 +41,9 @@ E_VOX_MATERIAL, E_VOX_NOMATL, E_VOX_NOMODEL, E_IO, E_SCENE, E_NOSCENE, E_NOISE =
 
 # vxrt_image
 SAMPLED_COLOR, NORMAL_DEPTH, ALBEDO_NODE, ACCUM_COLOR, DENOISED = range(5)
+# the displayed frame: DENOISED encoded to 8-bit sRGB on the GPU by the library's exact rule (vxrt.h), 4 bytes per pixel
+DISPLAY_BGRA8_SRGB, DISPLAY_RGBA8_SRGB = 5, 6
+DISPLAY_IMAGES = (DISPLAY_BGRA8_SRGB, DISPLAY_RGBA8_SRGB)
 # render flags
 TRACE, TEMPORAL, DENOISE, ALL, TIMED = 1, 2, 4, 7, 8
 DENOISE_INTERIOR, DENOISE_EDGE = 16, 32   # the denoise stage in two launches around a halo exchange (vxrt.h)
@@ -383,19 +386,40 @@ def detmath_probe(fn, x, y=None, device=0):
     return out
 
 
-class PinnedImage:
-    """A float32 image in pinned host memory (vxrt_host_alloc / vxrt_host_free): the destination vxrt_read_async wants.  `.array`
-    is a numpy view of it; valid until close() / garbage collection."""
+def display_thresholds():
+    """vxrt_display_thresholds (host only): the 255 binary32 thresholds of the display images' colour byte — the byte of x is the
+    number of them that are <= x."""
+    out = np.zeros(255, np.float32)
+    _check(lib().vxrt_display_thresholds(_p(out)), "vxrt_display_thresholds")
+    return out
 
-    def __init__(self, L, shape):
+
+def display_encode(rgba, fmt=DISPLAY_RGBA8_SRGB, device=0):
+    """Test hook (vxrt_debug_display_encode): float32 pixels [..., 4] through the device encode of the display images ->
+    uint8 [..., 4] in the byte order of `fmt`."""
+    x = np.ascontiguousarray(rgba, np.float32)
+    if x.shape[-1] != 4:
+        raise ValueError("rgba must be [..., 4] float32")
+    out = np.zeros(x.shape, np.uint8)
+    _check(lib().vxrt_debug_display_encode(C.c_int32(device), _p(x), C.c_size_t(x.size // 4), C.c_uint32(fmt), _p(out)),
+           "vxrt_debug_display_encode")
+    return out
+
+
+class PinnedImage:
+    """An image in pinned host memory (vxrt_host_alloc / vxrt_host_free): the destination vxrt_read_async wants — float32 for the
+    rgba32f images, uint8 for the display images.  `.array` is a numpy view of it; valid until close() / garbage collection."""
+
+    def __init__(self, L, shape, dtype=np.float32):
         self._L = L
-        n = int(np.prod(shape)) * 4
+        dtype = np.dtype(dtype)
+        n = int(np.prod(shape)) * dtype.itemsize
         self._ptr = C.c_void_p()
         st = L.vxrt_host_alloc(C.c_size_t(n), C.byref(self._ptr))
         if st != 0:
             raise VxrtError(st, "vxrt_host_alloc", (L.vxrt_last_error() or b"").decode(errors="replace"))
-        buf = (C.c_float * (n // 4)).from_address(self._ptr.value) if n else (C.c_float * 0)()
-        self.array = np.frombuffer(buf, np.float32).reshape(shape)
+        buf = (C.c_uint8 * n).from_address(self._ptr.value) if n else (C.c_uint8 * 0)()
+        self.array = np.frombuffer(buf, dtype).reshape(shape)
 
     def close(self):
         if self._ptr:
@@ -609,20 +633,22 @@ class Context:
         return rows
 
     def read(self, which):
-        """-> float32[local_rows, width, 4] (whole frame for a single-GPU context)."""
+        """-> float32[local_rows, width, 4] (whole frame for a single-GPU context); uint8[local_rows, width, 4] for the display
+        images (DISPLAY_BGRA8_SRGB, DISPLAY_RGBA8_SRGB)."""
         n = C.c_uint32(0)
         self._chk(self._L.vxrt_local_rows(self._h, C.byref(n), None), "vxrt_local_rows")
-        out = np.zeros((n.value, self.width, 4), np.float32)
+        out = np.zeros((n.value, self.width, 4), np.uint8 if which in DISPLAY_IMAGES else np.float32)
         self._chk(self._L.vxrt_read(self._h, C.c_int(which), _p(out), C.c_size_t(out.nbytes)), "vxrt_read")
         return out
 
     def read_into(self, which, arr):
-        """vxrt_read into a caller's float32 array of the image's size (no allocation per call)."""
+        """vxrt_read into a caller's array of the image's size — float32, or uint8 for a display image (no allocation per call)."""
         self._chk(self._L.vxrt_read(self._h, C.c_int(which), _p(arr), C.c_size_t(arr.nbytes)), "vxrt_read")
 
     def read_async(self, which, dst, slot=0):
         """vxrt_read_async: snapshot image `which` as the stages enqueued so far leave it and start its transfer into `dst` (a
-        PinnedImage, or any C-contiguous float32 array of the image's size) without waiting; read_wait(slot) waits for it."""
+        PinnedImage, or any C-contiguous array of the image's size: float32, uint8 for a display image) without waiting; read_wait(slot)
+        waits for it."""
         arr = dst.array if isinstance(dst, PinnedImage) else dst
         self._chk(self._L.vxrt_read_async(self._h, C.c_int(which), _p(arr), C.c_size_t(arr.nbytes), C.c_uint32(slot)), "vxrt_read_async")
 
@@ -634,6 +660,13 @@ class Context:
         n = C.c_uint32(0)
         self._chk(self._L.vxrt_local_rows(self._h, C.byref(n), None), "vxrt_local_rows")
         return PinnedImage(self._L, (n.value, self.width, 4))
+
+    def pinned_display(self):
+        """A pinned uint8 host buffer of this context's display image size (local_rows x width x 4 bytes) for read_async of
+        DISPLAY_BGRA8_SRGB / DISPLAY_RGBA8_SRGB."""
+        n = C.c_uint32(0)
+        self._chk(self._L.vxrt_local_rows(self._h, C.byref(n), None), "vxrt_local_rows")
+        return PinnedImage(self._L, (n.value, self.width, 4), np.uint8)
 
     def touch_map(self, enable=True):
         """vxrt_debug_touch_map (-DVXRT_VARIANTS=1 library): mark every 64-byte line of the scene that the frames from now on read."""

@@ -144,7 +144,16 @@ typedef enum vxrt_image {
     VXRT_NORMAL_DEPTH = 1,    /* voxels.comp binding 1: (normal, t); miss = (2^30,2^30,2^30,-1)         */
     VXRT_ALBEDO_NODE = 2,     /* voxels.comp binding 2: (albedo, bits(leaf word))                       */
     VXRT_ACCUM_COLOR = 3,     /* temporal.comp binding 3: (blended rgb, next blending)                  */
-    VXRT_DENOISED = 4         /* denoise.comp binding 0: (rgb, 1) — what the reference displays         */
+    VXRT_DENOISED = 4,        /* denoise.comp binding 0: (rgb, 1) — what the reference displays         */
+    /* The displayed frame, 4 bytes per pixel: VXRT_DENOISED encoded as a Bgra8UnormSrgb swap chain stores it (src/context.rs:663,
+     * 696-706, the display pass at :2046-2063; shaders/display.frag maps pixels one to one, no tone map).  Vulkan leaves the rounding of
+     * an sRGB store to the implementation; the library fixes ONE exactly specified byte.  For a binary32 value x:
+     *   colour:  NaN -> 0;  x <= 0 (-0, -inf included) -> 0;  x >= 1 (+inf included) -> 255;  otherwise round_half_up(255 * S(x))
+     *            evaluated exactly, S(x) = 12.92 x for x <= 0.0031308, 1.055 x^(1/2.4) - 0.055 otherwise;
+     *   alpha:   linear, round_half_up(255 * clamp(a, 0, 1)), NaN -> 0 (the denoised image has a = 1: alpha 255).
+     * Added in ABI 6 without a new entry point: vxrt_abi_version() stays 6 (the change is additive). */
+    VXRT_DISPLAY_BGRA8_SRGB = 5,  /* the displayed frame: B, G, R, A bytes (the reference's swap chain)               */
+    VXRT_DISPLAY_RGBA8_SRGB = 6   /* the same bytes in R, G, B, A order (what PNG and video encoders take)          */
 } vxrt_image;
 
 enum {                        /* vxrt_render flags: which of the three dispatches of                    */
@@ -279,7 +288,11 @@ int vxrt_reset_history(vxrt_ctx* ctx);          /* still_sample = 0 path, src/co
 
 /* ---- outputs.  The reference only blits denoised_color (src/context.rs:1131-1136, the present at :2046-2070); every image is
  *      readable here.  dst receives this context's rows in ascending frame-row order, rgba32f,
- *      local_rows*width*16 bytes (vxrt_local_rows; = height for a single-GPU context). ------------ */
+ *      local_rows*width*16 bytes (vxrt_local_rows; = height for a single-GPU context).  The display images (VXRT_DISPLAY_BGRA8_SRGB,
+ *      VXRT_DISPLAY_RGBA8_SRGB) are 4 bytes per pixel: `bytes` must be local_rows*width*4 (the rgba32f size is refused with
+ *      VXRT_E_INVALID) and dst, still a float* in the signature, receives bytes — a C caller casts its uint8_t buffer.  They are
+ *      encoded on the GPU from VXRT_DENOISED as the stages enqueued so far leave it; vxrt_read_async(ctx, VXRT_DISPLAY_BGRA8_SRGB, ...)
+ *      is what replaces the present for a host that shows or stores every frame, at a quarter of the rgba32f transfer. ------------ */
 int vxrt_read(vxrt_ctx* ctx, vxrt_image which, float* dst, size_t bytes);      /* waits for the GPU, then copies: synchronous */
 /* The same without stalling the render loop — what a host that shows (or encodes) EVERY frame wants in place of the reference's
  * present (src/context.rs:2046-2070).  vxrt_read_async snapshots image `which` as the stages enqueued so far leave it (a device-side
@@ -295,7 +308,10 @@ int vxrt_read_wait(vxrt_ctx* ctx, uint32_t slot);
 int vxrt_host_alloc(size_t bytes, void** out);
 int vxrt_host_free(void* p);
 int vxrt_local_rows(const vxrt_ctx* ctx, uint32_t* count, uint32_t* rows /* optional: count entries */);
-/* Device pointer of an image (local rows, rgba32f) for zero-copy consumers on the same GPU. */
+/* Device pointer of an image (local rows, rgba32f) for zero-copy consumers on the same GPU.  A display image: the call enqueues the
+ * encode on the context's stream into a buffer the context owns (local_rows*width*4 bytes; re-made by vxrt_resize, freed by
+ * vxrt_destroy, rewritten by every vxrt_read / vxrt_device_image of a display image) and returns that buffer; the consumer orders
+ * itself after the encode with vxrt_stream_wait_context. */
 int vxrt_device_image(vxrt_ctx* ctx, vxrt_image which, void** device_ptr, size_t* bytes);
 int vxrt_get_stats(vxrt_ctx* ctx, vxrt_stats* out);
 int vxrt_reset_stats(vxrt_ctx* ctx);

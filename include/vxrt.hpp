@@ -225,6 +225,15 @@ class Context {
         check(vxrt_read(ctx_, which, img.data(), img.size() * sizeof(float)), "vxrt_read");
         return img;
     }
+    // The displayed frame (VXRT_DISPLAY_BGRA8_SRGB / VXRT_DISPLAY_RGBA8_SRGB): VXRT_DENOISED encoded to 8-bit sRGB on the GPU by the
+    // library's exact rule, local rows x width x 4 bytes
+    std::vector<uint8_t> read_display(vxrt_image which) {
+        std::vector<uint8_t> img(display_bytes());
+        check(vxrt_read(ctx_, which, reinterpret_cast<float*>(img.data()), img.size()), "vxrt_read");
+        return img;
+    }
+    // bytes of one display image of this context (its local rows x width x 4)
+    size_t display_bytes() const { return image_floats(); }
     // floats of one image of this context (its local rows x width x 4)
     size_t image_floats() const {
         uint32_t rows = 0;
@@ -235,6 +244,8 @@ class Context {
     // reference presents (src/context.rs:2046-2070).  Frame k: render(...); read_async(VXRT_DENOISED, buf[k & 1], k & 1); then
     // read_wait((k + 1) & 1) and frame k - 1 is in buf[(k + 1) & 1] — it travelled while frame k rendered.
     void read_async(vxrt_image which, class PinnedImage& dst, uint32_t slot);
+    // ... and of a display image into pinned bytes: a quarter of the rgba32f transfer (read_async(VXRT_DISPLAY_BGRA8_SRGB, buf[k & 1], k & 1))
+    void read_async(vxrt_image which, class PinnedDisplay& dst, uint32_t slot);
     void read_wait(uint32_t slot) { check(vxrt_read_wait(ctx_, slot), "vxrt_read_wait"); }
     vxrt_stats stats() {
         vxrt_stats s{};
@@ -273,6 +284,32 @@ class PinnedImage {
 
 inline void Context::read_async(vxrt_image which, PinnedImage& dst, uint32_t slot) {
     check(vxrt_read_async(ctx_, which, dst.data(), dst.bytes(), slot), "vxrt_read_async");
+}
+
+// Pinned host bytes for Context::read_async of a display image (Context::display_bytes() of them).
+class PinnedDisplay {
+  public:
+    explicit PinnedDisplay(size_t bytes) : bytes_(bytes) {
+        void* p = nullptr;
+        check(vxrt_host_alloc(bytes, &p), "vxrt_host_alloc");
+        data_ = static_cast<uint8_t*>(p);
+    }
+    ~PinnedDisplay() { if (data_) (void)vxrt_host_free(data_); }
+    PinnedDisplay(const PinnedDisplay&) = delete;
+    PinnedDisplay& operator=(const PinnedDisplay&) = delete;
+    uint8_t* data() { return data_; }
+    const uint8_t* data() const { return data_; }
+    size_t size() const { return bytes_; }
+    size_t bytes() const { return bytes_; }
+
+  private:
+    uint8_t* data_ = nullptr;
+    size_t bytes_;
+};
+
+inline void Context::read_async(vxrt_image which, PinnedDisplay& dst, uint32_t slot) {
+    // dst receives bytes; the C signature keeps float* (vxrt.h)
+    check(vxrt_read_async(ctx_, which, reinterpret_cast<float*>(dst.data()), dst.bytes(), slot), "vxrt_read_async");
 }
 
 }  // namespace vxrt

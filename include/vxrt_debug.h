@@ -102,6 +102,13 @@ int vxrt_build_records(const int16_t (*pos)[3], const uint8_t (*mrgb)[4], size_t
  * host-vs-device bit equality the numeric contract promises can be checked. */
 int vxrt_detmath_probe(int32_t device, int32_t fn, const float* x, const float* y, float* out, size_t n);
 
+/* The displayed frame's rule (vxrt.h: VXRT_DISPLAY_*).  vxrt_display_thresholds (host only, no GPU): the 255 thresholds the library
+ * encodes with — out[k] = the smallest binary32 value whose colour byte is >= k + 1, so that the byte of x is the number of out[k] <= x.
+ * vxrt_debug_display_encode: n_pixels rgba32f host pixels through the device encode of the display images (format =
+ * VXRT_DISPLAY_BGRA8_SRGB or VXRT_DISPLAY_RGBA8_SRGB) into n_pixels * 4 bytes of `out` — as vxrt_detmath_probe does for the maths. */
+int vxrt_display_thresholds(float out[255]);
+int vxrt_debug_display_encode(int32_t device, const float* rgba, size_t n_pixels, uint32_t format, uint8_t* out);
+
 /* Test hook: cast_bounded_ray (shaders/voxels.comp:134-247, max_distance 2^30) as the kernels implement it, for n caller-given
  * rays (origins, dirs: 3 floats each) through the current scene: hit flag, time, leaf word, normal (3 floats) per ray. */
 int vxrt_debug_cast_rays(vxrt_ctx* ctx, const float* origins, const float* dirs, size_t n, uint8_t* hit, float* time, int32_t* node,
