@@ -829,12 +829,12 @@ int vxrt_get_stats(vxrt_ctx* c, vxrt_stats* out) try {
     memcpy(out->cull_box_max, c->box_max, sizeof c->box_max);
     out->timed_frames = c->timed_frames;
     out->timed_launches = c->timed_launches;
-    out->scene_bytes = c->svo_count * sizeof(SvoRecord) + c->leaf_count * sizeof(int32_t);
+    out->scene_bytes = (c->svo_cap ? c->svo_cap : c->svo_count) * sizeof(SvoRecord) + (c->leaf_cap ? c->leaf_cap : c->leaf_count) * sizeof(int32_t);
     out->noise_bytes = kNoiseCount * sizeof(float);
     out->local_rows = uint32_t(c->band.local_rows);
     out->octree_depth = c->depth;
     out->node_order = uint32_t(c->node_order_applied);
-    out->octree_nodes = c->svo_count;
+    out->octree_nodes = c->live_nodes;
     for (size_t lane = 0; lane < c->queues.size(); lane++)   // fold in what the last launches wanted (the GPU is idle here)
         if (c->trace_variant >= 4) { if (int rc = grow_tail_queues(c, lane)) return rc; }
     out->wide_nodes = c->wide_count;

@@ -182,6 +182,7 @@ int upload_svo(vxrt_ctx* c, std::vector<SvoRecord>& recs, std::vector<int32_t>& 
     c->root_size = float(1u << depth);                                   // src/context.rs:779
     c->depth = depth;
     c->has_scene = true;
+    scene_replaced(c);
     c->box_valid = scene_box(recs.data(), recs.size(), depth, c->root_center, c->root_size, c->box_min, c->box_max);
     return c->scene_format == 1 ? VXRT_OK : apply_node_order(c);
 }
@@ -262,6 +263,7 @@ int vxrt_set_menger(vxrt_ctx* c, uint32_t level, uint32_t clip, const uint8_t mr
         c->root_size = float(1u << depth);
         c->depth = depth;
         c->has_scene = true;
+        scene_replaced(c);
         // the sky cull's box from the top of the tree: levels 0 .. 6 are a prefix of the records (find where level 7 starts, copy that much)
         c->box_valid = false;
         size_t prefix = 1;

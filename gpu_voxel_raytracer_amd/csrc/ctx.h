@@ -7,6 +7,7 @@
 //   api_halo.hip     the multi-rank halo: layout, pack / unpack, interior / edge denoise split
 //   api_host.cpp     host-only helpers (no GPU): .vox decoding, octree words, camera basis, noise archive
 //   api_debug.hip    test hooks and diagnostics
+//   api_edit.hip     in-place scene edits and the pick query (vxrt_edit.h)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -84,6 +85,12 @@ struct vxrt_ctx {
     int sky_cull = 1;   // VXRT_OPT_SKY_CULL
     uint32_t depth = 0;
     float* d_noise = nullptr;
+    // in-place edits (api_edit.hip, vxrt_edit.h).  The first edit records how many records / leaf words the build produced: a block
+    // below those counts is tight, one at or above them was allocated by an edit and holds 8 entries.  The storage grows only there.
+    bool edited = false;
+    size_t svo_built = 0, leaf_built = 0;
+    size_t svo_cap = 0, leaf_cap = 0;   // entries allocated once an edit grew the storage (0: exactly svo_count / leaf_count)
+    size_t live_nodes = 0;              // records in the tree (svo_count less the holes edits left: vxrt_stats.octree_nodes)
 
     // Images (local rows x width, rgba32f).  The trace outputs live in a ring of frame slots so that the
     // trace stage of up to `inflight` consecutive frames can be on the GPU together (one stream each) while
@@ -257,6 +264,12 @@ inline void drop_touch_maps(vxrt_ctx* c) {
     c->touch_node_lines = c->touch_leaf_lines = 0;
     for (void*& g : c->dda_grid) { if (g) (void)hipFree(g); g = nullptr; }   // ... and so was the DDA prototype's grid
     c->dda_levels = 0;
+}
+// a scene was just set (api_scene.hip): none of it comes from an edit
+inline void scene_replaced(vxrt_ctx* c) {
+    c->edited = false;
+    c->svo_built = c->leaf_built = c->svo_cap = c->leaf_cap = 0;
+    c->live_nodes = c->svo_count;
 }
 // ---- api_context.hip
 size_t image_bytes(const vxrt_ctx* c);

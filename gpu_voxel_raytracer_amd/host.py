@@ -165,6 +165,12 @@ class HaloInfo(C.Structure):
                 ("edge_tile_rows", C.c_uint32), ("max_rows", C.c_uint32), ("message_bytes", C.c_uint64)]
 
 
+# vxrt_pick_hit (include/vxrt_edit.h)
+PICK_HIT_DTYPE = np.dtype([("status", np.uint32), ("time", np.float32), ("normal", np.float32, (3,)), ("voxel", np.int32, (3,)),
+                           ("leaf", np.int32)])
+PICK_MISS, PICK_HIT, PICK_CAP = 0, 1, 2
+
+
 class Camera:
     """Camera, src/camera.rs:5-9.  Default = the reference's start camera, src/context.rs:618-622."""
 
@@ -512,6 +518,49 @@ class Context:
         self._chk(self._L.vxrt_debug_read_scene(self._h, _p(svo), C.c_size_t(len(svo)), C.byref(ns), _p(leaves), C.c_size_t(len(leaves)), C.byref(nl)),
                "vxrt_debug_read_scene")
         return svo, leaves
+
+    def edit_voxels(self, pos, mrgb):
+        """vxrt_edit_voxels: set (insert or overwrite) voxels of the scene in place, on the device; the last entry for a position wins.
+        Same positions and words as recreate_octree; the octree depth never changes (positions outside the root cube are refused);
+        the temporal history is kept.  Multi-GPU: apply the same edits on every rank's context (each holds the whole scene)."""
+        pos = np.ascontiguousarray(pos, np.int16).reshape(-1, 3)
+        mrgb = np.ascontiguousarray(mrgb, np.uint8).reshape(-1, 4)
+        if len(mrgb) != len(pos):
+            raise ValueError("one mrgb per position")
+        self._chk(self._L.vxrt_edit_voxels(self._h, _p(pos), _p(mrgb), C.c_size_t(len(pos))), "vxrt_edit_voxels")
+
+    def clear_voxels(self, pos):
+        """vxrt_edit_voxels without words: remove voxels of the scene in place (absent positions are ignored)."""
+        pos = np.ascontiguousarray(pos, np.int16).reshape(-1, 3)
+        self._chk(self._L.vxrt_edit_voxels(self._h, _p(pos), None, C.c_size_t(len(pos))), "vxrt_edit_voxels")
+
+    def pick(self, origins, dirs):
+        """vxrt_pick: cast rays against the scene as it stands after everything enqueued so far -> dict of numpy arrays
+        status (PICK_MISS / PICK_HIT / PICK_CAP), time, normal [n,3], voxel [n,3] (vxrt_set_voxels coordinates), leaf (the word)."""
+        o = np.ascontiguousarray(origins, np.float32).reshape(-1, 3)
+        d = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
+        if len(o) != len(d):
+            raise ValueError("one direction per origin")
+        out = np.zeros(len(o), PICK_HIT_DTYPE)
+        self._chk(self._L.vxrt_pick(self._h, _p(o), _p(d), C.c_size_t(len(o)), _p(out)), "vxrt_pick")
+        return {name: out[name].copy() for name in PICK_HIT_DTYPE.names}
+
+    def pixel_rays(self, xs, ys):
+        """Rays through the CENTRES of pixels (xs, ys) of the full frame from the current camera (Camera.axis_scaled):
+        direction normalize((x + 0.5) right - (y + 0.5) up + forward_ray), origin the camera position.  Note that the tracer's own
+        primary ray of pixel (x, y) passes through its corner (x, y) instead (voxels.comp:299-303).  -> (origins, dirs) float32 [n,3]."""
+        x = np.asarray(xs, np.float32).reshape(-1, 1) + np.float32(0.5)
+        y = np.asarray(ys, np.float32).reshape(-1, 1) + np.float32(0.5)
+        r, u, f = self.camera.axis_scaled(self.width, self.height)
+        d = (x * r - y * u) + f
+        d = (d / np.sqrt(np.sum(d.astype(np.float64) ** 2, axis=1, keepdims=True))).astype(np.float32)
+        o = np.broadcast_to(np.asarray(self.camera.position, np.float32), d.shape).copy()
+        return o, d
+
+    def pick_pixels(self, xs, ys):
+        """pick() of the CENTRE rays of pixels (xs, ys) (pixel_rays: through x + 0.5, y + 0.5 — not the tracer's corner rays):
+        what lies under the cursor."""
+        return self.pick(*self.pixel_rays(xs, ys))
 
     def load_vox(self, path, flags=0):
         """vox::load + voxels_from_vox + recreate_octree (src/context.rs:1817-1821); flags: VOX_* for whole scenes."""

@@ -22,6 +22,7 @@
  *                 callable on their own for tools and tests;
  *   vxrt_debug.h  test hooks, diagnostics and the scheduling options of experiments (vxrt_debug_*, vxrt_create_tuned,
  *                 VXRT_OPT_* from 7 on).  Nothing in there is needed to render, and none of it changes what a frame means.
+ * An optional extension for hosts that edit a loaded scene in place and pick the voxel under a ray: vxrt_edit.h.
  */
 #ifndef VXRT_H
 #define VXRT_H

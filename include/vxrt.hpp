@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "vxrt.h"
+#include "vxrt_edit.h"
 #include "vxrt_host.h"
 
 namespace vxrt {
@@ -154,6 +155,26 @@ class Context {
         std::vector<float> table(size_t(512) * 128 * 128);
         check(vxrt_blue_noise(device, seed, 128, 0, 512, table.data()), "vxrt_blue_noise");
         check(vxrt_set_noise(ctx_, table.data()), "vxrt_set_noise");
+    }
+    // in-place scene edits (vxrt_edit.h): set / overwrite voxels, clear voxels (absent ones are ignored); the depth never changes.
+    // Multi-GPU: every rank holds the whole scene, so the same edits go to every rank's context.
+    void edit_voxels(const VoxelList& voxels) {
+        if (voxels.mrgb.size() != voxels.pos.size()) throw Error(VXRT_E_INVALID, "edit_voxels: one mrgb per position");
+        check(vxrt_edit_voxels(ctx_, reinterpret_cast<const int16_t(*)[3]>(voxels.pos.data()),
+                               reinterpret_cast<const uint8_t(*)[4]>(voxels.mrgb.data()), voxels.pos.size()),
+              "vxrt_edit_voxels");
+    }
+    void clear_voxels(const std::vector<std::array<int16_t, 3>>& pos) {
+        check(vxrt_edit_voxels(ctx_, reinterpret_cast<const int16_t(*)[3]>(pos.data()), nullptr, pos.size()), "vxrt_edit_voxels");
+    }
+    // the voxel each ray hits (vxrt_pick_hit: status, time, normal, voxel, leaf word)
+    std::vector<vxrt_pick_hit> pick(const std::vector<std::array<float, 3>>& origins, const std::vector<std::array<float, 3>>& dirs) {
+        if (origins.size() != dirs.size()) throw Error(VXRT_E_INVALID, "pick: one direction per origin");
+        std::vector<vxrt_pick_hit> out(origins.size());
+        check(vxrt_pick(ctx_, reinterpret_cast<const float(*)[3]>(origins.data()), reinterpret_cast<const float(*)[3]>(dirs.data()),
+                        origins.size(), out.data()),
+              "vxrt_pick");
+        return out;
     }
     void set_menger(uint32_t level, uint32_t clip, std::array<uint8_t, 4> mrgb, uint32_t emissive_period) {
         check(vxrt_set_menger(ctx_, level, clip, mrgb.data(), emissive_period), "vxrt_set_menger");
