@@ -605,6 +605,7 @@ int vxrt_destroy(vxrt_ctx* c) try {
         if (rs.arrived) (void)hipEventDestroy(rs.arrived);
     }
     drop_touch_maps(c);
+    free_extract(c);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
     return VXRT_OK;

@@ -1,0 +1,131 @@
+// api_extract.hip — host side of vxrt_extract.h: the scene's voxels, whole or by box, decoded on the device (extract.hip).
+// The host runs the levels (extract.h) and reads back one number per level, the size of the next frontier, so that the scratch can
+// grow to it; the output goes to device buffers and comes back in one copy per array.  DESIGN.md "Reading the scene back".
+#include <algorithm>
+
+#include "ctx.h"
+#include "extract.h"
+#include "../../include/vxrt_extract.h"
+
+namespace vxrt {
+namespace {
+
+// `*p` holds at least `need` bytes afterwards; growth is geometric (x 1.5).  A failed allocation leaves the old buffer in place.
+// The contents are not kept (every buffer here is written before it is read, within one call).
+hipError_t ensure(void** p, size_t* cap, size_t need) {
+    if (need <= *cap && *p != nullptr) return hipSuccess;
+    const size_t want = std::max(need, *cap + *cap / 2);
+    void* fresh = nullptr;
+    hipError_t e = hipMalloc(&fresh, want);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        fresh = nullptr;
+        if (want == need) return e;
+        e = hipMalloc(&fresh, need);   // the geometric step did not fit: exactly what is needed
+        if (e != hipSuccess) { (void)hipGetLastError(); return e; }
+        if (*p) (void)hipFree(*p);
+        *p = fresh;
+        *cap = need;
+        return hipSuccess;
+    }
+    if (*p) (void)hipFree(*p);
+    *p = fresh;
+    *cap = want;
+    return hipSuccess;
+}
+
+int fail_alloc(hipError_t e, const char* what) {
+    set_error(std::string("vxrt_get_voxels: allocating ") + what + ": " + hipGetErrorString(e));
+    return VXRT_E_DEVICE;
+}
+
+}  // namespace
+
+void free_extract(vxrt_ctx* c) {
+    vxrt_ctx::ExtractScratch& x = c->extract;
+    for (void** p : {&x.front[0], &x.front[1], &x.part, &x.pos, &x.mrgb})
+        if (*p) { (void)hipFree(*p); *p = nullptr; }
+    x.front_cap[0] = x.front_cap[1] = x.part_cap = x.pos_cap = x.mrgb_cap = 0;
+}
+
+}  // namespace vxrt
+
+extern "C" {
+
+int vxrt_get_voxels(vxrt_ctx* c, const int32_t box_min[3], const int32_t box_max[3], int16_t (*pos)[3], uint8_t (*mrgb)[4], size_t cap,
+                    size_t* n) try {
+    if (!valid_ctx(c) || !n) { set_error("null argument"); return VXRT_E_INVALID; }
+    if ((box_min == nullptr) != (box_max == nullptr)) { set_error("box_min and box_max: both or neither"); return VXRT_E_INVALID; }
+    if ((pos == nullptr) != (mrgb == nullptr)) { set_error("pos and mrgb: both or neither"); return VXRT_E_INVALID; }
+    if (!c->has_scene || c->d_svo == nullptr || c->d_leaves == nullptr) { set_error("no scene set"); return VXRT_E_NOSCENE; }
+    const bool count_only = pos == nullptr;
+    const uint32_t L = c->depth;
+    const int64_t half = int64_t(1) << L;
+    // the box on the voxel grid u = p + 2^depth, clamped to the root cube [0, 2^(depth+1))^3
+    ExtractLevel a{};
+    bool empty = c->svo_count == 0;
+    for (int ax = 0; ax < 3; ax++) {
+        const int64_t lo = box_min ? std::clamp(int64_t(box_min[ax]) + half, int64_t(0), 2 * half) : 0;
+        const int64_t hi = box_max ? std::clamp(int64_t(box_max[ax]) + half, int64_t(0), 2 * half) : 2 * half;
+        if (lo >= hi) empty = true;
+        a.lo[ax] = uint32_t(lo);
+        a.hi[ax] = uint32_t(hi);
+    }
+    if (empty) { *n = 0; return VXRT_OK; }
+    a.svo = c->d_svo;
+    a.leaves = c->d_leaves;
+    a.half = uint32_t(half);
+
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    vxrt_ctx::ExtractScratch& x = c->extract;
+    // the root: record 0 at cell 0 (the decode runs on the context's stream, behind everything enqueued on it)
+    if (hipError_t e = ensure(&x.front[0], &x.front_cap[0], sizeof(uint4)); e != hipSuccess) return fail_alloc(e, "the frontier");
+    HIP_TRY(hipMemsetAsync(x.front[0], 0, sizeof(uint4), c->stream));
+    int cur = 0;
+    uint64_t count = 0;
+    uint32_t frontier = 1;
+    for (uint32_t l = 0; l <= L; l++) {
+        a.leaf = l == L ? 1u : 0u;
+        a.shift = L - l;
+        a.front = static_cast<const uint4*>(x.front[cur]);
+        a.n = frontier;
+        const uint32_t blocks = extract_blocks(frontier);
+        if (hipError_t e = ensure(&x.part, &x.part_cap, (size_t(blocks) + 1) * sizeof(uint64_t)); e != hipSuccess)
+            return fail_alloc(e, "the scan partials");
+        a.part = static_cast<uint64_t*>(x.part);
+        HIP_TRY(launch_extract_count(a, c->stream));
+        HIP_TRY(launch_extract_scan(a.part, blocks, c->stream));
+        uint64_t total = 0;
+        HIP_TRY(hipMemcpyAsync(&total, a.part + blocks, sizeof total, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        if (total == 0) break;
+        if (a.leaf) { count = total; break; }
+        if (total >= (uint64_t(1) << 32)) { set_error("vxrt_get_voxels: a tree level of 2^32 nodes or more"); return VXRT_E_INVALID; }
+        if (hipError_t e = ensure(&x.front[cur ^ 1], &x.front_cap[cur ^ 1], size_t(total) * sizeof(uint4)); e != hipSuccess)
+            return fail_alloc(e, "the frontier");
+        a.next = static_cast<uint4*>(x.front[cur ^ 1]);
+        HIP_TRY(launch_extract_expand(a, c->stream));
+        a.next = nullptr;
+        cur ^= 1;
+        frontier = uint32_t(total);
+    }
+    if (count_only || count == 0) { *n = size_t(count); return VXRT_OK; }
+    if (cap < count) {
+        *n = size_t(count);
+        set_error("vxrt_get_voxels: " + std::to_string(count) + " voxels, room for " + std::to_string(cap));
+        return VXRT_E_INVALID;
+    }
+    // the leaf parents' frontier is still in place (a.front, a.n, a.part): write the voxels at their offsets
+    if (hipError_t e = ensure(&x.pos, &x.pos_cap, size_t(count) * 3 * sizeof(int16_t)); e != hipSuccess) return fail_alloc(e, "the positions");
+    if (hipError_t e = ensure(&x.mrgb, &x.mrgb_cap, size_t(count) * 4); e != hipSuccess) return fail_alloc(e, "the leaf words");
+    a.pos = static_cast<int16_t*>(x.pos);
+    a.mrgb = static_cast<uint32_t*>(x.mrgb);
+    HIP_TRY(launch_extract_expand(a, c->stream));
+    HIP_TRY(hipMemcpyAsync(pos, x.pos, size_t(count) * 3 * sizeof(int16_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(mrgb, x.mrgb, size_t(count) * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    *n = size_t(count);
+    return VXRT_OK;
+} VXRT_CATCH
+
+}  // extern "C"

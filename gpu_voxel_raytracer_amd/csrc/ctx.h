@@ -8,6 +8,7 @@
 //   api_host.cpp     host-only helpers (no GPU): .vox decoding, octree words, camera basis, noise archive
 //   api_debug.hip    test hooks and diagnostics
 //   api_edit.hip     in-place scene edits and the pick query (vxrt_edit.h)
+//   api_extract.hip  the scene's voxels read back from the device, whole or by box (vxrt_extract.h)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -91,6 +92,17 @@ struct vxrt_ctx {
     size_t svo_built = 0, leaf_built = 0;
     size_t svo_cap = 0, leaf_cap = 0;   // entries allocated once an edit grew the storage (0: exactly svo_count / leaf_count)
     size_t live_nodes = 0;              // records in the tree (svo_count less the holes edits left: vxrt_stats.octree_nodes)
+    // vxrt_get_voxels (api_extract.hip): the decode's scratch, grown on demand (never shrunk), freed by vxrt_destroy
+    struct ExtractScratch {
+        void* front[2] = {nullptr, nullptr};   // frontier double buffer: uint4 {record, u.x, u.y, u.z} per node
+        size_t front_cap[2] = {0, 0};          // bytes
+        void* part = nullptr;                  // uint64 scan partials, one per block of the frontier, + the total
+        size_t part_cap = 0;
+        void* pos = nullptr;                   // output staging: int16[3] and 4 bytes per voxel
+        void* mrgb = nullptr;
+        size_t pos_cap = 0, mrgb_cap = 0;
+    };
+    ExtractScratch extract;
 
     // Images (local rows x width, rgba32f).  The trace outputs live in a ring of frame slots so that the
     // trace stage of up to `inflight` consecutive frames can be on the GPU together (one stream each) while
@@ -285,6 +297,8 @@ bool valid_ctx(const vxrt_ctx* c);
 float4* image_ptr(vxrt_ctx* c, vxrt_image which);
 bool is_display(vxrt_image which);                    // VXRT_DISPLAY_BGRA8_SRGB / VXRT_DISPLAY_RGBA8_SRGB
 size_t display_bytes(const vxrt_ctx* c);              // local_rows * width * 4
+// ---- api_extract.hip
+void free_extract(vxrt_ctx* c);
 // ---- api_scene.hip
 bool use_wide(const vxrt_ctx* c);
 // the smallest box of cells of tree level min(depth, 7) that holds every voxel; recs: the first records of the tree, breadth first,

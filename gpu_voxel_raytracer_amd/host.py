@@ -545,6 +545,46 @@ class Context:
         self._chk(self._L.vxrt_pick(self._h, _p(o), _p(d), C.c_size_t(len(o)), _p(out)), "vxrt_pick")
         return {name: out[name].copy() for name in PICK_HIT_DTYPE.names}
 
+    def _box(self, box_min, box_max):
+        if (box_min is None) != (box_max is None):
+            raise ValueError("box_min and box_max: both or neither")
+        if box_min is None:
+            return None, None
+        lo, hi = (np.ascontiguousarray(np.asarray(b, np.int64).reshape(3), np.int32) for b in (box_min, box_max))
+        return lo, hi
+
+    def count_voxels(self, box_min=None, box_max=None):
+        """vxrt_get_voxels, counting only: the number of voxels of the scene in the half-open box [box_min, box_max)
+        (vxrt_set_voxels coordinates, int32; None = the whole root cube)."""
+        lo, hi = self._box(box_min, box_max)
+        n = C.c_size_t(0)
+        self._chk(self._L.vxrt_get_voxels(self._h, _p(lo), _p(hi), None, None, C.c_size_t(0), C.byref(n)), "vxrt_get_voxels")
+        return int(n.value)
+
+    def get_voxels(self, box_min=None, box_max=None):
+        """vxrt_get_voxels: the voxels of the scene as it stands (after edits), decoded on the device, that lie in the half-open box
+        [box_min, box_max) (None = the whole root cube) -> (pos int16[n,3], mrgb uint8[n,4]) in octree path order
+        (include/vxrt_extract.h).  recreate_octree of the whole list builds the same scene."""
+        lo, hi = self._box(box_min, box_max)
+        n = self.count_voxels(box_min, box_max)
+        pos, mrgb = np.zeros((n, 3), np.int16), np.zeros((n, 4), np.uint8)
+        if n:
+            got = C.c_size_t(0)
+            self._chk(self._L.vxrt_get_voxels(self._h, _p(lo), _p(hi), _p(pos), _p(mrgb), C.c_size_t(n), C.byref(got)), "vxrt_get_voxels")
+            assert got.value == n
+        return pos, mrgb
+
+    def save_voxels(self, path):
+        """The scene's voxel list (get_voxels) as .npz (pos, mrgb): what load_voxels gives back to a context."""
+        pos, mrgb = self.get_voxels()
+        with open(path, "wb") as f:
+            np.savez(f, pos=pos, mrgb=mrgb)
+
+    def load_voxels(self, path):
+        """A voxel list saved by save_voxels -> the context's scene (recreate_octree)."""
+        with np.load(path) as z:
+            self.recreate_octree(z["pos"], z["mrgb"])
+
     def pixel_rays(self, xs, ys):
         """Rays through the CENTRES of pixels (xs, ys) of the full frame from the current camera (Camera.axis_scaled):
         direction normalize((x + 0.5) right - (y + 0.5) up + forward_ray), origin the camera position.  Note that the tracer's own

@@ -17,6 +17,7 @@
 
 #include "vxrt.h"
 #include "vxrt_edit.h"
+#include "vxrt_extract.h"
 #include "vxrt_host.h"
 
 namespace vxrt {
@@ -176,6 +177,16 @@ class Context {
               "vxrt_pick");
         return out;
     }
+    // the scene's voxels (vxrt_extract.h), in octree path order, whole (no box) or those in the half-open box [box_min, box_max);
+    // what set_voxels / recreate_octree turns back into the same scene.  size stays 0.
+    VoxelList get_voxels() { return get_voxels_in(nullptr, nullptr); }
+    VoxelList get_voxels(const std::array<int32_t, 3>& box_min, const std::array<int32_t, 3>& box_max) {
+        return get_voxels_in(box_min.data(), box_max.data());
+    }
+    size_t count_voxels() { return count_in(nullptr, nullptr); }
+    size_t count_voxels(const std::array<int32_t, 3>& box_min, const std::array<int32_t, 3>& box_max) {
+        return count_in(box_min.data(), box_max.data());
+    }
     void set_menger(uint32_t level, uint32_t clip, std::array<uint8_t, 4> mrgb, uint32_t emissive_period) {
         check(vxrt_set_menger(ctx_, level, clip, mrgb.data(), emissive_period), "vxrt_set_menger");
     }
@@ -278,6 +289,21 @@ class Context {
     vxrt_ctx* handle() { return ctx_; }
 
   private:
+    size_t count_in(const int32_t* lo, const int32_t* hi) {
+        size_t n = 0;
+        check(vxrt_get_voxels(ctx_, lo, hi, nullptr, nullptr, 0, &n), "vxrt_get_voxels");
+        return n;
+    }
+    VoxelList get_voxels_in(const int32_t* lo, const int32_t* hi) {
+        VoxelList v;
+        size_t n = count_in(lo, hi);
+        // the scene cannot change between the two calls (edits are calls on this context), so the count is the count
+        v.pos.resize(n);
+        v.mrgb.resize(n);
+        check(vxrt_get_voxels(ctx_, lo, hi, reinterpret_cast<int16_t(*)[3]>(v.pos.data()), reinterpret_cast<uint8_t(*)[4]>(v.mrgb.data()), n, &n),
+              "vxrt_get_voxels");
+        return v;
+    }
     vxrt_ctx* ctx_ = nullptr;
     uint32_t width_, height_;
 };
