@@ -148,6 +148,41 @@ int apply_node_order(vxrt_ctx* c) {
     return VXRT_OK;
 }
 
+// Device arrays built for the context become its scene (the context owns them from here; the old scene's arrays are freed): the
+// tail of every device build (vxrt_set_menger, vxrt_set_voxels_device).  The caller has drained the context (sync_all).  wide: the
+// same tree's wide records (VXRT_OPT_SCENE_FORMAT 1) or null.
+int install_scene(vxrt_ctx* c, SvoRecord* svo, size_t nsvo, int32_t* lw, size_t nlw, uint32_t depth, SvoRecord root, WideRec* wide,
+                  size_t nwide, WideRec wide_root) {
+    if (c->d_svo) (void)hipFree(c->d_svo);
+    if (c->d_leaves) (void)hipFree(c->d_leaves);
+    if (c->d_wide) (void)hipFree(c->d_wide);
+    drop_touch_maps(c);
+    c->d_svo = svo; c->d_leaves = lw; c->d_wide = wide;
+    c->svo_count = nsvo; c->leaf_count = nlw; c->wide_count = nwide;
+    c->root_rec = root;
+    c->wide_root = wide_root;
+    c->root_center[0] = c->root_center[1] = c->root_center[2] = 0.0f;
+    c->root_size = float(1u << depth);
+    c->depth = depth;
+    c->has_scene = true;
+    scene_replaced(c);
+    // the sky cull's box from the top of the tree: levels 0 .. 6 are a prefix of the records (find where level 7 starts, copy that much)
+    c->box_valid = false;
+    size_t prefix = 1;
+    SvoRecord first = root;
+    for (uint32_t l = 0; l < (depth < 7u ? depth : 7u) && (first.masks & 0xffu) != 0u; l++) {
+        prefix = first.base;
+        if (prefix >= nsvo) break;
+        HIP_TRY(hipMemcpy(&first, svo + prefix, sizeof first, hipMemcpyDeviceToHost));
+    }
+    if (prefix <= nsvo && prefix <= (size_t(1) << 22)) {
+        std::vector<SvoRecord> top(prefix);
+        HIP_TRY(hipMemcpy(top.data(), svo, prefix * sizeof(SvoRecord), hipMemcpyDeviceToHost));
+        c->box_valid = scene_box(top.data(), top.size(), depth, c->root_center, c->root_size, c->box_min, c->box_max);
+    }
+    return c->scene_format == 1 ? VXRT_OK : apply_node_order(c);
+}
+
 int upload_svo(vxrt_ctx* c, std::vector<SvoRecord>& recs, std::vector<int32_t>& leaves, uint32_t depth) {
     if (leaves.empty()) leaves.push_back(0);
     HIP_TRY(hipSetDevice(c->cfg.device));
@@ -251,34 +286,7 @@ int vxrt_set_menger(vxrt_ctx* c, uint32_t level, uint32_t clip, const uint8_t mr
         size_t nsvo = 0, nlw = 0;
         SvoRecord root{0, 0};
         if (int rc = build_menger_svo_device(level, clip, mrgb, emissive_period, c->stream, &svo, &nsvo, &lw, &nlw, &depth, &root)) return rc;
-        if (c->d_svo) (void)hipFree(c->d_svo);
-        if (c->d_leaves) (void)hipFree(c->d_leaves);
-        if (c->d_wide) (void)hipFree(c->d_wide);
-        drop_touch_maps(c);
-        c->d_svo = svo; c->d_leaves = lw; c->d_wide = nullptr;
-        c->svo_count = nsvo; c->leaf_count = nlw; c->wide_count = 0;
-        c->root_rec = root;
-        c->wide_root = WideRec{0, 0, 0, 0};
-        c->root_center[0] = c->root_center[1] = c->root_center[2] = 0.0f;
-        c->root_size = float(1u << depth);
-        c->depth = depth;
-        c->has_scene = true;
-        scene_replaced(c);
-        // the sky cull's box from the top of the tree: levels 0 .. 6 are a prefix of the records (find where level 7 starts, copy that much)
-        c->box_valid = false;
-        size_t prefix = 1;
-        SvoRecord first = root;
-        for (uint32_t l = 0; l < (depth < 7u ? depth : 7u) && (first.masks & 0xffu) != 0u; l++) {
-            prefix = first.base;
-            if (prefix >= nsvo) break;
-            HIP_TRY(hipMemcpy(&first, svo + prefix, sizeof first, hipMemcpyDeviceToHost));
-        }
-        if (prefix <= nsvo && prefix <= (size_t(1) << 22)) {
-            std::vector<SvoRecord> top(prefix);
-            HIP_TRY(hipMemcpy(top.data(), svo, prefix * sizeof(SvoRecord), hipMemcpyDeviceToHost));
-            c->box_valid = scene_box(top.data(), top.size(), depth, c->root_center, c->root_size, c->box_min, c->box_max);
-        }
-        return apply_node_order(c);
+        return install_scene(c, svo, nsvo, lw, nlw, depth, root, nullptr, 0, WideRec{0, 0, 0, 0});
     }
     std::vector<SvoRecord> recs;
     std::vector<int32_t> leaves;

@@ -9,6 +9,7 @@
 //   api_debug.hip    test hooks and diagnostics
 //   api_edit.hip     in-place scene edits and the pick query (vxrt_edit.h)
 //   api_extract.hip  the scene's voxels read back from the device, whole or by box (vxrt_extract.h)
+//   api_device_scene.hip  a scene built on the device from a voxel list in device memory (vxrt_device_scene.h)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -304,6 +305,10 @@ bool use_wide(const vxrt_ctx* c);
 // the smallest box of cells of tree level min(depth, 7) that holds every voxel; recs: the first records of the tree, breadth first,
 // at least those of levels 0 .. min(depth, 7) - 1.  false: no voxel at all
 bool scene_box(const SvoRecord* recs, size_t count, uint32_t depth, const float root_center[3], float root_size, float box_min[3], float box_max[3]);
+// device arrays built for the context become its scene (frees the old one; sets the counts, the sky cull's box, the node order)
+int install_scene(vxrt_ctx* c, SvoRecord* svo, size_t nsvo, int32_t* lw, size_t nlw, uint32_t depth, SvoRecord root, WideRec* wide,
+                  size_t nwide, WideRec wide_root);
+int widen_svo(const std::vector<SvoRecord>& recs, uint32_t depth, std::vector<WideRec>* out);
 // ---- api_trace.hip
 int resize_tail_queues(vxrt_ctx* c, unsigned want);
 int apply_option(vxrt_ctx* c, uint32_t option, uint32_t value, bool at_create);   // api_context.hip

@@ -6,6 +6,7 @@
 // base + popc(mask & (bit(s) - 1)).  Following those pointers from the root reads the tree in any layout the records can have: the
 // breadth-first build, the holes and 8-entry blocks edits leave (edit.hip), the depth-first treelets of VXRT_OPT_NODE_ORDER 2 / 3.
 // Children are visited in ascending slot order and written at prefix offsets, so every frontier, and the output, is in path order.
+#include "block_scan.h"
 #include "extract.h"
 
 namespace vxrt {
@@ -40,39 +41,6 @@ __device__ __forceinline__ uint32_t kept_slots(const ExtractLevel& a, const uint
     rec->base = r.y;
     const uint32_t mask = a.leaf ? (r.x >> 8) & 0xffu : r.x & 0xffu;
     return mask == 0u ? 0u : mask & box_slots(a, e.y, e.z, e.w);
-}
-
-template <typename T> __device__ __forceinline__ T wave_sum(T v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
-template <typename T> __device__ __forceinline__ T wave_inclusive(T v, uint32_t lane) {
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const T up = __shfl_up(v, off, 64);
-        if (lane >= uint32_t(off)) v += up;
-    }
-    return v;
-}
-
-// exclusive prefix sum of v over the block of W waves (in thread order); *total = the block's sum.  Ends with a barrier.
-template <typename T, uint32_t W> __device__ __forceinline__ T block_exclusive(T v, T* lds, T* total) {
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const T incl = wave_inclusive(v, lane);
-    if (lane == 63u) lds[wave] = incl;
-    __syncthreads();
-    T before = 0, all = 0;
-#pragma unroll
-    for (uint32_t w = 0; w < W; w++) {
-        const T t = lds[w];
-        if (w < wave) before += t;
-        all += t;
-    }
-    *total = all;
-    __syncthreads();
-    return before + incl - v;
 }
 
 __global__ __launch_bounds__(kExtractThreads) void extract_count_kernel(const ExtractLevel a) {

@@ -458,6 +458,7 @@ class Context:
             frames_in_flight = int(os.environ.get("VXRT_INFLIGHT", frames_in_flight))
             frames_per_launch = int(os.environ.get("VXRT_BATCH", frames_per_launch))
         self.width, self.height = int(width), int(height)
+        self.device = int(device)
         self.camera = Camera()
         cfg = Config(self.width, self.height, int(device), int(max_bounces), int(noise_seed), None, int(rank),
                      int(nranks), int(band_rows), int(frames_in_flight), int(tracer), int(frames_per_launch))
@@ -503,6 +504,30 @@ class Context:
         if pos.shape != (len(pos), 3) or mrgb.shape != (len(pos), 4):
             raise ValueError("pos must be [n,3] int16 and mrgb [n,4] uint8")
         self._chk(self._L.vxrt_set_voxels(self._h, _p(pos), _p(mrgb), C.c_size_t(len(pos))), "vxrt_set_voxels")
+
+    def set_voxels_device(self, pos, mrgb):
+        """vxrt_set_voxels_device (include/vxrt_device_scene.h): recreate_octree with the octree built on the device.  pos / mrgb are
+        torch tensors on the context's device (int16 [n,3], uint8 [n,4]), or numpy arrays, which are uploaded with torch first.  The
+        context's stream first waits for torch's current stream, so a tensor just written there is read whole.  Same records, stats
+        and frames as recreate_octree of the same list; lists the host builder refuses (2^26 nodes or more) are built too.  Import torch
+        before the first Context is made (as bench.py does), so that the process holds one HIP runtime."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        pos = torch.as_tensor(pos, device=dev) if isinstance(pos, np.ndarray) else pos
+        mrgb = torch.as_tensor(mrgb, device=dev) if isinstance(mrgb, np.ndarray) else mrgb
+        if not (isinstance(pos, torch.Tensor) and isinstance(mrgb, torch.Tensor)):
+            raise TypeError("pos and mrgb must be torch tensors or numpy arrays")
+        if pos.dtype != torch.int16 or mrgb.dtype != torch.uint8:
+            raise ValueError("pos must be int16 and mrgb uint8")
+        pos, mrgb = pos.reshape(-1, 3).contiguous(), mrgb.reshape(-1, 4).contiguous()
+        if len(pos) != len(mrgb):
+            raise ValueError("one mrgb per position")
+        if pos.device != dev or mrgb.device != dev:
+            raise ValueError(f"pos and mrgb must be on {dev}")
+        self.context_wait_stream(torch.cuda.current_stream(dev).cuda_stream)
+        self._chk(self._L.vxrt_set_voxels_device(self._h, C.c_void_p(pos.data_ptr() if len(pos) else None),
+                                                 C.c_void_p(mrgb.data_ptr() if len(pos) else None), C.c_size_t(len(pos))),
+                  "vxrt_set_voxels_device")
 
     def set_menger(self, level, clip=0, mrgb=(0, 0xb0, 0xd0, 0x60), emissive_period=0):
         """Procedural Menger sponge built straight into the device scene format (BASELINE config 5)."""

@@ -24,6 +24,7 @@
  *                 VXRT_OPT_* from 7 on).  Nothing in there is needed to render, and none of it changes what a frame means.
  * An optional extension for hosts that edit a loaded scene in place and pick the voxel under a ray: vxrt_edit.h.
  * An optional extension for hosts that read a loaded scene's voxels back, whole or by box: vxrt_extract.h.
+ * An optional extension for hosts that build a scene on the device from a voxel list in device memory: vxrt_device_scene.h.
  */
 #ifndef VXRT_H
 #define VXRT_H

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "vxrt.h"
+#include "vxrt_device_scene.h"
 #include "vxrt_edit.h"
 #include "vxrt_extract.h"
 #include "vxrt_host.h"
@@ -186,6 +187,11 @@ class Context {
     size_t count_voxels() { return count_in(nullptr, nullptr); }
     size_t count_voxels(const std::array<int32_t, 3>& box_min, const std::array<int32_t, 3>& box_max) {
         return count_in(box_min.data(), box_max.data());
+    }
+    // vxrt_set_voxels_device (vxrt_device_scene.h): pos / mrgb are n entries in device memory of the context's device, read on the
+    // context's stream (a producer on another stream calls context_wait_stream first); the octree is built on the device
+    void set_voxels_device(const int16_t (*pos)[3], const uint8_t (*mrgb)[4], size_t n) {
+        check(vxrt_set_voxels_device(ctx_, pos, mrgb, n), "vxrt_set_voxels_device");
     }
     void set_menger(uint32_t level, uint32_t clip, std::array<uint8_t, 4> mrgb, uint32_t emissive_period) {
         check(vxrt_set_menger(ctx_, level, clip, mrgb.data(), emissive_period), "vxrt_set_menger");
