@@ -5,18 +5,16 @@
 #include "../../include/vxrt_device_scene.h"
 
 namespace vxrt {
-namespace {
 
-// `bytes` at p must be device memory of the context's device, inside one allocation
-int check_device_array(const vxrt_ctx* c, const void* p, size_t bytes, const char* what) {
+int check_device_array(const vxrt_ctx* c, const void* p, size_t bytes, const char* who, const char* what) {
     hipPointerAttribute_t a{};
     if (hipPointerGetAttributes(&a, p) != hipSuccess) {
         (void)hipGetLastError();
-        set_error(std::string("vxrt_set_voxels_device: ") + what + " is not device memory");
+        set_error(std::string(who) + ": " + what + " is not device memory");
         return VXRT_E_INVALID;
     }
     if (a.type != hipMemoryTypeDevice || a.device != c->cfg.device) {
-        set_error(std::string("vxrt_set_voxels_device: ") + what + " is not device memory of the context's device");
+        set_error(std::string(who) + ": " + what + " is not device memory of the context's device");
         return VXRT_E_INVALID;
     }
     hipDeviceptr_t base = nullptr;
@@ -24,7 +22,7 @@ int check_device_array(const vxrt_ctx* c, const void* p, size_t bytes, const cha
     if (hipMemGetAddressRange(&base, &size, const_cast<void*>(p)) == hipSuccess) {
         const uintptr_t lo = reinterpret_cast<uintptr_t>(base), at = reinterpret_cast<uintptr_t>(p);
         if (at - lo > size || bytes > size - (at - lo)) {
-            set_error(std::string("vxrt_set_voxels_device: ") + what + " ends past its allocation");
+            set_error(std::string(who) + ": " + what + " ends past its allocation");
             return VXRT_E_INVALID;
         }
     } else {
@@ -33,25 +31,7 @@ int check_device_array(const vxrt_ctx* c, const void* p, size_t bytes, const cha
     return VXRT_OK;
 }
 
-}  // namespace
-}  // namespace vxrt
-
-extern "C" {
-
-int vxrt_set_voxels_device(vxrt_ctx* c, const int16_t (*pos)[3], const uint8_t (*mrgb)[4], size_t n) try {
-    if (!valid_ctx(c)) return VXRT_E_INVALID;
-    if (n != 0 && (!pos || !mrgb)) { set_error("null voxel arrays"); return VXRT_E_INVALID; }
-    if (uint64_t(n) >= (uint64_t(1) << 32)) { set_error("vxrt_set_voxels_device: 2^32 voxels or more"); return VXRT_E_INVALID; }
-    HIP_TRY(hipSetDevice(c->cfg.device));
-    if (n != 0) {
-        if (int rc = check_device_array(c, pos, n * 3 * sizeof(int16_t), "pos")) return rc;
-        if (int rc = check_device_array(c, mrgb, n * 4, "mrgb")) return rc;
-    }
-    // the old scene may still be read by frames in flight: drain them before it is replaced (this also orders the build behind
-    // everything enqueued on the context's stream, vxrt_context_wait_stream's events included)
-    if (int rc = sync_all(c)) return rc;
-    DeviceTree t;
-    if (int rc = build_svo_device_list(reinterpret_cast<const int16_t*>(pos), reinterpret_cast<const uint8_t*>(mrgb), n, c->stream, &t)) return rc;
+int install_device_tree(vxrt_ctx* c, const DeviceTree& t, const char* who) {
     ScratchBuffer svo, leaves, wide;   // owned here until installed
     svo.p = t.svo;
     leaves.p = t.leaves;
@@ -65,7 +45,7 @@ int vxrt_set_voxels_device(vxrt_ctx* c, const int16_t (*pos)[3], const uint8_t (
         if (hipError_t e = wide.alloc(w.size() * sizeof(WideRec)); e != hipSuccess) {
             (void)hipGetLastError();
             wide.p = nullptr;
-            return hip_fail(e, "vxrt_set_voxels_device: allocating the wide records");
+            return hip_fail(e, (std::string(who) + ": allocating the wide records").c_str());
         }
         HIP_TRY(hipMemcpy(wide.p, w.data(), w.size() * sizeof(WideRec), hipMemcpyHostToDevice));
         nwide = w.size();
@@ -74,6 +54,27 @@ int vxrt_set_voxels_device(vxrt_ctx* c, const int16_t (*pos)[3], const uint8_t (
     WideRec* d_wide = wide.as<WideRec>();
     svo.p = leaves.p = wide.p = nullptr;
     return install_scene(c, t.svo, t.svo_count, t.leaves, t.leaf_count, t.depth, t.root, d_wide, nwide, wide_root);
+}
+
+}  // namespace vxrt
+
+extern "C" {
+
+int vxrt_set_voxels_device(vxrt_ctx* c, const int16_t (*pos)[3], const uint8_t (*mrgb)[4], size_t n) try {
+    if (!valid_ctx(c)) return VXRT_E_INVALID;
+    if (n != 0 && (!pos || !mrgb)) { set_error("null voxel arrays"); return VXRT_E_INVALID; }
+    if (uint64_t(n) >= (uint64_t(1) << 32)) { set_error("vxrt_set_voxels_device: 2^32 voxels or more"); return VXRT_E_INVALID; }
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    if (n != 0) {
+        if (int rc = check_device_array(c, pos, n * 3 * sizeof(int16_t), "vxrt_set_voxels_device", "pos")) return rc;
+        if (int rc = check_device_array(c, mrgb, n * 4, "vxrt_set_voxels_device", "mrgb")) return rc;
+    }
+    // the old scene may still be read by frames in flight: drain them before it is replaced (this also orders the build behind
+    // everything enqueued on the context's stream, vxrt_context_wait_stream's events included)
+    if (int rc = sync_all(c)) return rc;
+    DeviceTree t;
+    if (int rc = build_svo_device_list(reinterpret_cast<const int16_t*>(pos), reinterpret_cast<const uint8_t*>(mrgb), n, c->stream, &t)) return rc;
+    return install_device_tree(c, t, "vxrt_set_voxels_device");
 } VXRT_CATCH
 
 }  // extern "C"

@@ -1,10 +1,12 @@
-// device_build.h — what api_device_scene.hip (host side of vxrt_device_scene.h) and device_build.hip (the builder) share.
+// device_build.h — what api_device_scene.hip (host side of vxrt_device_scene.h), device_build.hip (the list builder), grid_build.hip
+// (the dense-grid builder) and api_grid.hip (host side of vxrt_grid.h) share.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
 #include <cstdint>
 
+#include "ctx.h"
 #include "kernels.h"
 
 namespace vxrt {
@@ -25,5 +27,40 @@ struct DeviceTree {
 // result.  VXRT_E_SCENE: depth > 15 or 2^32 records or more; VXRT_E_DEVICE: an allocation or launch failed.  Nothing is allocated
 // on failure.  The pipeline is in device_build.hip and DESIGN.md §11.
 int build_svo_device_list(const int16_t* pos, const uint8_t* mrgb, size_t n, hipStream_t stream, DeviceTree* out);
+
+// The host builder's empty tree (the root {masks 0, base 1} and one zero leaf word).  `who` names the API call in error messages.
+int build_empty_tree(hipStream_t stream, const char* who, DeviceTree* out);
+
+// Stable LSD radix sort of (keys, vals), n entries, over the low `bits` key bits, 8 per pass, ping-ponging between keys[0] / vals[0]
+// and keys[1] / vals[1] starting at [*cur]; the result is in [*cur] on return.  hist: radix_hist_entries(n) words; totals: 256 words.
+size_t radix_hist_entries(size_t n);
+hipError_t radix_sort_pairs(uint64_t* keys[2], uint32_t* vals[2], uint32_t n, uint32_t bits, uint32_t* hist, uint32_t* totals,
+                            hipStream_t stream, int* cur);
+
+// The back half of both builders: the node levels over m > 0 unique path keys in ascending order (ukeys, m < 2^32) and their leaf
+// words (*leaves, exactly m int32, handed to *out on success) -> the records, one exact allocation.  ukeys is overwritten; spare
+// (the level ping-pong) holds at least m keys, or is null and then allocated at the leaf parents' count.  part: level_part_entries(m),
+// bins: level_bin_entries(m).  scratch: the caller's scratch bytes so far (out->scratch_bytes adds this call's own).  Waits for the
+// result.  VXRT_E_SCENE: 2^32 records or more; VXRT_E_DEVICE: an allocation failed.
+size_t level_part_entries(size_t m);
+size_t level_bin_entries(size_t m);
+int build_levels(uint64_t* ukeys, uint64_t* spare, size_t m, uint64_t* part, uint64_t* bins, uint32_t depth, ScratchBuffer* leaves,
+                 size_t scratch, hipStream_t stream, const char* who, DeviceTree* out);
+
+// u16::next_power_of_two().trailing_zeros() of |lo| and |hi| + 1 (scene_host.cpp: build_octree's depth rule over the coordinates' min
+// and max); may exceed 15
+inline uint32_t depth_of_bounds(int lo, int hi) {
+    auto ceil_log2_u16 = [](uint32_t v) { uint32_t bits = 0; while ((1u << bits) < v) bits++; return bits; };
+    const uint32_t dlo = ceil_log2_u16(uint32_t(lo < 0 ? -lo : lo) & 0xffffu);
+    const uint32_t dhi = ceil_log2_u16((uint32_t(hi < 0 ? -hi : hi) + 1u) & 0xffffu);
+    return dlo > dhi ? dlo : dhi;
+}
+
+// `bytes` at p must be device memory of the context's device, inside one allocation (api_device_scene.hip).  who: the API call.
+int check_device_array(const vxrt_ctx* c, const void* p, size_t bytes, const char* who, const char* what);
+
+// A tree built on the device -> the context's scene: the wide records when the context asks for them, then install_scene (which
+// owns the arrays from then on, or frees them on failure).  who: the API call.
+int install_device_tree(vxrt_ctx* c, const DeviceTree& t, const char* who);
 
 }  // namespace vxrt

@@ -345,13 +345,6 @@ __global__ __launch_bounds__(kThreads) void level_write_kernel(const uint64_t* k
     }
 }
 
-// u16::next_power_of_two().trailing_zeros() (scene_host.cpp: build_octree's depth rule)
-uint32_t ceil_log2_u16(uint32_t v) {
-    uint32_t bits = 0;
-    while ((1u << bits) < v) bits++;
-    return bits;
-}
-
 hipError_t alloc(ScratchBuffer* b, size_t bytes, size_t* total) {
     *total += bytes;
     const hipError_t e = b->alloc(bytes);
@@ -366,23 +359,119 @@ int fail(hipError_t e, const char* what) {
 
 }  // namespace
 
+size_t radix_hist_entries(size_t n) { return size_t(kDigits) * tiles(n); }
+
+hipError_t radix_sort_pairs(uint64_t* keys[2], uint32_t* vals[2], uint32_t n, uint32_t bits, uint32_t* hist, uint32_t* totals, hipStream_t s,
+                            int* cur) {
+    const uint32_t blocks = tiles(n);
+    for (uint32_t shift = 0; shift < bits; shift += 8u) {
+        const int c = *cur;
+        hipLaunchKernelGGL(radix_hist_kernel, dim3(blocks), dim3(kThreads), 0, s, keys[c], n, shift, blocks, hist);
+        if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+        hipLaunchKernelGGL(radix_scan_kernel, dim3(kDigits), dim3(kRowThreads), 0, s, hist, blocks, totals);
+        if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+        hipLaunchKernelGGL(radix_scatter_kernel, dim3(blocks), dim3(kThreads), 0, s, keys[c], vals[c], keys[c ^ 1], vals[c ^ 1], n, shift,
+                           blocks, hist, totals);
+        if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+        *cur = c ^ 1;
+    }
+    return hipSuccess;
+}
+
+size_t level_part_entries(size_t m) { return size_t(tiles(m)) + 1; }
+size_t level_bin_entries(size_t m) { return size_t(kLevelBins) * tiles(m) + kLevelBins; }
+
+int build_levels(uint64_t* ukeys, uint64_t* spare, size_t m, uint64_t* part, uint64_t* bins, uint32_t depth, ScratchBuffer* leaves,
+                 size_t scratch, hipStream_t s, const char* who, DeviceTree* out) {
+    ScratchBuffer svo, own_spare;
+    size_t outputs = 0;
+    const std::string w(who);
+    // every level's node count: level j (1 = the leaf parents .. depth + 1 = the root) has the unique keys that open a node there
+    const uint32_t mm = uint32_t(m), ublocks = tiles(m), top = depth + 1u;
+    hipLaunchKernelGGL(level_hist_kernel, dim3(ublocks), dim3(kThreads), 0, s, ukeys, mm, top, ublocks, bins);
+    HIP_TRY(hipGetLastError());
+    uint64_t* bin_sums = bins + size_t(kLevelBins) * ublocks;
+    hipLaunchKernelGGL(level_sum_kernel, dim3(kLevelBins), dim3(kRowThreads), 0, s, bins, ublocks, bin_sums);
+    HIP_TRY(hipGetLastError());
+    uint64_t bin[kLevelBins];
+    HIP_TRY(hipMemcpyAsync(bin, bin_sums, sizeof bin, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    uint64_t level_count[kLevelBins + 1] = {};   // [j], j = 1 .. top: the keys that open a node at level j or higher
+    level_count[top] = bin[top];
+    for (uint32_t j = top - 1u; j >= 1u; j--) level_count[j] = level_count[j + 1] + bin[j];
+    uint64_t level_start[kLevelBins + 2] = {};   // top-down: the root's level first
+    uint64_t nodes = 0;
+    for (uint32_t j = top; j >= 1u; j--) { level_start[j] = nodes; nodes += level_count[j]; }
+    if (level_count[top] != 1u) { set_error(w + ": internal error: the root level has " + std::to_string(level_count[top]) + " nodes"); return VXRT_E_SCENE; }
+    if (nodes > 0xffffffffull) { set_error(w + ": " + std::to_string(nodes) + " octree nodes: 2^32 or more"); return VXRT_E_SCENE; }
+    if (spare == nullptr && top > 1u) {   // the levels above the leaf parents ping-pong between ukeys and a buffer of the leaf parents' size
+        if (hipError_t e = alloc(&own_spare, size_t(level_count[1]) * sizeof(uint64_t), &scratch); e != hipSuccess) {
+            set_error(w + ": allocating the node keys: " + hipGetErrorString(e));
+            return VXRT_E_DEVICE;
+        }
+        spare = own_spare.as<uint64_t>();
+    }
+    if (hipError_t e = alloc(&svo, size_t(nodes) * sizeof(SvoRecord), &outputs); e != hipSuccess) {
+        set_error(w + ": allocating the records: " + hipGetErrorString(e));
+        return VXRT_E_DEVICE;
+    }
+
+    // the levels, bottom-up, each written at its top-down place
+    uint64_t* buf[2] = {ukeys, spare};
+    int cur = 0;
+    uint32_t below = mm;   // entries of the level below (the unique keys, then level j's nodes)
+    for (uint32_t j = 1; j <= top; j++) {
+        const uint32_t lb = tiles(below);
+        const uint64_t* in = buf[cur];
+        uint64_t* next = j < top ? buf[cur ^ 1] : nullptr;
+        hipLaunchKernelGGL(flag_count_kernel<false>, dim3(lb), dim3(kThreads), 0, s, in, below, part);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(launch_extract_scan(part, lb, s));
+        hipLaunchKernelGGL(level_write_kernel, dim3(lb), dim3(kThreads), 0, s, in, below, part, next, svo.as<SvoRecord>(),
+                           level_start[j], j == 1u ? 0ull : level_start[j - 1], j == 1u ? 1u : 0u);
+        HIP_TRY(hipGetLastError());
+        below = uint32_t(level_count[j]);
+        cur ^= 1;
+    }
+    SvoRecord root;
+    HIP_TRY(hipMemcpyAsync(&root, svo.p, sizeof root, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+
+    out->svo = svo.as<SvoRecord>(); out->svo_count = size_t(nodes); svo.p = nullptr;
+    out->leaves = leaves->as<int32_t>(); out->leaf_count = m; leaves->p = nullptr;
+    out->depth = depth;
+    out->root = root;
+    out->scratch_bytes = scratch;
+    return VXRT_OK;
+}
+
+int build_empty_tree(hipStream_t s, const char* who, DeviceTree* out) {
+    *out = DeviceTree{};
+    // the host builder's empty tree: the root {masks 0, base 1} and one zero leaf word (api_scene.hip: upload_svo)
+    ScratchBuffer svo, leaves;
+    size_t outputs = 0;
+    const SvoRecord root{0u, 1u};
+    const int32_t zero = 0;
+    hipError_t e = alloc(&svo, sizeof root, &outputs);
+    if (e == hipSuccess) e = alloc(&leaves, sizeof zero, &outputs);
+    if (e != hipSuccess) {
+        set_error(std::string(who) + ": allocating the " + (svo.p ? "leaf words: " : "records: ") + hipGetErrorString(e));
+        return VXRT_E_DEVICE;
+    }
+    HIP_TRY(hipMemcpyAsync(svo.p, &root, sizeof root, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(leaves.p, &zero, sizeof zero, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    out->svo = svo.as<SvoRecord>(); out->svo_count = 1; svo.p = nullptr;
+    out->leaves = leaves.as<int32_t>(); out->leaf_count = 1; leaves.p = nullptr;
+    out->root = root;
+    return VXRT_OK;
+}
+
 int build_svo_device_list(const int16_t* pos, const uint8_t* mrgb, size_t n, hipStream_t s, DeviceTree* out) {
     *out = DeviceTree{};
-    ScratchBuffer svo, leaves;
+    ScratchBuffer leaves;
     size_t scratch = 0, outputs = 0;
-    if (n == 0) {   // the host builder's empty tree: the root {masks 0, base 1} and one zero leaf word (api_scene.hip: upload_svo)
-        const SvoRecord root{0u, 1u};
-        const int32_t zero = 0;
-        if (hipError_t e = alloc(&svo, sizeof root, &outputs); e != hipSuccess) return fail(e, "the records");
-        if (hipError_t e = alloc(&leaves, sizeof zero, &outputs); e != hipSuccess) return fail(e, "the leaf words");
-        HIP_TRY(hipMemcpyAsync(svo.p, &root, sizeof root, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(leaves.p, &zero, sizeof zero, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        out->svo = svo.as<SvoRecord>(); out->svo_count = 1; svo.p = nullptr;
-        out->leaves = leaves.as<int32_t>(); out->leaf_count = 1; leaves.p = nullptr;
-        out->root = root;
-        return VXRT_OK;
-    }
+    if (n == 0) return build_empty_tree(s, "vxrt_set_voxels_device", out);
     const uint32_t nn = uint32_t(n);   // the caller refuses n >= 2^32
 
     // bounds -> depth
@@ -396,9 +485,7 @@ int build_svo_device_list(const int16_t* pos, const uint8_t* mrgb, size_t n, hip
     int2 lohi;
     HIP_TRY(hipMemcpyAsync(&lohi, bpart.as<int2>() + kBoundsBlocks, sizeof lohi, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
-    const uint32_t dlo = ceil_log2_u16(uint32_t(abs(lohi.x)) & 0xffffu);
-    const uint32_t dhi = ceil_log2_u16((uint32_t(abs(lohi.y)) + 1u) & 0xffffu);
-    const uint32_t depth = dlo > dhi ? dlo : dhi;
+    const uint32_t depth = depth_of_bounds(lohi.x, lohi.y);
     if (depth > 15) { set_error("octree depth > 15"); return VXRT_E_SCENE; }
 
     // scratch: keys and leaf words double-buffered, the digit counts, the scan partials, the level bins
@@ -420,18 +507,10 @@ int build_svo_device_list(const int16_t* pos, const uint8_t* mrgb, size_t n, hip
     HIP_TRY(hipGetLastError());
 
     // stable LSD radix sort over the key's 3(depth + 1) bits
+    uint64_t* kp[2] = {keys[0].as<uint64_t>(), keys[1].as<uint64_t>()};
+    uint32_t* vp[2] = {vals[0].as<uint32_t>(), vals[1].as<uint32_t>()};
     int cur = 0;
-    for (uint32_t shift = 0; shift < 3u * (depth + 1u); shift += 8u) {
-        hipLaunchKernelGGL(radix_hist_kernel, dim3(blocks), dim3(kThreads), 0, s, keys[cur].as<uint64_t>(), nn, shift, blocks, hist.as<uint32_t>());
-        HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(radix_scan_kernel, dim3(kDigits), dim3(kRowThreads), 0, s, hist.as<uint32_t>(), blocks, totals.as<uint32_t>());
-        HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(radix_scatter_kernel, dim3(blocks), dim3(kThreads), 0, s, keys[cur].as<uint64_t>(), vals[cur].as<uint32_t>(),
-                           keys[cur ^ 1].as<uint64_t>(), vals[cur ^ 1].as<uint32_t>(), nn, shift, blocks, hist.as<uint32_t>(),
-                           totals.as<uint32_t>());
-        HIP_TRY(hipGetLastError());
-        cur ^= 1;
-    }
+    HIP_TRY(radix_sort_pairs(kp, vp, nn, 3u * (depth + 1u), hist.as<uint32_t>(), totals.as<uint32_t>(), s, &cur));
 
     // dedupe: the last entry of each key -> the leaf words (exactly sized) and the unique keys (keys[cur ^ 1])
     hipLaunchKernelGGL(flag_count_kernel<true>, dim3(blocks), dim3(kThreads), 0, s, keys[cur].as<uint64_t>(), nn, part.as<uint64_t>());
@@ -446,51 +525,9 @@ int build_svo_device_list(const int16_t* pos, const uint8_t* mrgb, size_t n, hip
     HIP_TRY(hipGetLastError());
     cur ^= 1;
 
-    // every level's node count: level j (1 = the leaf parents .. depth + 1 = the root) has the unique keys that open a node there
-    const uint32_t mm = uint32_t(m), ublocks = tiles(m), top = depth + 1u;
-    hipLaunchKernelGGL(level_hist_kernel, dim3(ublocks), dim3(kThreads), 0, s, keys[cur].as<uint64_t>(), mm, top, ublocks, bins.as<uint64_t>());
-    HIP_TRY(hipGetLastError());
-    uint64_t* bin_sums = bins.as<uint64_t>() + size_t(kLevelBins) * ublocks;
-    hipLaunchKernelGGL(level_sum_kernel, dim3(kLevelBins), dim3(kRowThreads), 0, s, bins.as<uint64_t>(), ublocks, bin_sums);
-    HIP_TRY(hipGetLastError());
-    uint64_t bin[kLevelBins];
-    HIP_TRY(hipMemcpyAsync(bin, bin_sums, sizeof bin, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    uint64_t level_count[kLevelBins + 1] = {};   // [j], j = 1 .. top: the keys that open a node at level j or higher
-    level_count[top] = bin[top];
-    for (uint32_t j = top - 1u; j >= 1u; j--) level_count[j] = level_count[j + 1] + bin[j];
-    uint64_t level_start[kLevelBins + 2] = {};   // top-down: the root's level first
-    uint64_t nodes = 0;
-    for (uint32_t j = top; j >= 1u; j--) { level_start[j] = nodes; nodes += level_count[j]; }
-    if (level_count[top] != 1u) { set_error("vxrt_set_voxels_device: internal error: the root level has " + std::to_string(level_count[top]) + " nodes"); return VXRT_E_SCENE; }
-    if (nodes > 0xffffffffull) { set_error("vxrt_set_voxels_device: " + std::to_string(nodes) + " octree nodes: 2^32 or more"); return VXRT_E_SCENE; }
-    if (hipError_t e = alloc(&svo, size_t(nodes) * sizeof(SvoRecord), &outputs); e != hipSuccess) return fail(e, "the records");
-
-    // the levels, bottom-up, each written at its top-down place
-    uint32_t below = mm;   // entries of the level below (the unique keys, then level j's nodes)
-    for (uint32_t j = 1; j <= top; j++) {
-        const uint32_t lb = tiles(below);
-        const uint64_t* in = keys[cur].as<uint64_t>();
-        uint64_t* next = j < top ? keys[cur ^ 1].as<uint64_t>() : nullptr;
-        hipLaunchKernelGGL(flag_count_kernel<false>, dim3(lb), dim3(kThreads), 0, s, in, below, part.as<uint64_t>());
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(launch_extract_scan(part.as<uint64_t>(), lb, s));
-        hipLaunchKernelGGL(level_write_kernel, dim3(lb), dim3(kThreads), 0, s, in, below, part.as<uint64_t>(), next, svo.as<SvoRecord>(),
-                           level_start[j], j == 1u ? 0ull : level_start[j - 1], j == 1u ? 1u : 0u);
-        HIP_TRY(hipGetLastError());
-        below = uint32_t(level_count[j]);
-        cur ^= 1;
-    }
-    SvoRecord root;
-    HIP_TRY(hipMemcpyAsync(&root, svo.p, sizeof root, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-
-    out->svo = svo.as<SvoRecord>(); out->svo_count = size_t(nodes); svo.p = nullptr;
-    out->leaves = leaves.as<int32_t>(); out->leaf_count = size_t(m); leaves.p = nullptr;
-    out->depth = depth;
-    out->root = root;
-    out->scratch_bytes = scratch;
-    return VXRT_OK;
+    return build_levels(keys[cur].as<uint64_t>(), keys[cur ^ 1].as<uint64_t>(), size_t(m), part.as<uint64_t>(), bins.as<uint64_t>(), depth,
+                        &leaves, scratch, s, "vxrt_set_voxels_device", out);
 }
+
 
 }  // namespace vxrt

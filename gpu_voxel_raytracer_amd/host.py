@@ -39,6 +39,9 @@ OK, E_INVALID, E_DEVICE = 0, -1, -2
 E_VOX_MAGIC, E_VOX_VERSION, E_VOX_NOMAIN, E_VOX_EOF, E_VOX_CHUNK = -10, -11, -12, -13, -14
 E_VOX_MATERIAL, E_VOX_NOMATL, E_VOX_NOMODEL, E_IO, E_SCENE, E_NOSCENE, E_NOISE = -15, -16, -17, -18, -20, -21, -30
 
+# vxrt_grid_format (include/vxrt_grid.h)
+GRID_PALETTE8, GRID_WORD32 = 1, 2
+
 # vxrt_image
 SAMPLED_COLOR, NORMAL_DEPTH, ALBEDO_NODE, ACCUM_COLOR, DENOISED = range(5)
 # the displayed frame: DENOISED encoded to 8-bit sRGB on the GPU by the library's exact rule (vxrt.h), 4 bytes per pixel
@@ -528,6 +531,50 @@ class Context:
         self._chk(self._L.vxrt_set_voxels_device(self._h, C.c_void_p(pos.data_ptr() if len(pos) else None),
                                                  C.c_void_p(mrgb.data_ptr() if len(pos) else None), C.c_size_t(len(pos))),
                   "vxrt_set_voxels_device")
+
+    def set_voxel_grid(self, cells, origin=(0, 0, 0), palette=None):
+        """vxrt_set_voxel_grid (include/vxrt_grid.h): the scene of a dense grid.  cells: a torch tensor [nx, ny, nz] on the context's
+        device (or a numpy array, uploaded with torch first); cell (i, j, k) is the voxel at origin + (i, j, k).  uint8 cells are
+        palette indices (GRID_PALETTE8: 0 empty, palette [256, 4] uint8 of (material, r, g, b) required); int32 cells are leaf words
+        (GRID_WORD32: bit 31 set = a voxel).  The context's stream first waits for torch's current stream.  Same records, stats and
+        frames as recreate_octree of the occupied cells as a list."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        cells = torch.as_tensor(cells, device=dev) if isinstance(cells, np.ndarray) else cells
+        if not isinstance(cells, torch.Tensor) or cells.dim() != 3:
+            raise TypeError("cells must be a 3-D torch tensor or numpy array")
+        if cells.device != dev:
+            raise ValueError(f"cells must be on {dev}")
+        fmt = {torch.uint8: GRID_PALETTE8, torch.int32: GRID_WORD32}.get(cells.dtype)
+        if fmt is None:
+            raise ValueError("cells must be uint8 (palette indices) or int32 (leaf words)")
+        cells = cells.contiguous()
+        pal = None if palette is None else np.ascontiguousarray(np.asarray(palette, np.uint8).reshape(256, 4))
+        dims = (C.c_uint32 * 3)(*cells.shape)
+        org = (C.c_int32 * 3)(*(int(v) for v in origin))
+        self.context_wait_stream(torch.cuda.current_stream(dev).cuda_stream)
+        self._chk(self._L.vxrt_set_voxel_grid(self._h, C.c_void_p(cells.data_ptr() if cells.numel() else None), C.c_int(fmt), dims, org,
+                                              _p(pal)), "vxrt_set_voxel_grid")
+
+    def get_voxel_grid(self, origin, dims, out=None):
+        """vxrt_get_voxel_grid: the box origin + [0, dims) of the scene as it stands (after edits) -> an int32 torch tensor
+        [nx, ny, nz] of leaf words on the context's device (0: empty or outside the root cube), or into `out` (int32, contiguous, that
+        shape).  Ordered on both sides against torch's current stream: the tensor may be used by the next torch op without a sync."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        shape = tuple(int(v) for v in dims)
+        if len(shape) != 3 or min(shape) < 0:
+            raise ValueError("dims must be three sizes")
+        if out is None:
+            out = torch.empty(shape, dtype=torch.int32, device=dev)
+        elif out.dtype != torch.int32 or tuple(out.shape) != shape or out.device != dev or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous int32 tensor of shape {shape} on {dev}")
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        self.context_wait_stream(stream)
+        self._chk(self._L.vxrt_get_voxel_grid(self._h, (C.c_int32 * 3)(*(int(v) for v in origin)), (C.c_uint32 * 3)(*shape),
+                                              C.c_void_p(out.data_ptr() if out.numel() else None)), "vxrt_get_voxel_grid")
+        self.stream_wait_context(stream)
+        return out
 
     def set_menger(self, level, clip=0, mrgb=(0, 0xb0, 0xd0, 0x60), emissive_period=0):
         """Procedural Menger sponge built straight into the device scene format (BASELINE config 5)."""

@@ -25,6 +25,7 @@
  * An optional extension for hosts that edit a loaded scene in place and pick the voxel under a ray: vxrt_edit.h.
  * An optional extension for hosts that read a loaded scene's voxels back, whole or by box: vxrt_extract.h.
  * An optional extension for hosts that build a scene on the device from a voxel list in device memory: vxrt_device_scene.h.
+ * An optional extension for hosts that build a scene from a dense voxel grid in device memory and read boxes back as grids: vxrt_grid.h.
  */
 #ifndef VXRT_H
 #define VXRT_H

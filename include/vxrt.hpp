@@ -19,6 +19,7 @@
 #include "vxrt_device_scene.h"
 #include "vxrt_edit.h"
 #include "vxrt_extract.h"
+#include "vxrt_grid.h"
 #include "vxrt_host.h"
 
 namespace vxrt {
@@ -192,6 +193,17 @@ class Context {
     // context's stream (a producer on another stream calls context_wait_stream first); the octree is built on the device
     void set_voxels_device(const int16_t (*pos)[3], const uint8_t (*mrgb)[4], size_t n) {
         check(vxrt_set_voxels_device(ctx_, pos, mrgb, n), "vxrt_set_voxels_device");
+    }
+    // vxrt_set_voxel_grid (vxrt_grid.h): dims[0] x dims[1] x dims[2] cells in device memory of the context's device, C order
+    // [x][y][z], cell (i, j, k) at origin + (i, j, k); palette: 256 entries for VXRT_GRID_PALETTE8, nullptr for VXRT_GRID_WORD32
+    void set_voxel_grid(const void* cells, vxrt_grid_format format, const std::array<uint32_t, 3>& dims,
+                        const std::array<int32_t, 3>& origin = {0, 0, 0}, const uint8_t (*palette)[4] = nullptr) {
+        check(vxrt_set_voxel_grid(ctx_, cells, format, dims.data(), origin.data(), palette), "vxrt_set_voxel_grid");
+    }
+    // vxrt_get_voxel_grid: the box origin + [0, dims) as leaf words into device memory, enqueued on the context's stream (a consumer on
+    // another stream calls stream_wait_context first)
+    void get_voxel_grid(const std::array<int32_t, 3>& origin, const std::array<uint32_t, 3>& dims, uint32_t* cells) {
+        check(vxrt_get_voxel_grid(ctx_, origin.data(), dims.data(), cells), "vxrt_get_voxel_grid");
     }
     void set_menger(uint32_t level, uint32_t clip, std::array<uint8_t, 4> mrgb, uint32_t emissive_period) {
         check(vxrt_set_menger(ctx_, level, clip, mrgb.data(), emissive_period), "vxrt_set_menger");
