@@ -2,7 +2,9 @@
 // The batch is sorted and cut into per-level segments here (the edits are in host memory already, and the cut is key arithmetic
 // only); the tree surgery runs on the device (edit.hip: edit_kernel).  DESIGN.md "Scene edits".
 #include <algorithm>
+#include <climits>
 #include <cmath>
+#include <cstring>
 
 #include "ctx.h"
 #include "edit.h"
@@ -54,6 +56,135 @@ template <typename T> hipError_t grow_to(T** p, size_t used, size_t cap, T** fre
 size_t grown_capacity(size_t cap, size_t need) { return std::max(need, cap + cap / 2 + 4096); }
 
 }  // namespace
+
+namespace {
+
+// the storage for `svo_need` records and `leaf_need` leaf words: fresh arrays (*new_svo / *new_leaves, at the capacities *svo_grow /
+// *leaf_grow) where the current ones are too small, nullptr where they are not.  Nothing changes in the context; nothing is left
+// allocated on failure.
+int grow_storage(vxrt_ctx* c, size_t svo_need, size_t leaf_need, SvoRecord** new_svo, int32_t** new_leaves, size_t* svo_grow,
+                 size_t* leaf_grow) {
+    *new_svo = nullptr;
+    *new_leaves = nullptr;
+    const size_t svo_cap = c->svo_cap ? c->svo_cap : c->svo_count, leaf_cap = c->leaf_cap ? c->leaf_cap : c->leaf_count;
+    if (svo_need >= (size_t(1) << 32) || leaf_need >= (size_t(1) << 32)) { set_error("the edited scene would exceed 2^32 records"); return VXRT_E_SCENE; }
+    *svo_grow = svo_need > svo_cap ? grown_capacity(svo_cap, svo_need) : 0;
+    *leaf_grow = leaf_need > leaf_cap ? grown_capacity(leaf_cap, leaf_need) : 0;
+    if (*svo_grow) HIP_TRY(grow_to(&c->d_svo, c->svo_count, *svo_grow, new_svo));
+    if (*leaf_grow) {
+        const hipError_t e = grow_to(&c->d_leaves, c->leaf_count, *leaf_grow, new_leaves);
+        if (e != hipSuccess) { if (*new_svo) (void)hipFree(*new_svo); *new_svo = nullptr; return hip_fail(e, "growing the scene's leaf words"); }
+    }
+    if (*svo_grow || *leaf_grow) HIP_TRY(hipDeviceSynchronize());   // the copies and fills ran on the null stream; the edit runs on c->stream
+    return VXRT_OK;
+}
+
+// the grown storage replaces the old
+void commit_storage(vxrt_ctx* c, SvoRecord* new_svo, int32_t* new_leaves, size_t svo_grow, size_t leaf_grow) {
+    if (new_svo) { (void)hipFree(c->d_svo); c->d_svo = new_svo; c->svo_cap = svo_grow; }
+    if (new_leaves) { (void)hipFree(c->d_leaves); c->d_leaves = new_leaves; c->leaf_cap = leaf_grow; }
+}
+
+}  // namespace
+
+int reserve_edit_storage(vxrt_ctx* c, size_t nodes, size_t parents) {
+    SvoRecord* new_svo;
+    int32_t* new_leaves;
+    size_t svo_grow, leaf_grow;
+    if (int rc = grow_storage(c, c->svo_count + 8 * nodes, c->leaf_count + 8 * parents, &new_svo, &new_leaves, &svo_grow, &leaf_grow))
+        return rc;
+    commit_storage(c, new_svo, new_leaves, svo_grow, leaf_grow);
+    return VXRT_OK;
+}
+
+int apply_edit_batch(vxrt_ctx* c, const EditBatch& b) {
+    const bool clear = b.clear;
+    const uint32_t L = c->depth;
+    const size_t node_segs = b.seg_off[L + 1];
+
+    // storage: a set may give every touched node of levels 0 .. L-1 a new block of 8 records, every leaf parent 8 leaf words
+    const size_t svo_need = clear ? 0 : c->svo_count + 8 * size_t(b.seg_off[L]);
+    const size_t leaf_need = clear ? 0 : c->leaf_count + 8 * size_t(b.seg_off[L + 1] - b.seg_off[L]);
+    if (svo_need >= (size_t(1) << 32) || leaf_need >= (size_t(1) << 32)) { set_error("the edited scene would exceed 2^32 records"); return VXRT_E_SCENE; }
+
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    if (int rc = sync_all(c)) return rc;   // frames enqueued before the edit see the old scene
+    SvoRecord* new_svo = nullptr;
+    int32_t* new_leaves = nullptr;
+    size_t svo_grow = 0, leaf_grow = 0;
+    if (int rc = grow_storage(c, svo_need, leaf_need, &new_svo, &new_leaves, &svo_grow, &leaf_grow)) return rc;
+    // host batches: one scratch of  the arrays | node scratch | flag scratch | out
+    const size_t o_node = (b.host_bytes + 3) & ~size_t(3), o_flag = o_node + node_segs * 4;
+    const size_t o_out = (o_flag + node_segs + 15) & ~size_t(15), bytes = o_out + 8 * 4;
+    ScratchBuffer scratch;
+    if (b.host) {
+        if (hipError_t e = scratch.alloc(bytes); e != hipSuccess) {
+            if (new_svo) (void)hipFree(new_svo);
+            if (new_leaves) (void)hipFree(new_leaves);
+            return hip_fail(e, "edit batch");
+        }
+    }
+    // from here on the edit happens
+    commit_storage(c, new_svo, new_leaves, svo_grow, leaf_grow);
+    if (!c->edited) { c->edited = true; c->svo_built = c->svo_count; c->leaf_built = c->leaf_count; }
+    EditArgs a{};
+    memcpy(a.seg_off, b.seg_off, sizeof a.seg_off);
+    if (b.host) {
+        char* s = scratch.as<char>();
+        HIP_TRY(hipMemcpy(s, b.host, b.host_bytes, hipMemcpyHostToDevice));
+        a.child_begin = reinterpret_cast<const uint32_t*>(s);
+        a.words = reinterpret_cast<const int32_t*>(s + b.host_words);
+        a.oct = reinterpret_cast<const uint8_t*>(s + b.host_oct);
+        a.node = reinterpret_cast<uint32_t*>(s + o_node);
+        a.flag = reinterpret_cast<uint8_t*>(s + o_flag);
+        a.out = reinterpret_cast<uint32_t*>(s + o_out);
+    } else {
+        a.child_begin = b.child_begin;
+        a.words = b.words;
+        a.oct = b.oct;
+        a.node = b.node;
+        a.flag = b.flag;
+        a.out = b.out;
+    }
+    a.svo = c->d_svo;
+    a.leaves = c->d_leaves;
+    a.depth = L;
+    a.svo_end = uint32_t(c->svo_count);
+    a.leaf_end = uint32_t(c->leaf_count);
+    a.svo_built = uint32_t(c->svo_built);
+    a.leaf_built = uint32_t(c->leaf_built);
+    a.clear = clear ? 1 : 0;
+    const bool was_empty = (c->root_rec.masks & 0xffffu) == 0u;
+    HIP_TRY(launch_edit(a, c->stream));
+    uint32_t out[8];
+    HIP_TRY(hipMemcpyAsync(out, a.out, sizeof out, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    c->svo_count = out[0];
+    c->leaf_count = out[1];
+    c->live_nodes = clear ? c->live_nodes - out[2] : c->live_nodes + out[2];
+    c->root_rec = SvoRecord{out[3], out[4]};
+    drop_touch_maps(c);   // sized for the records before the edit; the DDA prototype's grid is of the old scene
+
+    // the sky cull's box grows to hold every set voxel's cell of level min(depth, 7); a clear never shrinks it (the cull is exact
+    // for any box that holds the scene).  A scene without a box keeps none (its top levels were too large to read back), unless it
+    // was empty: then the set voxels are all of it.  A cell's bounds are monotone in its position, so the set voxels' least and
+    // greatest positions per axis give the box that growing it voxel by voxel gives.
+    if (!clear && (c->box_valid || was_empty)) {
+        const uint32_t Lc = L < 7u ? L : 7u;
+        const float cell = ldexpf(c->root_size, -int(Lc));
+        const int32_t half = int32_t(1) << L;
+        for (int ax = 0; ax < 3; ax++) {
+            const float root_min = c->root_center[ax] - 0.5f * c->root_size;
+            const uint32_t clo = uint32_t(b.lo[ax] + half) >> (L + 1 - Lc), chi = uint32_t(b.hi[ax] + half) >> (L + 1 - Lc);
+            const float lo = root_min + float(clo) * cell, hi = root_min + float(chi + 1u) * cell;
+            c->box_min[ax] = c->box_valid ? std::min(c->box_min[ax], lo) : lo;
+            c->box_max[ax] = c->box_valid ? std::max(c->box_max[ax], hi) : hi;
+        }
+        c->box_valid = true;
+    }
+    return VXRT_OK;
+}
+
 }  // namespace vxrt
 
 extern "C" {
@@ -124,92 +255,31 @@ int vxrt_edit_voxels(vxrt_ctx* c, const int16_t (*pos)[3], const uint8_t (*mrgb)
     }
     child_begin[node_segs] = uint32_t(total);
 
-    // storage: a set may give every touched node of levels 0 .. L-1 a new block of 8 records, every leaf parent 8 leaf words
-    const size_t svo_cap = c->svo_cap ? c->svo_cap : c->svo_count, leaf_cap = c->leaf_cap ? c->leaf_cap : c->leaf_count;
-    const size_t svo_need = clear ? 0 : c->svo_count + 8 * size_t(a.seg_off[L]);
-    const size_t leaf_need = clear ? 0 : c->leaf_count + 8 * size_t(a.seg_off[L + 1] - a.seg_off[L]);
-    if (svo_need >= (size_t(1) << 32) || leaf_need >= (size_t(1) << 32)) { set_error("the edited scene would exceed 2^32 records"); return VXRT_E_SCENE; }
-
-    HIP_TRY(hipSetDevice(c->cfg.device));
-    if (int rc = sync_all(c)) return rc;   // frames enqueued before the edit see the old scene
-    SvoRecord* new_svo = nullptr;
-    int32_t* new_leaves = nullptr;
-    const size_t svo_grow = svo_need > svo_cap ? grown_capacity(svo_cap, svo_need) : 0;
-    const size_t leaf_grow = leaf_need > leaf_cap ? grown_capacity(leaf_cap, leaf_need) : 0;
-    if (svo_grow) HIP_TRY(grow_to(&c->d_svo, c->svo_count, svo_grow, &new_svo));
-    if (leaf_grow) {
-        const hipError_t e = grow_to(&c->d_leaves, c->leaf_count, leaf_grow, &new_leaves);
-        if (e != hipSuccess) { if (new_svo) (void)hipFree(new_svo); return hip_fail(e, "growing the scene's leaf words"); }
-    }
-    if (svo_grow || leaf_grow) HIP_TRY(hipDeviceSynchronize());   // the copies and fills ran on the null stream; the edit runs on c->stream
-    // the batch (one upload): child_begin | node scratch | words | oct | flag scratch | out
+    EditBatch b;
+    memcpy(b.seg_off, a.seg_off, sizeof b.seg_off);
+    b.clear = clear;
+    // the batch (one upload): child_begin | words | oct
     std::vector<int32_t> words(clear ? 0 : m);
     for (size_t i = 0; i < words.size(); i++) {
         const uint8_t* v = mrgb[idx[i]];
         words[i] = int32_t(0x80000000u | uint32_t(v[0] & 0x7f) << 24 | uint32_t(v[1]) << 16 | uint32_t(v[2]) << 8 | v[3]);
     }
-    const size_t o_node = (node_segs + 1) * 4, o_words = o_node + node_segs * 4, o_oct = o_words + words.size() * 4;
-    const size_t o_flag = (o_oct + total + 3) & ~size_t(3), o_out = (o_flag + node_segs + 15) & ~size_t(15), bytes = o_out + 8 * 4;
-    std::vector<uint8_t> host(o_flag, 0);
+    b.host_words = (node_segs + 1) * 4;
+    b.host_oct = b.host_words + words.size() * 4;
+    b.host_bytes = b.host_oct + total;
+    std::vector<uint8_t> host(b.host_bytes, 0);
     memcpy(host.data(), child_begin.data(), child_begin.size() * 4);
-    memcpy(host.data() + o_words, words.data(), words.size() * 4);
-    memcpy(host.data() + o_oct, oct.data(), total);
-    ScratchBuffer scratch;
-    if (hipError_t e = scratch.alloc(bytes); e != hipSuccess) {
-        if (new_svo) (void)hipFree(new_svo);
-        if (new_leaves) (void)hipFree(new_leaves);
-        return hip_fail(e, "edit batch");
-    }
-    // from here on the edit happens: the grown storage replaces the old
-    if (new_svo) { (void)hipFree(c->d_svo); c->d_svo = new_svo; c->svo_cap = svo_grow; }
-    if (new_leaves) { (void)hipFree(c->d_leaves); c->d_leaves = new_leaves; c->leaf_cap = leaf_grow; }
-    if (!c->edited) { c->edited = true; c->svo_built = c->svo_count; c->leaf_built = c->leaf_count; }
-    char* s = scratch.as<char>();
-    HIP_TRY(hipMemcpy(s, host.data(), host.size(), hipMemcpyHostToDevice));
-    a.svo = c->d_svo;
-    a.leaves = c->d_leaves;
-    a.child_begin = reinterpret_cast<const uint32_t*>(s);
-    a.node = reinterpret_cast<uint32_t*>(s + o_node);
-    a.words = reinterpret_cast<const int32_t*>(s + o_words);
-    a.oct = reinterpret_cast<const uint8_t*>(s + o_oct);
-    a.flag = reinterpret_cast<uint8_t*>(s + o_flag);
-    a.out = reinterpret_cast<uint32_t*>(s + o_out);
-    a.depth = L;
-    a.svo_end = uint32_t(c->svo_count);
-    a.leaf_end = uint32_t(c->leaf_count);
-    a.svo_built = uint32_t(c->svo_built);
-    a.leaf_built = uint32_t(c->leaf_built);
-    a.clear = clear ? 1 : 0;
-    const bool was_empty = (c->root_rec.masks & 0xffffu) == 0u;
-    HIP_TRY(launch_edit(a, c->stream));
-    uint32_t out[8];
-    HIP_TRY(hipMemcpyAsync(out, a.out, sizeof out, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    c->svo_count = out[0];
-    c->leaf_count = out[1];
-    c->live_nodes = clear ? c->live_nodes - out[2] : c->live_nodes + out[2];
-    c->root_rec = SvoRecord{out[3], out[4]};
-    drop_touch_maps(c);   // sized for the records before the edit; the DDA prototype's grid is of the old scene
-
-    // the sky cull's box grows to hold every set voxel's cell of level min(depth, 7); a clear never shrinks it (the cull is exact
-    // for any box that holds the scene).  A scene without a box keeps none (its top levels were too large to read back), unless it
-    // was empty: then the set voxels are all of it.
-    if (!clear && (c->box_valid || was_empty)) {
-        const uint32_t Lc = L < 7u ? L : 7u;
-        const float cell = ldexpf(c->root_size, -int(Lc));
-        for (size_t i = 0; i < m; i++) {
-            const int16_t* p = pos[idx[i]];
-            for (int ax = 0; ax < 3; ax++) {
-                const uint32_t cidx = uint32_t(int32_t(p[ax]) + half) >> (L + 1 - Lc);
-                const float root_min = c->root_center[ax] - 0.5f * c->root_size;
-                const float lo = root_min + float(cidx) * cell, hi = root_min + float(cidx + 1u) * cell;
-                c->box_min[ax] = c->box_valid ? std::min(c->box_min[ax], lo) : lo;
-                c->box_max[ax] = c->box_valid ? std::max(c->box_max[ax], hi) : hi;
-            }
-            c->box_valid = true;
+    memcpy(host.data() + b.host_words, words.data(), words.size() * 4);
+    memcpy(host.data() + b.host_oct, oct.data(), total);
+    b.host = host.data();
+    // the set voxels' bounds (the sky cull's box)
+    for (int ax = 0; ax < 3; ax++) { b.lo[ax] = INT32_MAX; b.hi[ax] = INT32_MIN; }
+    for (size_t i = 0; i < m; i++)
+        for (int ax = 0; ax < 3; ax++) {
+            b.lo[ax] = std::min(b.lo[ax], int32_t(pos[idx[i]][ax]));
+            b.hi[ax] = std::max(b.hi[ax], int32_t(pos[idx[i]][ax]));
         }
-    }
-    return VXRT_OK;
+    return apply_edit_batch(c, b);
 } VXRT_CATCH
 
 int vxrt_pick(vxrt_ctx* c, const float (*origins)[3], const float (*dirs)[3], size_t n, vxrt_pick_hit* out) try {

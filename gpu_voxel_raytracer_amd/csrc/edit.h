@@ -31,6 +31,32 @@ struct EditArgs {
 };
 
 hipError_t launch_edit(const EditArgs& a, hipStream_t s);
+
+// A batch cut into segments, as the tail of an edit takes it (api_edit.hip: apply_edit_batch).  vxrt_edit_voxels cuts on the host
+// and hands the arrays over in `host` (child_begin | words | oct, uploaded in one copy); vxrt_edit_voxel_grid cuts on the device
+// and gives the device arrays and the kernel's scratch (node, flag: seg_off[depth + 1] entries each; out: 8 words) itself.
+struct EditBatch {
+    uint32_t seg_off[18];                       // as EditArgs, levels 0 .. depth + 1 and the end
+    bool clear = false;
+    int32_t lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};   // sets: the least and greatest set position per axis (the sky cull's box grows by them)
+    const uint8_t* host = nullptr;              // host arrays: `host_bytes` bytes, words at host_words, oct at host_oct
+    size_t host_bytes = 0, host_words = 0, host_oct = 0;
+    const uint32_t* child_begin = nullptr;      // device arrays (host == nullptr)
+    const uint8_t* oct = nullptr;
+    const int32_t* words = nullptr;
+    uint32_t* node = nullptr;
+    uint8_t* flag = nullptr;
+    uint32_t* out = nullptr;
+};
+
+// Room for a set batch with `nodes` segments on node levels 0 .. depth - 1 and `parents` leaf parents: the storage grows
+// (geometrically) when it has to.  VXRT_E_SCENE: 2^32 records or leaf words; VXRT_E_DEVICE: the storage could not grow (nothing
+// changed).  Call after sync_all.
+int reserve_edit_storage(vxrt_ctx* c, size_t nodes, size_t parents);
+
+// The tail of an edit, shared by vxrt_edit_voxels and vxrt_edit_voxel_grid: storage growth, the `edited` bookkeeping, the launch, the
+// counters, the touch maps and the sky cull's box.  Drains the frames in flight first; waits for the edit.  All or nothing.
+int apply_edit_batch(vxrt_ctx* c, const EditBatch& b);
 hipError_t launch_pick(const TraceArgs& a, const float* origins, const float* dirs, vxrt_pick_hit* out, unsigned n, hipStream_t s);
 
 }  // namespace vxrt

@@ -1,4 +1,5 @@
-// grid.h — what api_grid.hip (host side of vxrt_grid.h) and grid_build.hip (its kernels) share.  DESIGN.md §12.
+// grid.h — what api_grid.hip (host side of vxrt_grid.h), grid_build.hip (its kernels) and grid_edit.hip (vxrt_grid_edit.h) share.
+// DESIGN.md §12, §13.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -18,6 +19,86 @@ struct GridDesc {
     int32_t t0[3];     // the first 16-aligned tile per axis: floor(o / 16)
     uint32_t nt[3];    // tiles per axis
 };
+
+// ---- device helpers of the grid kernels (grid_build.hip, grid_edit.hip) -------------------------------------------------------
+// 4 bits per axis, x highest: bit k of x -> bit 3k + 2, of y -> 3k + 1, of z -> 3k
+__device__ __forceinline__ uint32_t morton4(uint32_t x, uint32_t y, uint32_t z) {
+    uint32_t m = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < 4; k++) m |= ((x >> k) & 1u) << (3u * k + 2u) | ((y >> k) & 1u) << (3u * k + 1u) | ((z >> k) & 1u) << (3u * k);
+    return m;
+}
+
+__device__ __forceinline__ uint64_t morton_tile(uint32_t x, uint32_t y, uint32_t z, uint32_t bits) {
+    uint64_t m = 0;
+    for (uint32_t k = 0; k < bits; k++)
+        m |= uint64_t(((x >> k) & 1u) << 2 | ((y >> k) & 1u) << 1 | ((z >> k) & 1u)) << (3u * k);
+    return m;
+}
+
+// The 16 cells p = (px, py, pz0 .. pz0 + 15) as leaf words (0: empty or outside the grid's box; the box may be any int32 box).  A row wholly inside the box whose
+// address is 16-byte aligned is read with 16-byte loads (one for uint8 cells, four for uint32 cells).
+__device__ __forceinline__ void load_row(const GridDesc& g, const uint32_t* pal, int px, int py, int pz0, uint32_t w[16]) {
+#pragma unroll
+    for (int k = 0; k < 16; k++) w[k] = 0u;
+    const int64_t i = int64_t(px) - g.o[0], j = int64_t(py) - g.o[1], k0 = int64_t(pz0) - g.o[2], n2 = g.n[2];
+    if (i < 0 || i >= int64_t(g.n[0]) || j < 0 || j >= int64_t(g.n[1])) return;
+    const size_t row = (size_t(i) * g.n[1] + size_t(j)) * g.n[2];
+    const bool whole = k0 >= 0 && k0 + 16 <= n2;
+    if (g.format == 1u) {
+        const uint8_t* q = static_cast<const uint8_t*>(g.cells) + row;
+        if (whole && (reinterpret_cast<uintptr_t>(q + k0) & 15u) == 0u) {
+            const uint4 v = *reinterpret_cast<const uint4*>(q + k0);
+            const uint32_t b[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+            for (int k = 0; k < 16; k++) w[k] = pal[(b[k >> 2] >> (8 * (k & 3))) & 0xffu];
+            return;
+        }
+#pragma unroll
+        for (int k = 0; k < 16; k++)
+            if (k0 + k >= 0 && k0 + k < n2) w[k] = pal[q[k0 + k]];
+    } else {
+        const uint32_t* q = static_cast<const uint32_t*>(g.cells) + row;
+        if (whole && (reinterpret_cast<uintptr_t>(q + k0) & 15u) == 0u) {
+#pragma unroll
+            for (int v4 = 0; v4 < 4; v4++) {
+                const uint4 v = reinterpret_cast<const uint4*>(q + k0)[v4];
+                w[4 * v4 + 0] = v.x; w[4 * v4 + 1] = v.y; w[4 * v4 + 2] = v.z; w[4 * v4 + 3] = v.w;
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < 16; k++)
+                if (k0 + k >= 0 && k0 + k < n2) w[k] = q[k0 + k];
+        }
+#pragma unroll
+        for (int k = 0; k < 16; k++) w[k] = w[k] >> 31 ? w[k] : 0u;
+    }
+}
+
+__device__ __forceinline__ void tile_coords(const GridDesc& g, uint32_t tile, int* tx, int* ty, int* tz) {
+    *tz = g.t0[2] + int(tile % g.nt[2]);
+    const uint32_t r = tile / g.nt[2];
+    *ty = g.t0[1] + int(r % g.nt[1]);
+    *tx = g.t0[0] + int(r / g.nt[1]);
+}
+
+// The leaf word of the voxel at u = p + 2^depth (u inside the root cube [0, 2^(depth+1))^3), 0 where there is none: the descent from
+// the root record along base + popc(mask & (bit(s) - 1)), as extract.hip walks, so it reads every layout of the 8-byte records.
+__device__ __forceinline__ uint32_t leaf_at(const SvoRecord* svo, const int32_t* leaves, uint32_t depth, uint32_t ux, uint32_t uy,
+                                            uint32_t uz) {
+    uint32_t node = 0;
+    for (uint32_t l = 0; l <= depth; l++) {
+        const uint2 r = *reinterpret_cast<const uint2*>(svo + node);
+        const uint32_t b = depth - l;
+        const uint32_t s = ((ux >> b) & 1u) << 2 | ((uy >> b) & 1u) << 1 | ((uz >> b) & 1u);
+        const uint32_t mask = l == depth ? (r.x >> 8) & 0xffu : r.x & 0xffu;
+        if (!((mask >> s) & 1u)) return 0u;
+        const uint32_t slot = r.y + uint32_t(__popc(mask & ((1u << s) - 1u)));
+        if (l == depth) return uint32_t(leaves[slot]);
+        node = slot;
+    }
+    return 0u;
+}
 
 // The scene of the grid's occupied cells, exactly as build_svo_device_list builds it from them as a list.  pal: for format 1, 256
 // leaf words in device memory (entry 0 = 0).  The grid is read on `stream` behind what is enqueued there; waits for the result.

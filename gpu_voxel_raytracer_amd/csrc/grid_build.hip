@@ -42,67 +42,6 @@ struct Stat {
     int lo, hi;
 };
 
-// 4 bits per axis, x highest: bit k of x -> bit 3k + 2, of y -> 3k + 1, of z -> 3k
-__device__ __forceinline__ uint32_t morton4(uint32_t x, uint32_t y, uint32_t z) {
-    uint32_t m = 0;
-#pragma unroll
-    for (uint32_t k = 0; k < 4; k++) m |= ((x >> k) & 1u) << (3u * k + 2u) | ((y >> k) & 1u) << (3u * k + 1u) | ((z >> k) & 1u) << (3u * k);
-    return m;
-}
-
-__device__ __forceinline__ uint64_t morton_tile(uint32_t x, uint32_t y, uint32_t z, uint32_t bits) {
-    uint64_t m = 0;
-    for (uint32_t k = 0; k < bits; k++)
-        m |= uint64_t(((x >> k) & 1u) << 2 | ((y >> k) & 1u) << 1 | ((z >> k) & 1u)) << (3u * k);
-    return m;
-}
-
-// The 16 cells p = (px, py, pz0 .. pz0 + 15) as leaf words (0: empty or outside the grid's box).  A row wholly inside the box whose
-// address is 16-byte aligned is read with 16-byte loads (one for uint8 cells, four for uint32 cells).
-__device__ __forceinline__ void load_row(const GridDesc& g, const uint32_t* pal, int px, int py, int pz0, uint32_t w[16]) {
-#pragma unroll
-    for (int k = 0; k < 16; k++) w[k] = 0u;
-    const int i = px - g.o[0], j = py - g.o[1], k0 = pz0 - g.o[2];
-    if (i < 0 || i >= int(g.n[0]) || j < 0 || j >= int(g.n[1])) return;
-    const size_t row = (size_t(i) * g.n[1] + size_t(j)) * g.n[2];
-    const bool whole = k0 >= 0 && k0 + 16 <= int(g.n[2]);
-    if (g.format == 1u) {
-        const uint8_t* q = static_cast<const uint8_t*>(g.cells) + row;
-        if (whole && (reinterpret_cast<uintptr_t>(q + k0) & 15u) == 0u) {
-            const uint4 v = *reinterpret_cast<const uint4*>(q + k0);
-            const uint32_t b[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-            for (int k = 0; k < 16; k++) w[k] = pal[(b[k >> 2] >> (8 * (k & 3))) & 0xffu];
-            return;
-        }
-#pragma unroll
-        for (int k = 0; k < 16; k++)
-            if (k0 + k >= 0 && k0 + k < int(g.n[2])) w[k] = pal[q[k0 + k]];
-    } else {
-        const uint32_t* q = static_cast<const uint32_t*>(g.cells) + row;
-        if (whole && (reinterpret_cast<uintptr_t>(q + k0) & 15u) == 0u) {
-#pragma unroll
-            for (int v4 = 0; v4 < 4; v4++) {
-                const uint4 v = reinterpret_cast<const uint4*>(q + k0)[v4];
-                w[4 * v4 + 0] = v.x; w[4 * v4 + 1] = v.y; w[4 * v4 + 2] = v.z; w[4 * v4 + 3] = v.w;
-            }
-        } else {
-#pragma unroll
-            for (int k = 0; k < 16; k++)
-                if (k0 + k >= 0 && k0 + k < int(g.n[2])) w[k] = q[k0 + k];
-        }
-#pragma unroll
-        for (int k = 0; k < 16; k++) w[k] = w[k] >> 31 ? w[k] : 0u;
-    }
-}
-
-__device__ __forceinline__ void tile_coords(const GridDesc& g, uint32_t tile, int* tx, int* ty, int* tz) {
-    *tz = g.t0[2] + int(tile % g.nt[2]);
-    const uint32_t r = tile / g.nt[2];
-    *ty = g.t0[1] + int(r % g.nt[1]);
-    *tx = g.t0[0] + int(r / g.nt[1]);
-}
-
 // ---- tile stats ----------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kThreads) void grid_tile_stats_kernel(const GridDesc g, const uint32_t* pal, Stat* stats) {
     __shared__ uint32_t s_cnt[kWaves];
@@ -284,19 +223,8 @@ __global__ __launch_bounds__(kThreads) void grid_export_kernel(const SvoRecord* 
         const uint64_t i = row / n.y;
         const int64_t u[3] = {int64_t(o.x) + int64_t(i) + half, int64_t(o.y) + int64_t(j) + half, int64_t(o.z) + int64_t(k) + half};
         uint32_t word = 0;
-        if (u[0] >= 0 && u[0] < 2 * half && u[1] >= 0 && u[1] < 2 * half && u[2] >= 0 && u[2] < 2 * half) {
-            uint32_t node = 0;
-            for (uint32_t l = 0; l <= depth; l++) {
-                const uint2 r = *reinterpret_cast<const uint2*>(svo + node);
-                const uint32_t b = depth - l;
-                const uint32_t s = uint32_t((u[0] >> b) & 1) << 2 | uint32_t((u[1] >> b) & 1) << 1 | uint32_t((u[2] >> b) & 1);
-                const uint32_t mask = l == depth ? (r.x >> 8) & 0xffu : r.x & 0xffu;
-                if (!((mask >> s) & 1u)) break;
-                const uint32_t slot = r.y + uint32_t(__popc(mask & ((1u << s) - 1u)));
-                if (l == depth) word = uint32_t(leaves[slot]);
-                else node = slot;
-            }
-        }
+        if (u[0] >= 0 && u[0] < 2 * half && u[1] >= 0 && u[1] < 2 * half && u[2] >= 0 && u[2] < 2 * half)
+            word = leaf_at(svo, leaves, depth, uint32_t(u[0]), uint32_t(u[1]), uint32_t(u[2]));
         cells[(i * n.y + j) * n.z + k] = word;
     }
 }

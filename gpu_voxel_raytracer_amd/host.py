@@ -41,6 +41,9 @@ E_VOX_MATERIAL, E_VOX_NOMATL, E_VOX_NOMODEL, E_IO, E_SCENE, E_NOSCENE, E_NOISE =
 
 # vxrt_grid_format (include/vxrt_grid.h)
 GRID_PALETTE8, GRID_WORD32 = 1, 2
+# vxrt_grid_edit_mode (include/vxrt_grid_edit.h)
+GRID_EDIT_REPLACE, GRID_EDIT_SET, GRID_EDIT_CLEAR = 1, 2, 3
+GRID_EDIT_MODES = {"replace": GRID_EDIT_REPLACE, "set": GRID_EDIT_SET, "clear": GRID_EDIT_CLEAR}
 
 # vxrt_image
 SAMPLED_COLOR, NORMAL_DEPTH, ALBEDO_NODE, ACCUM_COLOR, DENOISED = range(5)
@@ -555,6 +558,35 @@ class Context:
         self.context_wait_stream(torch.cuda.current_stream(dev).cuda_stream)
         self._chk(self._L.vxrt_set_voxel_grid(self._h, C.c_void_p(cells.data_ptr() if cells.numel() else None), C.c_int(fmt), dims, org,
                                               _p(pal)), "vxrt_set_voxel_grid")
+
+    def edit_voxel_grid(self, cells, origin=(0, 0, 0), palette=None, mode="replace"):
+        """vxrt_edit_voxel_grid (include/vxrt_grid_edit.h): write the grid into the box origin + [0, cells.shape) of the scene in place,
+        on the device.  cells and palette as set_voxel_grid; mode "replace" (every cell of the box becomes the grid's), "set" (occupied
+        cells are set) or "clear" (occupied cells are cleared), or a GRID_EDIT_* value.  Exactly clear_voxels(clears) then
+        edit_voxels(sets) of the cells that change; the temporal history is kept.  The context's stream first waits for torch's
+        current stream.  -> (cells set, cells cleared)."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        cells = torch.as_tensor(cells, device=dev) if isinstance(cells, np.ndarray) else cells
+        if not isinstance(cells, torch.Tensor) or cells.dim() != 3:
+            raise TypeError("cells must be a 3-D torch tensor or numpy array")
+        if cells.device != dev:
+            raise ValueError(f"cells must be on {dev}")
+        fmt = {torch.uint8: GRID_PALETTE8, torch.int32: GRID_WORD32}.get(cells.dtype)
+        if fmt is None:
+            raise ValueError("cells must be uint8 (palette indices) or int32 (leaf words)")
+        m = GRID_EDIT_MODES.get(mode, mode) if isinstance(mode, str) else int(mode)
+        if isinstance(m, str):
+            raise ValueError(f"mode must be one of {sorted(GRID_EDIT_MODES)}")
+        cells = cells.contiguous()
+        pal = None if palette is None else np.ascontiguousarray(np.asarray(palette, np.uint8).reshape(256, 4))
+        dims = (C.c_uint32 * 3)(*cells.shape)
+        org = (C.c_int32 * 3)(*(int(v) for v in origin))
+        counts = (C.c_uint64 * 2)()
+        self.context_wait_stream(torch.cuda.current_stream(dev).cuda_stream)
+        self._chk(self._L.vxrt_edit_voxel_grid(self._h, C.c_void_p(cells.data_ptr() if cells.numel() else None), C.c_int(fmt), dims, org,
+                                               _p(pal), C.c_int(m), counts), "vxrt_edit_voxel_grid")
+        return int(counts[0]), int(counts[1])
 
     def get_voxel_grid(self, origin, dims, out=None):
         """vxrt_get_voxel_grid: the box origin + [0, dims) of the scene as it stands (after edits) -> an int32 torch tensor

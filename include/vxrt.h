@@ -26,6 +26,7 @@
  * An optional extension for hosts that read a loaded scene's voxels back, whole or by box: vxrt_extract.h.
  * An optional extension for hosts that build a scene on the device from a voxel list in device memory: vxrt_device_scene.h.
  * An optional extension for hosts that build a scene from a dense voxel grid in device memory and read boxes back as grids: vxrt_grid.h.
+ * An optional extension for hosts that write a dense grid in device memory into a box of a loaded scene in place: vxrt_grid_edit.h.
  */
 #ifndef VXRT_H
 #define VXRT_H

@@ -20,6 +20,7 @@
 #include "vxrt_edit.h"
 #include "vxrt_extract.h"
 #include "vxrt_grid.h"
+#include "vxrt_grid_edit.h"
 #include "vxrt_host.h"
 
 namespace vxrt {
@@ -204,6 +205,15 @@ class Context {
     // another stream calls stream_wait_context first)
     void get_voxel_grid(const std::array<int32_t, 3>& origin, const std::array<uint32_t, 3>& dims, uint32_t* cells) {
         check(vxrt_get_voxel_grid(ctx_, origin.data(), dims.data(), cells), "vxrt_get_voxel_grid");
+    }
+    // vxrt_edit_voxel_grid (vxrt_grid_edit.h): the grid (as set_voxel_grid takes it) written into the box origin + [0, dims) of the
+    // scene in place; returns how many cells were set and cleared
+    vxrt_grid_edit_counts edit_voxel_grid(const void* cells, vxrt_grid_format format, const std::array<uint32_t, 3>& dims,
+                                          const std::array<int32_t, 3>& origin = {0, 0, 0}, const uint8_t (*palette)[4] = nullptr,
+                                          vxrt_grid_edit_mode mode = VXRT_GRID_EDIT_REPLACE) {
+        vxrt_grid_edit_counts counts{0, 0};
+        check(vxrt_edit_voxel_grid(ctx_, cells, format, dims.data(), origin.data(), palette, mode, &counts), "vxrt_edit_voxel_grid");
+        return counts;
     }
     void set_menger(uint32_t level, uint32_t clip, std::array<uint8_t, 4> mrgb, uint32_t emissive_period) {
         check(vxrt_set_menger(ctx_, level, clip, mrgb.data(), emissive_period), "vxrt_set_menger");
