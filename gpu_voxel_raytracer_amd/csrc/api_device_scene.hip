@@ -2,34 +2,10 @@
 // (device_build.hip) and installed like the procedural scene (api_scene.hip: install_scene).  DESIGN.md §11.
 #include "ctx.h"
 #include "device_build.h"
+#include "scene_args.h"
 #include "../../include/vxrt_device_scene.h"
 
 namespace vxrt {
-
-int check_device_array(const vxrt_ctx* c, const void* p, size_t bytes, const char* who, const char* what) {
-    hipPointerAttribute_t a{};
-    if (hipPointerGetAttributes(&a, p) != hipSuccess) {
-        (void)hipGetLastError();
-        set_error(std::string(who) + ": " + what + " is not device memory");
-        return VXRT_E_INVALID;
-    }
-    if (a.type != hipMemoryTypeDevice || a.device != c->cfg.device) {
-        set_error(std::string(who) + ": " + what + " is not device memory of the context's device");
-        return VXRT_E_INVALID;
-    }
-    hipDeviceptr_t base = nullptr;
-    size_t size = 0;
-    if (hipMemGetAddressRange(&base, &size, const_cast<void*>(p)) == hipSuccess) {
-        const uintptr_t lo = reinterpret_cast<uintptr_t>(base), at = reinterpret_cast<uintptr_t>(p);
-        if (at - lo > size || bytes > size - (at - lo)) {
-            set_error(std::string(who) + ": " + what + " ends past its allocation");
-            return VXRT_E_INVALID;
-        }
-    } else {
-        (void)hipGetLastError();
-    }
-    return VXRT_OK;
-}
 
 int install_device_tree(vxrt_ctx* c, const DeviceTree& t, const char* who) {
     ScratchBuffer svo, leaves, wide;   // owned here until installed
@@ -42,11 +18,7 @@ int install_device_tree(vxrt_ctx* c, const DeviceTree& t, const char* who) {
         HIP_TRY(hipMemcpy(recs.data(), t.svo, t.svo_count * sizeof(SvoRecord), hipMemcpyDeviceToHost));
         std::vector<WideRec> w;
         if (int rc = widen_svo(recs, t.depth, &w)) return rc;
-        if (hipError_t e = wide.alloc(w.size() * sizeof(WideRec)); e != hipSuccess) {
-            (void)hipGetLastError();
-            wide.p = nullptr;
-            return hip_fail(e, (std::string(who) + ": allocating the wide records").c_str());
-        }
+        if (int rc = alloc_scratch(&wide, w.size() * sizeof(WideRec), who, "the wide records")) return rc;
         HIP_TRY(hipMemcpy(wide.p, w.data(), w.size() * sizeof(WideRec), hipMemcpyHostToDevice));
         nwide = w.size();
         wide_root = w[0];

@@ -8,6 +8,7 @@
 
 #include "ctx.h"
 #include "edit.h"
+#include "scene_args.h"
 
 namespace vxrt {
 namespace {
@@ -192,10 +193,9 @@ extern "C" {
 int vxrt_edit_voxels(vxrt_ctx* c, const int16_t (*pos)[3], const uint8_t (*mrgb)[4], size_t n) try {
     if (!valid_ctx(c)) { set_error("null context"); return VXRT_E_INVALID; }
     if (n != 0 && !pos) { set_error("null voxel positions"); return VXRT_E_INVALID; }
-    if (!c->has_scene || c->d_svo == nullptr || c->d_leaves == nullptr) { set_error("no scene set"); return VXRT_E_NOSCENE; }
+    if (int rc = require_scene(c)) return rc;
     if (n == 0) return VXRT_OK;
-    if (c->d_wide != nullptr || c->scene_format == 1) { set_error("scene edits need the 8-byte records only (VXRT_OPT_SCENE_FORMAT 0)"); return VXRT_E_INVALID; }
-    if (c->node_order_applied != 0) { set_error("scene edits need the breadth-first records (VXRT_OPT_NODE_ORDER 0)"); return VXRT_E_INVALID; }
+    if (int rc = require_editable_scene(c)) return rc;
     const bool clear = mrgb == nullptr;
     const uint32_t L = c->depth;
     const int32_t half = int32_t(1) << L;

@@ -4,7 +4,9 @@
 #include <algorithm>
 
 #include "ctx.h"
+#include "device_build.h"
 #include "extract.h"
+#include "scene_args.h"
 #include "../../include/vxrt_extract.h"
 
 namespace vxrt {
@@ -34,11 +36,6 @@ hipError_t ensure(void** p, size_t* cap, size_t need) {
     return hipSuccess;
 }
 
-int fail_alloc(hipError_t e, const char* what) {
-    set_error(std::string("vxrt_get_voxels: allocating ") + what + ": " + hipGetErrorString(e));
-    return VXRT_E_DEVICE;
-}
-
 }  // namespace
 
 void free_extract(vxrt_ctx* c) {
@@ -57,7 +54,7 @@ int vxrt_get_voxels(vxrt_ctx* c, const int32_t box_min[3], const int32_t box_max
     if (!valid_ctx(c) || !n) { set_error("null argument"); return VXRT_E_INVALID; }
     if ((box_min == nullptr) != (box_max == nullptr)) { set_error("box_min and box_max: both or neither"); return VXRT_E_INVALID; }
     if ((pos == nullptr) != (mrgb == nullptr)) { set_error("pos and mrgb: both or neither"); return VXRT_E_INVALID; }
-    if (!c->has_scene || c->d_svo == nullptr || c->d_leaves == nullptr) { set_error("no scene set"); return VXRT_E_NOSCENE; }
+    if (int rc = require_scene(c)) return rc;
     const bool count_only = pos == nullptr;
     const uint32_t L = c->depth;
     const int64_t half = int64_t(1) << L;
@@ -79,7 +76,7 @@ int vxrt_get_voxels(vxrt_ctx* c, const int32_t box_min[3], const int32_t box_max
     HIP_TRY(hipSetDevice(c->cfg.device));
     vxrt_ctx::ExtractScratch& x = c->extract;
     // the root: record 0 at cell 0 (the decode runs on the context's stream, behind everything enqueued on it)
-    if (hipError_t e = ensure(&x.front[0], &x.front_cap[0], sizeof(uint4)); e != hipSuccess) return fail_alloc(e, "the frontier");
+    if (hipError_t e = ensure(&x.front[0], &x.front_cap[0], sizeof(uint4)); e != hipSuccess) return alloc_failed(e, "vxrt_get_voxels", "the frontier");
     HIP_TRY(hipMemsetAsync(x.front[0], 0, sizeof(uint4), c->stream));
     int cur = 0;
     uint64_t count = 0;
@@ -91,10 +88,10 @@ int vxrt_get_voxels(vxrt_ctx* c, const int32_t box_min[3], const int32_t box_max
         a.n = frontier;
         const uint32_t blocks = extract_blocks(frontier);
         if (hipError_t e = ensure(&x.part, &x.part_cap, (size_t(blocks) + 1) * sizeof(uint64_t)); e != hipSuccess)
-            return fail_alloc(e, "the scan partials");
+            return alloc_failed(e, "vxrt_get_voxels", "the scan partials");
         a.part = static_cast<uint64_t*>(x.part);
         HIP_TRY(launch_extract_count(a, c->stream));
-        HIP_TRY(launch_extract_scan(a.part, blocks, c->stream));
+        HIP_TRY(launch_exclusive_scan(a.part, blocks, c->stream));
         uint64_t total = 0;
         HIP_TRY(hipMemcpyAsync(&total, a.part + blocks, sizeof total, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
@@ -102,7 +99,7 @@ int vxrt_get_voxels(vxrt_ctx* c, const int32_t box_min[3], const int32_t box_max
         if (a.leaf) { count = total; break; }
         if (total >= (uint64_t(1) << 32)) { set_error("vxrt_get_voxels: a tree level of 2^32 nodes or more"); return VXRT_E_INVALID; }
         if (hipError_t e = ensure(&x.front[cur ^ 1], &x.front_cap[cur ^ 1], size_t(total) * sizeof(uint4)); e != hipSuccess)
-            return fail_alloc(e, "the frontier");
+            return alloc_failed(e, "vxrt_get_voxels", "the frontier");
         a.next = static_cast<uint4*>(x.front[cur ^ 1]);
         HIP_TRY(launch_extract_expand(a, c->stream));
         a.next = nullptr;
@@ -116,8 +113,8 @@ int vxrt_get_voxels(vxrt_ctx* c, const int32_t box_min[3], const int32_t box_max
         return VXRT_E_INVALID;
     }
     // the leaf parents' frontier is still in place (a.front, a.n, a.part): write the voxels at their offsets
-    if (hipError_t e = ensure(&x.pos, &x.pos_cap, size_t(count) * 3 * sizeof(int16_t)); e != hipSuccess) return fail_alloc(e, "the positions");
-    if (hipError_t e = ensure(&x.mrgb, &x.mrgb_cap, size_t(count) * 4); e != hipSuccess) return fail_alloc(e, "the leaf words");
+    if (hipError_t e = ensure(&x.pos, &x.pos_cap, size_t(count) * 3 * sizeof(int16_t)); e != hipSuccess) return alloc_failed(e, "vxrt_get_voxels", "the positions");
+    if (hipError_t e = ensure(&x.mrgb, &x.mrgb_cap, size_t(count) * 4); e != hipSuccess) return alloc_failed(e, "vxrt_get_voxels", "the leaf words");
     a.pos = static_cast<int16_t*>(x.pos);
     a.mrgb = static_cast<uint32_t*>(x.mrgb);
     HIP_TRY(launch_extract_expand(a, c->stream));

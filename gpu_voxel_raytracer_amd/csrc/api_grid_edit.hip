@@ -5,6 +5,7 @@
 
 #include "ctx.h"
 #include "grid_edit.h"
+#include "scene_args.h"
 #include "../../include/vxrt_grid_edit.h"
 
 namespace vxrt {
@@ -46,26 +47,19 @@ int vxrt_edit_voxel_grid(vxrt_ctx* c, const void* cells, vxrt_grid_format format
     using namespace vxrt;
     if (counts) *counts = vxrt_grid_edit_counts{0, 0};
     if (!valid_ctx(c) || !dims || !origin) { set_error("null argument"); return VXRT_E_INVALID; }
-    if (format != VXRT_GRID_PALETTE8 && format != VXRT_GRID_WORD32) { set_error("vxrt_edit_voxel_grid: bad format"); return VXRT_E_INVALID; }
+    if (int rc = check_grid_format(format, "vxrt_edit_voxel_grid")) return rc;
     if (mode != VXRT_GRID_EDIT_REPLACE && mode != VXRT_GRID_EDIT_SET && mode != VXRT_GRID_EDIT_CLEAR) {
         set_error("vxrt_edit_voxel_grid: bad mode");
         return VXRT_E_INVALID;
     }
-    if ((format == VXRT_GRID_PALETTE8) != (palette != nullptr)) {
-        set_error("vxrt_edit_voxel_grid: a palette is required for PALETTE8 cells and refused for WORD32 cells");
-        return VXRT_E_INVALID;
-    }
-    const size_t cell_bytes = format == VXRT_GRID_PALETTE8 ? 1 : 4;
-    unsigned __int128 bytes = cell_bytes;
-    for (int ax = 0; ax < 3; ax++) bytes *= dims[ax];
-    if (bytes >> 64) { set_error("vxrt_edit_voxel_grid: a box of 2^64 bytes or more"); return VXRT_E_INVALID; }
-    if (bytes != 0 && !cells) { set_error("vxrt_edit_voxel_grid: null cells"); return VXRT_E_INVALID; }
-    if (!c->has_scene || c->d_svo == nullptr || c->d_leaves == nullptr) { set_error("no scene set"); return VXRT_E_NOSCENE; }
-    if (c->d_wide != nullptr || c->scene_format == 1) { set_error("scene edits need the 8-byte records only (VXRT_OPT_SCENE_FORMAT 0)"); return VXRT_E_INVALID; }
-    if (c->node_order_applied != 0) { set_error("scene edits need the breadth-first records (VXRT_OPT_NODE_ORDER 0)"); return VXRT_E_INVALID; }
+    if (int rc = check_grid_palette(format, palette, "vxrt_edit_voxel_grid")) return rc;
+    size_t bytes = 0;
+    if (int rc = check_grid_cells(cells, format, dims, "vxrt_edit_voxel_grid", &bytes)) return rc;
+    if (int rc = require_scene(c)) return rc;
+    if (int rc = require_editable_scene(c)) return rc;
     if (bytes == 0) return VXRT_OK;
     HIP_TRY(hipSetDevice(c->cfg.device));
-    if (int rc = check_device_array(c, cells, size_t(bytes), "vxrt_edit_voxel_grid", "cells")) return rc;
+    if (int rc = check_device_array(c, cells, bytes, "vxrt_edit_voxel_grid", "cells")) return rc;
     // frames in flight read the scene: drain them first (this also orders the reads behind everything enqueued on the context's
     // stream, vxrt_context_wait_stream's events included)
     if (int rc = sync_all(c)) return rc;
@@ -100,19 +94,7 @@ int vxrt_edit_voxel_grid(vxrt_ctx* c, const void* cells, vxrt_grid_format format
     const uint32_t n_slabs = mode != VXRT_GRID_EDIT_CLEAR && !inside ? outside_slabs(origin, dims, h, slabs) : 0u;
 
     ScratchBuffer pal;
-    if (format == VXRT_GRID_PALETTE8) {   // the palette as leaf words (scene_host.cpp: build_octree's rule); index 0 is empty
-        uint32_t words[256];
-        words[0] = 0u;
-        for (int i = 1; i < 256; i++)
-            words[i] = 0x80000000u | (uint32_t(palette[i][0]) & 0x7fu) << 24 | uint32_t(palette[i][1]) << 16 | uint32_t(palette[i][2]) << 8 |
-                       uint32_t(palette[i][3]);
-        if (hipError_t err = pal.alloc(sizeof words); err != hipSuccess) {
-            (void)hipGetLastError();
-            pal.p = nullptr;
-            return hip_fail(err, "vxrt_edit_voxel_grid: allocating the palette");
-        }
-        HIP_TRY(hipMemcpyAsync(pal.p, words, sizeof words, hipMemcpyHostToDevice, c->stream));
-    }
+    if (int rc = upload_palette(palette, c->stream, "vxrt_edit_voxel_grid", &pal)) return rc;
     GridEditLists lists;
     if (int rc = diff_grid_device(e, pal.as<uint32_t>(), slabs, n_slabs, c->stream, &lists)) return rc;
     if (lists.set == 0 && lists.cleared == 0) return VXRT_OK;

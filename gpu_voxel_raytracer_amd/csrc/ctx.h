@@ -56,6 +56,21 @@ struct ScratchBuffer {
     template <typename T> T* as() const { return static_cast<T*>(p); }
 };
 
+// A failed device allocation of an entry point: clears the HIP error, sets "<who>: allocating <what>: <hip error>", VXRT_E_DEVICE.
+inline int alloc_failed(hipError_t e, const char* who, const char* what) {
+    (void)hipGetLastError();
+    set_error(std::string(who) + ": allocating " + what + ": " + hipGetErrorString(e));
+    return VXRT_E_DEVICE;
+}
+
+// b->alloc(bytes), or alloc_failed.  A request for 0 bytes gets 16, so every buffer is non-null.
+inline int alloc_scratch(ScratchBuffer* b, size_t bytes, const char* who, const char* what) {
+    const hipError_t e = b->alloc(bytes ? bytes : 16);
+    if (e == hipSuccess) return VXRT_OK;
+    b->p = nullptr;
+    return alloc_failed(e, who, what);
+}
+
 struct EventPair {
     hipEvent_t a = nullptr, b = nullptr;
     int stage = 0;  // 0 trace, 1 temporal, 2 denoise, 3 halo pack, 4 halo unpack

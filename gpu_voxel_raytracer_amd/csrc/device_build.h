@@ -1,5 +1,6 @@
 // device_build.h — what api_device_scene.hip (host side of vxrt_device_scene.h), device_build.hip (the list builder), grid_build.hip
-// (the dense-grid builder) and api_grid.hip (host side of vxrt_grid.h) share.
+// (the dense-grid builder), grid_edit.hip (the grid editor) and api_grid.hip (host side of vxrt_grid.h) share, and the device
+// primitives they and api_extract.hip use: lanes_below, the exclusive scan and the radix sort (device_build.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -20,7 +21,6 @@ struct DeviceTree {
     size_t leaf_count = 0;
     uint32_t depth = 0;
     SvoRecord root{0, 0};
-    size_t scratch_bytes = 0;   // the build's peak scratch (freed before it returns)
 };
 
 // pos / mrgb: n entries in device memory of the current device, read on `stream` behind what is enqueued there.  Waits for the
@@ -31,6 +31,14 @@ int build_svo_device_list(const int16_t* pos, const uint8_t* mrgb, size_t n, hip
 // The host builder's empty tree (the root {masks 0, base 1} and one zero leaf word).  `who` names the API call in error messages.
 int build_empty_tree(hipStream_t stream, const char* who, DeviceTree* out);
 
+// The lanes of this wave below this one whose bit is set in m (a ballot): this lane's rank among them.
+__device__ __forceinline__ uint32_t lanes_below(uint64_t m) {
+    return __builtin_amdgcn_mbcnt_hi(uint32_t(m >> 32), __builtin_amdgcn_mbcnt_lo(uint32_t(m), 0u));
+}
+
+// One workgroup: part[0 .. blocks) -> its exclusive prefix sums in place, part[blocks] = the total.
+hipError_t launch_exclusive_scan(uint64_t* part, uint32_t blocks, hipStream_t stream);
+
 // Stable LSD radix sort of (keys, vals), n entries, over the low `bits` key bits, 8 per pass, ping-ponging between keys[0] / vals[0]
 // and keys[1] / vals[1] starting at [*cur]; the result is in [*cur] on return.  hist: radix_hist_entries(n) words; totals: 256 words.
 size_t radix_hist_entries(size_t n);
@@ -40,12 +48,11 @@ hipError_t radix_sort_pairs(uint64_t* keys[2], uint32_t* vals[2], uint32_t n, ui
 // The back half of both builders: the node levels over m > 0 unique path keys in ascending order (ukeys, m < 2^32) and their leaf
 // words (*leaves, exactly m int32, handed to *out on success) -> the records, one exact allocation.  ukeys is overwritten; spare
 // (the level ping-pong) holds at least m keys, or is null and then allocated at the leaf parents' count.  part: level_part_entries(m),
-// bins: level_bin_entries(m).  scratch: the caller's scratch bytes so far (out->scratch_bytes adds this call's own).  Waits for the
-// result.  VXRT_E_SCENE: 2^32 records or more; VXRT_E_DEVICE: an allocation failed.
+// bins: level_bin_entries(m).  Waits for the result.  VXRT_E_SCENE: 2^32 records or more; VXRT_E_DEVICE: an allocation failed.
 size_t level_part_entries(size_t m);
 size_t level_bin_entries(size_t m);
 int build_levels(uint64_t* ukeys, uint64_t* spare, size_t m, uint64_t* part, uint64_t* bins, uint32_t depth, ScratchBuffer* leaves,
-                 size_t scratch, hipStream_t stream, const char* who, DeviceTree* out);
+                 hipStream_t stream, const char* who, DeviceTree* out);
 
 // u16::next_power_of_two().trailing_zeros() of |lo| and |hi| + 1 (scene_host.cpp: build_octree's depth rule over the coordinates' min
 // and max); may exceed 15
@@ -55,9 +62,6 @@ inline uint32_t depth_of_bounds(int lo, int hi) {
     const uint32_t dhi = ceil_log2_u16((uint32_t(hi < 0 ? -hi : hi) + 1u) & 0xffffu);
     return dlo > dhi ? dlo : dhi;
 }
-
-// `bytes` at p must be device memory of the context's device, inside one allocation (api_device_scene.hip).  who: the API call.
-int check_device_array(const vxrt_ctx* c, const void* p, size_t bytes, const char* who, const char* what);
 
 // A tree built on the device -> the context's scene: the wide records when the context asks for them, then install_scene (which
 // owns the arrays from then on, or frees them on failure).  who: the API call.

@@ -25,7 +25,6 @@
 #include "block_scan.h"
 #include "ctx.h"
 #include "device_build.h"
-#include "extract.h"
 
 namespace vxrt {
 namespace {
@@ -38,12 +37,10 @@ constexpr uint32_t kDigits = 256;
 constexpr uint32_t kRowThreads = 1024;              // radix_scan: one workgroup per digit
 constexpr uint32_t kBoundsBlocks = 1024;
 constexpr uint32_t kLevelBins = 17;                 // a unique key opens nodes at levels 1 .. t, t = 0 .. 16
+constexpr uint32_t kScanThreads = 1024;             // exclusive_scan: one workgroup, 8 partials per thread per pass
+constexpr uint32_t kScanItems = 8;
 
 uint32_t tiles(size_t n) { return uint32_t((n + kTile - 1) / kTile); }
-
-__device__ __forceinline__ uint32_t lanes_below(uint64_t m) {
-    return __builtin_amdgcn_mbcnt_hi(uint32_t(m >> 32), __builtin_amdgcn_mbcnt_lo(uint32_t(m), 0u));
-}
 
 // the lanes of this wave that are valid and hold the same 8-bit digit as this lane
 __device__ __forceinline__ uint64_t digit_peers(uint32_t d, bool ok) {
@@ -226,7 +223,7 @@ __global__ __launch_bounds__(kThreads) void radix_scatter_kernel(const uint64_t*
     }
 }
 
-// ---- dedupe and levels: flags over a sorted list, counted per tile, scanned (extract_scan), written at the prefix ---------------
+// ---- dedupe and levels: flags over a sorted list, counted per tile, scanned (exclusive_scan), written at the prefix -------------
 // dedupe: the last entry of each run of equal keys.  level: the first entry of each run of equal key >> 3.
 template <bool kLast> __device__ __forceinline__ bool flag_at(const uint64_t* k, uint32_t n, uint32_t i) {
     if (kLast) return i + 1u == n || k[i] != k[i + 1u];
@@ -345,19 +342,37 @@ __global__ __launch_bounds__(kThreads) void level_write_kernel(const uint64_t* k
     }
 }
 
-hipError_t alloc(ScratchBuffer* b, size_t bytes, size_t* total) {
-    *total += bytes;
-    const hipError_t e = b->alloc(bytes);
-    if (e != hipSuccess) { (void)hipGetLastError(); b->p = nullptr; }
-    return e;
-}
-
-int fail(hipError_t e, const char* what) {
-    set_error(std::string("vxrt_set_voxels_device: allocating ") + what + ": " + hipGetErrorString(e));
-    return VXRT_E_DEVICE;
+// one workgroup: part[0 .. blocks) -> exclusive prefix sums in place, part[blocks] = the total.  Each pass takes 8 consecutive
+// partials per thread.
+__global__ __launch_bounds__(kScanThreads) void exclusive_scan_kernel(uint64_t* part, uint32_t blocks) {
+    __shared__ uint64_t lds[kScanThreads / 64];
+    uint64_t carry = 0;
+    for (uint32_t c = 0; c < blocks; c += kScanThreads * kScanItems) {
+        const uint32_t i0 = c + threadIdx.x * kScanItems;
+        uint64_t v[kScanItems], mine = 0;
+#pragma unroll
+        for (uint32_t k = 0; k < kScanItems; k++) {
+            v[k] = i0 + k < blocks ? part[i0 + k] : 0ull;
+            mine += v[k];
+        }
+        uint64_t total;
+        uint64_t run = carry + block_exclusive<uint64_t, kScanThreads / 64>(mine, lds, &total);
+#pragma unroll
+        for (uint32_t k = 0; k < kScanItems; k++) {
+            if (i0 + k < blocks) part[i0 + k] = run;
+            run += v[k];
+        }
+        carry += total;
+    }
+    if (threadIdx.x == 0) part[blocks] = carry;
 }
 
 }  // namespace
+
+hipError_t launch_exclusive_scan(uint64_t* part, uint32_t blocks, hipStream_t s) {
+    hipLaunchKernelGGL(exclusive_scan_kernel, dim3(1), dim3(kScanThreads), 0, s, part, blocks);
+    return hipGetLastError();
+}
 
 size_t radix_hist_entries(size_t n) { return size_t(kDigits) * tiles(n); }
 
@@ -382,9 +397,8 @@ size_t level_part_entries(size_t m) { return size_t(tiles(m)) + 1; }
 size_t level_bin_entries(size_t m) { return size_t(kLevelBins) * tiles(m) + kLevelBins; }
 
 int build_levels(uint64_t* ukeys, uint64_t* spare, size_t m, uint64_t* part, uint64_t* bins, uint32_t depth, ScratchBuffer* leaves,
-                 size_t scratch, hipStream_t s, const char* who, DeviceTree* out) {
+                 hipStream_t s, const char* who, DeviceTree* out) {
     ScratchBuffer svo, own_spare;
-    size_t outputs = 0;
     const std::string w(who);
     // every level's node count: level j (1 = the leaf parents .. depth + 1 = the root) has the unique keys that open a node there
     const uint32_t mm = uint32_t(m), ublocks = tiles(m), top = depth + 1u;
@@ -405,16 +419,10 @@ int build_levels(uint64_t* ukeys, uint64_t* spare, size_t m, uint64_t* part, uin
     if (level_count[top] != 1u) { set_error(w + ": internal error: the root level has " + std::to_string(level_count[top]) + " nodes"); return VXRT_E_SCENE; }
     if (nodes > 0xffffffffull) { set_error(w + ": " + std::to_string(nodes) + " octree nodes: 2^32 or more"); return VXRT_E_SCENE; }
     if (spare == nullptr && top > 1u) {   // the levels above the leaf parents ping-pong between ukeys and a buffer of the leaf parents' size
-        if (hipError_t e = alloc(&own_spare, size_t(level_count[1]) * sizeof(uint64_t), &scratch); e != hipSuccess) {
-            set_error(w + ": allocating the node keys: " + hipGetErrorString(e));
-            return VXRT_E_DEVICE;
-        }
+        if (int rc = alloc_scratch(&own_spare, size_t(level_count[1]) * sizeof(uint64_t), who, "the node keys")) return rc;
         spare = own_spare.as<uint64_t>();
     }
-    if (hipError_t e = alloc(&svo, size_t(nodes) * sizeof(SvoRecord), &outputs); e != hipSuccess) {
-        set_error(w + ": allocating the records: " + hipGetErrorString(e));
-        return VXRT_E_DEVICE;
-    }
+    if (int rc = alloc_scratch(&svo, size_t(nodes) * sizeof(SvoRecord), who, "the records")) return rc;
 
     // the levels, bottom-up, each written at its top-down place
     uint64_t* buf[2] = {ukeys, spare};
@@ -426,7 +434,7 @@ int build_levels(uint64_t* ukeys, uint64_t* spare, size_t m, uint64_t* part, uin
         uint64_t* next = j < top ? buf[cur ^ 1] : nullptr;
         hipLaunchKernelGGL(flag_count_kernel<false>, dim3(lb), dim3(kThreads), 0, s, in, below, part);
         HIP_TRY(hipGetLastError());
-        HIP_TRY(launch_extract_scan(part, lb, s));
+        HIP_TRY(launch_exclusive_scan(part, lb, s));
         hipLaunchKernelGGL(level_write_kernel, dim3(lb), dim3(kThreads), 0, s, in, below, part, next, svo.as<SvoRecord>(),
                            level_start[j], j == 1u ? 0ull : level_start[j - 1], j == 1u ? 1u : 0u);
         HIP_TRY(hipGetLastError());
@@ -441,7 +449,6 @@ int build_levels(uint64_t* ukeys, uint64_t* spare, size_t m, uint64_t* part, uin
     out->leaves = leaves->as<int32_t>(); out->leaf_count = m; leaves->p = nullptr;
     out->depth = depth;
     out->root = root;
-    out->scratch_bytes = scratch;
     return VXRT_OK;
 }
 
@@ -449,15 +456,10 @@ int build_empty_tree(hipStream_t s, const char* who, DeviceTree* out) {
     *out = DeviceTree{};
     // the host builder's empty tree: the root {masks 0, base 1} and one zero leaf word (api_scene.hip: upload_svo)
     ScratchBuffer svo, leaves;
-    size_t outputs = 0;
     const SvoRecord root{0u, 1u};
     const int32_t zero = 0;
-    hipError_t e = alloc(&svo, sizeof root, &outputs);
-    if (e == hipSuccess) e = alloc(&leaves, sizeof zero, &outputs);
-    if (e != hipSuccess) {
-        set_error(std::string(who) + ": allocating the " + (svo.p ? "leaf words: " : "records: ") + hipGetErrorString(e));
-        return VXRT_E_DEVICE;
-    }
+    if (int rc = alloc_scratch(&svo, sizeof root, who, "the records")) return rc;
+    if (int rc = alloc_scratch(&leaves, sizeof zero, who, "the leaf words")) return rc;
     HIP_TRY(hipMemcpyAsync(svo.p, &root, sizeof root, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(leaves.p, &zero, sizeof zero, hipMemcpyHostToDevice, s));
     HIP_TRY(hipStreamSynchronize(s));
@@ -469,14 +471,14 @@ int build_empty_tree(hipStream_t s, const char* who, DeviceTree* out) {
 
 int build_svo_device_list(const int16_t* pos, const uint8_t* mrgb, size_t n, hipStream_t s, DeviceTree* out) {
     *out = DeviceTree{};
+    const char* who = "vxrt_set_voxels_device";
     ScratchBuffer leaves;
-    size_t scratch = 0, outputs = 0;
-    if (n == 0) return build_empty_tree(s, "vxrt_set_voxels_device", out);
+    if (n == 0) return build_empty_tree(s, who, out);
     const uint32_t nn = uint32_t(n);   // the caller refuses n >= 2^32
 
     // bounds -> depth
     ScratchBuffer bpart;
-    if (hipError_t e = alloc(&bpart, (kBoundsBlocks + 1) * sizeof(int2), &scratch); e != hipSuccess) return fail(e, "the scratch");
+    if (int rc = alloc_scratch(&bpart, (kBoundsBlocks + 1) * sizeof(int2), who, "the scratch")) return rc;
     const uint32_t vec = (reinterpret_cast<uintptr_t>(pos) & 15u) == 0u ? 1u : 0u;
     hipLaunchKernelGGL(bounds_kernel, dim3(kBoundsBlocks), dim3(kThreads), 0, s, pos, 3 * n, vec, bpart.as<int2>());
     HIP_TRY(hipGetLastError());
@@ -492,14 +494,13 @@ int build_svo_device_list(const int16_t* pos, const uint8_t* mrgb, size_t n, hip
     const uint32_t blocks = tiles(n);
     ScratchBuffer keys[2], vals[2], hist, totals, part, bins;
     for (int b = 0; b < 2; b++) {
-        if (hipError_t e = alloc(&keys[b], n * sizeof(uint64_t), &scratch); e != hipSuccess) return fail(e, "the keys");
-        if (hipError_t e = alloc(&vals[b], n * sizeof(uint32_t), &scratch); e != hipSuccess) return fail(e, "the leaf words");
+        if (int rc = alloc_scratch(&keys[b], n * sizeof(uint64_t), who, "the keys")) return rc;
+        if (int rc = alloc_scratch(&vals[b], n * sizeof(uint32_t), who, "the leaf words")) return rc;
     }
-    if (hipError_t e = alloc(&hist, size_t(kDigits) * blocks * sizeof(uint32_t), &scratch); e != hipSuccess) return fail(e, "the digit counts");
-    if (hipError_t e = alloc(&totals, kDigits * sizeof(uint32_t), &scratch); e != hipSuccess) return fail(e, "the digit counts");
-    if (hipError_t e = alloc(&part, (size_t(blocks) + 1) * sizeof(uint64_t), &scratch); e != hipSuccess) return fail(e, "the scan partials");
-    if (hipError_t e = alloc(&bins, (size_t(kLevelBins) * blocks + kLevelBins) * sizeof(uint64_t), &scratch); e != hipSuccess)
-        return fail(e, "the level counts");
+    if (int rc = alloc_scratch(&hist, size_t(kDigits) * blocks * sizeof(uint32_t), who, "the digit counts")) return rc;
+    if (int rc = alloc_scratch(&totals, kDigits * sizeof(uint32_t), who, "the digit counts")) return rc;
+    if (int rc = alloc_scratch(&part, (size_t(blocks) + 1) * sizeof(uint64_t), who, "the scan partials")) return rc;
+    if (int rc = alloc_scratch(&bins, (size_t(kLevelBins) * blocks + kLevelBins) * sizeof(uint64_t), who, "the level counts")) return rc;
 
     const uint32_t words = (reinterpret_cast<uintptr_t>(mrgb) & 3u) == 0u ? 1u : 0u;
     hipLaunchKernelGGL(keys_kernel, dim3(uint32_t((n + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, pos, mrgb, n, depth, words,
@@ -515,18 +516,18 @@ int build_svo_device_list(const int16_t* pos, const uint8_t* mrgb, size_t n, hip
     // dedupe: the last entry of each key -> the leaf words (exactly sized) and the unique keys (keys[cur ^ 1])
     hipLaunchKernelGGL(flag_count_kernel<true>, dim3(blocks), dim3(kThreads), 0, s, keys[cur].as<uint64_t>(), nn, part.as<uint64_t>());
     HIP_TRY(hipGetLastError());
-    HIP_TRY(launch_extract_scan(part.as<uint64_t>(), blocks, s));
+    HIP_TRY(launch_exclusive_scan(part.as<uint64_t>(), blocks, s));
     uint64_t m = 0;
     HIP_TRY(hipMemcpyAsync(&m, part.as<uint64_t>() + blocks, sizeof m, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
-    if (hipError_t e = alloc(&leaves, size_t(m) * sizeof(int32_t), &outputs); e != hipSuccess) return fail(e, "the leaf words");
+    if (int rc = alloc_scratch(&leaves, size_t(m) * sizeof(int32_t), who, "the leaf words")) return rc;
     hipLaunchKernelGGL(dedupe_write_kernel, dim3(blocks), dim3(kThreads), 0, s, keys[cur].as<uint64_t>(), vals[cur].as<uint32_t>(), nn,
                        part.as<uint64_t>(), keys[cur ^ 1].as<uint64_t>(), leaves.as<int32_t>());
     HIP_TRY(hipGetLastError());
     cur ^= 1;
 
     return build_levels(keys[cur].as<uint64_t>(), keys[cur ^ 1].as<uint64_t>(), size_t(m), part.as<uint64_t>(), bins.as<uint64_t>(), depth,
-                        &leaves, scratch, s, "vxrt_set_voxels_device", out);
+                        &leaves, s, who, out);
 }
 
 

@@ -12,7 +12,7 @@ namespace vxrt {
 // cube meets the box — {record index, u.x, u.y, u.z} with u the node's integer cell (l bits per axis; the root is {0, 0, 0, 0}).
 // Each level is three launches over the frontier, in blocks of kExtractSpan entries:
 //   extract_count  per block: the number of kept children (or voxels, at the leaf parents' level) -> part[block]
-//   extract_scan   one workgroup: part[] -> its exclusive prefix sum in place, the total -> part[blocks]
+//   exclusive_scan one workgroup: part[] -> its exclusive prefix sum in place, the total -> part[blocks] (device_build.h)
 //   extract_expand the kept children, written at their exclusive-prefix offsets (the next frontier), or at the leaf parents'
 //                  level the voxels (positions and mrgb)
 // Every offset is a prefix sum in frontier order; nothing is decided by an atomic, so two calls write the same bytes.
@@ -36,7 +36,6 @@ struct ExtractLevel {
 };
 
 hipError_t launch_extract_count(const ExtractLevel& a, hipStream_t s);
-hipError_t launch_extract_scan(uint64_t* part, uint32_t blocks, hipStream_t s);
 hipError_t launch_extract_expand(const ExtractLevel& a, hipStream_t s);
 
 inline uint32_t extract_blocks(uint32_t n) { return (n + kExtractSpan - 1) / kExtractSpan; }

@@ -12,9 +12,6 @@
 namespace vxrt {
 namespace {
 
-constexpr uint32_t kScanThreads = 1024;
-constexpr uint32_t kScanItems = 8;
-
 // the slots of a node at cell u whose children's cubes meet the box (a.lo, a.hi): per axis, which of the two halves meets it
 __device__ __forceinline__ uint32_t box_slots(const ExtractLevel& a, uint32_t ux, uint32_t uy, uint32_t uz) {
     const uint32_t u[3] = {ux, uy, uz};
@@ -65,31 +62,6 @@ __global__ __launch_bounds__(kExtractThreads) void extract_count_kernel(const Ex
     }
 }
 
-// one workgroup: part[0 .. blocks) -> exclusive prefix sums in place, part[blocks] = the total.  Each pass takes 8 consecutive
-// partials per thread.
-__global__ __launch_bounds__(kScanThreads) void extract_scan_kernel(uint64_t* part, uint32_t blocks) {
-    __shared__ uint64_t lds[kScanThreads / 64];
-    uint64_t carry = 0;
-    for (uint32_t c = 0; c < blocks; c += kScanThreads * kScanItems) {
-        const uint32_t i0 = c + threadIdx.x * kScanItems;
-        uint64_t v[kScanItems], mine = 0;
-#pragma unroll
-        for (uint32_t k = 0; k < kScanItems; k++) {
-            v[k] = i0 + k < blocks ? part[i0 + k] : 0ull;
-            mine += v[k];
-        }
-        uint64_t total;
-        uint64_t run = carry + block_exclusive<uint64_t, kScanThreads / 64>(mine, lds, &total);
-#pragma unroll
-        for (uint32_t k = 0; k < kScanItems; k++) {
-            if (i0 + k < blocks) part[i0 + k] = run;
-            run += v[k];
-        }
-        carry += total;
-    }
-    if (threadIdx.x == 0) part[blocks] = carry;
-}
-
 __global__ __launch_bounds__(kExtractThreads) void extract_expand_kernel(const ExtractLevel a) {
     __shared__ uint32_t lds[kExtractThreads / 64];
     const uint32_t first = blockIdx.x * kExtractSpan + threadIdx.x;
@@ -131,11 +103,6 @@ __global__ __launch_bounds__(kExtractThreads) void extract_expand_kernel(const E
 
 hipError_t launch_extract_count(const ExtractLevel& a, hipStream_t s) {
     hipLaunchKernelGGL(extract_count_kernel, dim3(extract_blocks(a.n)), dim3(kExtractThreads), 0, s, a);
-    return hipGetLastError();
-}
-
-hipError_t launch_extract_scan(uint64_t* part, uint32_t blocks, hipStream_t s) {
-    hipLaunchKernelGGL(extract_scan_kernel, dim3(1), dim3(kScanThreads), 0, s, part, blocks);
     return hipGetLastError();
 }
 

@@ -1,10 +1,11 @@
-// grid.h — what api_grid.hip (host side of vxrt_grid.h), grid_build.hip (its kernels) and grid_edit.hip (vxrt_grid_edit.h) share.
-// DESIGN.md §12, §13.
+// grid.h — what api_grid.hip (host side of vxrt_grid.h), grid_build.hip (its kernels) and grid_edit.hip (vxrt_grid_edit.h) share:
+// the grid, and the tile pipeline both run over its 16-aligned tiles (grid_build.hip).  DESIGN.md §12, §13.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 
+#include "block_scan.h"
 #include "device_build.h"
 
 namespace vxrt {
@@ -82,6 +83,101 @@ __device__ __forceinline__ void tile_coords(const GridDesc& g, uint32_t tile, in
     *tx = g.t0[0] + int(r / g.nt[1]);
 }
 
+// The first cell of tile `tile`; small: the root cube of a depth < 4 tree, the only tile, from p = -2^depth (not 16-aligned).
+__device__ __forceinline__ void tile_origin(const GridDesc& g, uint32_t small, uint32_t depth, uint32_t tile, int p0[3]) {
+    if (small) {
+        p0[0] = p0[1] = p0[2] = -(1 << depth);
+    } else {
+        tile_coords(g, tile, &p0[0], &p0[1], &p0[2]);
+        for (int a = 0; a < 3; a++) p0[a] *= 16;
+    }
+}
+
+// The path code of tile `tile` (depth >= 4): the Morton code of its u-tile (p-tile + 2^(depth - 4) per axis), 3 (depth - 3) bits.
+// A cell's path key is this << 12 | its in-tile Morton index.
+__device__ __forceinline__ uint64_t tile_code(const GridDesc& g, uint32_t tile, uint32_t depth) {
+    int tx, ty, tz;
+    tile_coords(g, tile, &tx, &ty, &tz);
+    const int shift = 1 << (depth - 4u);
+    return morton_tile(uint32_t(tx + shift), uint32_t(ty + shift), uint32_t(tz + shift), depth - 3u);
+}
+
+// ---- the tile pipeline (grid_build.hip: the builder; grid_edit.hip: the editor) -----------------------------------------------
+//   summary   one workgroup per tile, one thread per 16-cell row: a TileStat per tile -> launch_tile_reduce -> one read-back
+//   order     order_active_tiles: the active tiles in path order and their offsets
+//   emit      one workgroup per active tile: the tile staged in LDS in Morton order, its cells ranked by tile_rank_scan / tile_rank
+constexpr uint32_t kTileThreads = 256;
+constexpr uint32_t kTileWaves = kTileThreads / 64;
+constexpr uint32_t kTileCells = 4096;
+constexpr uint32_t kTileRounds = kTileCells / kTileThreads;
+constexpr uint32_t kTileReduceBlocks = 1024;
+
+// A tile's summary: two counts (the builder: its occupied cells, 0; the editor: its clears, its sets), whether it has a cell to emit
+// and the least and greatest position per axis of its occupied cells (the editor: of its sets).  Reduced: the sums, the number of
+// active tiles, the bounds.
+struct TileStat {
+    uint64_t count[2];
+    uint32_t active;
+    uint32_t pad;
+    int32_t lo[3], hi[3];
+};
+
+// a tile's weight in the scan of the active tiles: count[0] low, count[1] high (either total < 2^32, so the sums never carry)
+__device__ __forceinline__ uint64_t tile_weight(const TileStat& t) { return t.count[0] | t.count[1] << 32; }
+
+// The sums and bounds of the block's v -> *dst (thread 0).  tile: v is a thread's share of one tile, and dst->active is whether the
+// tile has a count; else dst->active is the sum of v.active.  lds: kTileWaves entries.
+__device__ __forceinline__ void block_tile_stat(TileStat v, bool tile, TileStat* lds, TileStat* dst) {
+    v.count[0] = wave_sum(v.count[0]);
+    v.count[1] = wave_sum(v.count[1]);
+    v.active = wave_sum(v.active);
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1)
+#pragma unroll
+        for (int a = 0; a < 3; a++) {
+            v.lo[a] = min(v.lo[a], __shfl_xor(v.lo[a], off, 64));
+            v.hi[a] = max(v.hi[a], __shfl_xor(v.hi[a], off, 64));
+        }
+    if ((threadIdx.x & 63u) == 0u) lds[threadIdx.x >> 6] = v;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (uint32_t w = 1; w < kTileWaves; w++) {
+            v.count[0] += lds[w].count[0];
+            v.count[1] += lds[w].count[1];
+            v.active += lds[w].active;
+            for (int a = 0; a < 3; a++) { v.lo[a] = min(v.lo[a], lds[w].lo[a]); v.hi[a] = max(v.hi[a], lds[w].hi[a]); }
+        }
+        if (tile) v.active = v.count[0] + v.count[1] != 0u ? 1u : 0u;
+        *dst = v;
+    }
+}
+
+// In-tile ranking.  With the tile staged in LDS at the in-tile Morton index, thread 64 wave + lane takes cell 256 j + 64 wave + lane
+// in round j.  tile_rank_scan: off[k][4 j + wave] = the cells of list k (flag(j, k)) before round j's wave, one ballot per
+// (round, wave) and one wave-wide scan of the 64 counts per list.  tile_rank: a flagged cell's rank in its list.
+template <uint32_t N, typename Flag> __device__ __forceinline__ void tile_rank_scan(Flag flag, uint32_t (*off)[kTileRounds * kTileWaves]) {
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (uint32_t j = 0; j < kTileRounds; j++)
+#pragma unroll
+        for (uint32_t k = 0; k < N; k++) {
+            const uint64_t b = __ballot(flag(j, k));
+            if (lane == 0u) off[k][j * kTileWaves + wave] = uint32_t(__popcll(b));
+        }
+    __syncthreads();
+    if (wave == 0u)
+#pragma unroll
+        for (uint32_t k = 0; k < N; k++) {
+            const uint32_t c = off[k][lane];
+            off[k][lane] = wave_inclusive(c, lane) - c;
+        }
+    __syncthreads();
+}
+
+__device__ __forceinline__ uint32_t tile_rank(const uint32_t* off, uint32_t j, bool flag) {
+    return off[j * kTileWaves + (threadIdx.x >> 6)] + lanes_below(__ballot(flag));
+}
+
 // The leaf word of the voxel at u = p + 2^depth (u inside the root cube [0, 2^(depth+1))^3), 0 where there is none: the descent from
 // the root record along base + popc(mask & (bit(s) - 1)), as extract.hip walks, so it reads every layout of the 8-byte records.
 __device__ __forceinline__ uint32_t leaf_at(const SvoRecord* svo, const int32_t* leaves, uint32_t depth, uint32_t ux, uint32_t uy,
@@ -99,6 +195,19 @@ __device__ __forceinline__ uint32_t leaf_at(const SvoRecord* svo, const int32_t*
     }
     return 0u;
 }
+
+// stats[0 .. n) reduced to *dst on `stream` (two launches); part: kTileReduceBlocks entries.
+hipError_t launch_tile_reduce(const TileStat* stats, uint32_t n, TileStat* part, TileStat* dst, hipStream_t stream);
+
+// The `active` active tiles of g's ntiles in path order (depth >= 4), enqueued on `stream`: the tiles keyed by tile_code, inactive
+// ones past every code, sorted (radix_sort_pairs); then their weights scanned in that order.  order[0 .. active): their indices,
+// offset[0 .. active): the exclusive prefix sums of their weights.  The buffers live as long as *out.  who: the API call.
+struct TileOrder {
+    ScratchBuffer keys[2], vals[2], hist, totals, part, offset;
+    const uint32_t* order = nullptr;
+};
+int order_active_tiles(const GridDesc& g, const TileStat* stats, uint32_t ntiles, uint32_t active, uint32_t depth, hipStream_t stream,
+                       const char* who, TileOrder* out);
 
 // The scene of the grid's occupied cells, exactly as build_svo_device_list builds it from them as a list.  pal: for format 1, 256
 // leaf words in device memory (entry 0 = 0).  The grid is read on `stream` behind what is enqueued there; waits for the result.

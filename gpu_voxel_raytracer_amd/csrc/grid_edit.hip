@@ -5,46 +5,34 @@
 //   outside       SET / REPLACE, a box that leaves the root cube: every cell of the box outside the cube (up to 6 slabs) is read, no
 //                 descent; an occupied one raises a flag (a plain store of 1: every writer writes the same word)
 //   tile diff     one workgroup per 16-aligned tile of box ∩ root cube (grid_build.hip's tiles): a thread per 16-cell row loads the
-//                 row (load_row), finds s(p) by leaf_at's descent for the cells the mode needs, and counts the tile's sets and
-//                 clears and the min / max of its set cells per axis -> reduced -> one read-back
-//   tile codes    the tiles with an action keyed by the Morton code of their u-tile, the others past every code -> radix_sort_pairs
-//                 -> the active tiles first, in path order; their (clears, sets) counts scanned in that order
+//                 row (load_row), finds s(p) by leaf_at's descent for the cells the mode needs, and sums a TileStat (grid.h) of the
+//                 tile's clears and sets and the min / max of its set cells per axis -> reduced -> one read-back
+//   order         the tile pipeline's order_active_tiles (grid.h): the tiles with an action first, in path order; their packed
+//                 (clears, sets) counts scanned in that order
 //   emit          one workgroup per active tile: the diff again, staged in LDS in in-tile Morton order, each list ranked by wave
-//                 ballots -> keys (and the sets' words) at the tile's offsets.  Tiles in path order and cells in Morton order give
-//                 each list sorted and unique by path key, as api_edit.hip's host sort does
+//                 ballots (tile_rank) -> keys (and the sets' words) at the tile's offsets.  Tiles in path order and cells in Morton
+//                 order give each list sorted and unique by path key, as api_edit.hip's host sort does
 //   cut           per list: the run starts of every level (key >> 3 (L + 1 - l) differs from the previous entry's) counted per chunk
 //                 of 4096 entries and level, one flat exclusive scan over [level][chunk] (which is also seg_off), one read-back of
 //                 the level counts for both lists, then child_begin and oct written by rank
 // Every position is a prefix sum; nothing is decided by an atomic, so two calls write the same bytes.
 #include <algorithm>
 #include <climits>
-#include <string>
 
 #include "block_scan.h"
 #include "ctx.h"
-#include "extract.h"
 #include "grid_edit.h"
 
 namespace vxrt {
 namespace {
 
-constexpr uint32_t kThreads = 256;                 // one thread per 16-cell row of a tile (16 x 16 rows)
-constexpr uint32_t kWaves = kThreads / 64;
-constexpr uint32_t kTileCells = 4096;
-constexpr uint32_t kChunk = 4096;                  // sorted tiles per offset block; list entries per cut chunk (16 per thread)
-constexpr uint32_t kChunkItems = kChunk / kThreads;
-constexpr uint32_t kReduceBlocks = 1024;
+constexpr uint32_t kThreads = kTileThreads;        // one thread per 16-cell row of a tile (16 x 16 rows)
+constexpr uint32_t kWaves = kTileWaves;
+constexpr uint32_t kChunk = 4096;                  // list entries per cut chunk (16 per thread)
 constexpr uint32_t kOutsideBlocks = 1024;
 
-struct Diff {
-    uint64_t set, clear;
-    uint32_t tiles;         // tiles with an action
-    uint32_t pad;
-    int32_t lo[3], hi[3];   // the set cells' least and greatest position per axis
-};
-
 struct Readback {
-    Diff all;
+    TileStat all;           // count[0]: the clears, count[1]: the sets
     uint32_t outside;       // an occupied cell lies outside the root cube
     uint32_t pad;
 };
@@ -71,41 +59,6 @@ __device__ __forceinline__ void row_diff(const GridEdit& e, const uint32_t* pal,
     *clears = cl;
 }
 
-__device__ __forceinline__ void tile_origin(const GridEdit& e, uint32_t tile, int p0[3]) {
-    if (e.small) {
-        p0[0] = p0[1] = p0[2] = -(1 << e.depth);
-    } else {
-        tile_coords(e.g, tile, &p0[0], &p0[1], &p0[2]);
-        for (int a = 0; a < 3; a++) p0[a] *= 16;
-    }
-}
-
-// the min / max of six coordinates and the sums of two counts over the block -> thread 0
-__device__ __forceinline__ void block_diff(uint64_t* set, uint64_t* clear, uint32_t* tiles, int lo[3], int hi[3], Diff* lds, Diff* dst) {
-    *set = wave_sum(*set);
-    *clear = wave_sum(*clear);
-    *tiles = wave_sum(*tiles);
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1)
-#pragma unroll
-        for (int a = 0; a < 3; a++) {
-            lo[a] = min(lo[a], __shfl_xor(lo[a], off, 64));
-            hi[a] = max(hi[a], __shfl_xor(hi[a], off, 64));
-        }
-    if ((threadIdx.x & 63u) == 0u) lds[threadIdx.x >> 6] = Diff{*set, *clear, *tiles, 0u, {lo[0], lo[1], lo[2]}, {hi[0], hi[1], hi[2]}};
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        Diff d = lds[0];
-        for (uint32_t v = 1; v < kWaves; v++) {
-            d.set += lds[v].set;
-            d.clear += lds[v].clear;
-            d.tiles += lds[v].tiles;
-            for (int a = 0; a < 3; a++) { d.lo[a] = min(d.lo[a], lds[v].lo[a]); d.hi[a] = max(d.hi[a], lds[v].hi[a]); }
-        }
-        *dst = d;
-    }
-}
-
 // ---- outside the root cube -----------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kThreads) void grid_edit_outside_kernel(const GridDesc g, uint64_t i0, uint64_t j0, uint64_t k0, uint64_t ni,
                                                                      uint64_t nj, uint64_t nk, uint32_t* flag) {
@@ -120,115 +73,42 @@ __global__ __launch_bounds__(kThreads) void grid_edit_outside_kernel(const GridD
 }
 
 // ---- tile diff -----------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kThreads) void grid_edit_diff_kernel(const GridEdit e, const uint32_t* pal, Diff* out) {
-    __shared__ Diff lds[kWaves];
+__global__ __launch_bounds__(kThreads) void grid_edit_diff_kernel(const GridEdit e, const uint32_t* pal, TileStat* out) {
+    __shared__ TileStat lds[kWaves];
     int p0[3];
-    tile_origin(e, blockIdx.x, p0);
+    tile_origin(e.g, e.small, e.depth, blockIdx.x, p0);
     const int px = p0[0] + int(threadIdx.x >> 4), py = p0[1] + int(threadIdx.x & 15u);
     uint32_t w[16], sets, clears;
     row_diff(e, pal, px, py, p0[2], w, &sets, &clears);
-    uint64_t set = uint32_t(__popc(sets)), clear = uint32_t(__popc(clears));
-    int lo[3] = {INT_MAX, INT_MAX, INT_MAX}, hi[3] = {INT_MIN, INT_MIN, INT_MIN};
+    TileStat v{{uint32_t(__popc(clears)), uint32_t(__popc(sets))}, 0, 0, {INT_MAX, INT_MAX, INT_MAX}, {INT_MIN, INT_MIN, INT_MIN}};
     if (sets) {
-        lo[0] = hi[0] = px;
-        lo[1] = hi[1] = py;
-        lo[2] = p0[2] + __builtin_ctz(sets);
-        hi[2] = p0[2] + 31 - __builtin_clz(sets);
+        v.lo[0] = v.hi[0] = px;
+        v.lo[1] = v.hi[1] = py;
+        v.lo[2] = p0[2] + __builtin_ctz(sets);
+        v.hi[2] = p0[2] + 31 - __builtin_clz(sets);
     }
-    uint32_t tiles = 0;
-    block_diff(&set, &clear, &tiles, lo, hi, lds, out + blockIdx.x);
-    if (threadIdx.x == 0) out[blockIdx.x].tiles = out[blockIdx.x].set + out[blockIdx.x].clear != 0u ? 1u : 0u;
-}
-
-// out[block] = the sums and the min / max over in[block, block + grid, ...)
-__global__ __launch_bounds__(kThreads) void grid_edit_reduce_kernel(const Diff* in, uint32_t n, Diff* out) {
-    __shared__ Diff lds[kWaves];
-    uint64_t set = 0, clear = 0;
-    uint32_t tiles = 0;
-    int lo[3] = {INT_MAX, INT_MAX, INT_MAX}, hi[3] = {INT_MIN, INT_MIN, INT_MIN};
-    for (uint32_t i = blockIdx.x * kThreads + threadIdx.x; i < n; i += gridDim.x * kThreads) {
-        const Diff d = in[i];
-        set += d.set;
-        clear += d.clear;
-        tiles += d.tiles;
-        for (int a = 0; a < 3; a++) { lo[a] = min(lo[a], d.lo[a]); hi[a] = max(hi[a], d.hi[a]); }
-    }
-    block_diff(&set, &clear, &tiles, lo, hi, lds, out + blockIdx.x);
-}
-
-// ---- tile codes and offsets ----------------------------------------------------------------------------------------------------
-// keys[t] = the Morton code of tile t's u-tile when it has an action, 2^bits (past every code) when it has none
-__global__ __launch_bounds__(kThreads) void grid_edit_code_kernel(const GridEdit e, const Diff* d, uint32_t ntiles, uint32_t bits,
-                                                                   uint64_t* keys, uint32_t* vals) {
-    const uint32_t t = blockIdx.x * kThreads + threadIdx.x;
-    if (t >= ntiles) return;
-    uint64_t key = uint64_t(1) << bits;
-    if (d[t].tiles) {
-        int tx, ty, tz;
-        tile_coords(e.g, t, &tx, &ty, &tz);
-        const int shift = 1 << (e.depth - 4u);
-        key = morton_tile(uint32_t(tx + shift), uint32_t(ty + shift), uint32_t(tz + shift), e.depth - 3u);
-    }
-    keys[t] = key;
-    vals[t] = t;
-}
-
-// a tile's two counts in one word: clears low, sets high (either total < 2^32, so the sums never carry)
-__device__ __forceinline__ uint64_t packed(const Diff& d) { return d.clear | d.set << 32; }
-
-__global__ __launch_bounds__(kThreads) void grid_edit_chunk_sum_kernel(const Diff* d, const uint32_t* order, uint32_t n, uint64_t* part) {
-    __shared__ uint64_t lds[kWaves];
-    uint64_t sum = 0;
-#pragma unroll 4
-    for (uint32_t j = 0; j < kChunkItems; j++) {
-        const uint32_t i = blockIdx.x * kChunk + j * kThreads + threadIdx.x;
-        if (i < n) sum += packed(d[order[i]]);
-    }
-    sum = wave_sum(sum);
-    if ((threadIdx.x & 63u) == 0u) lds[threadIdx.x >> 6] = sum;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint64_t all = 0;
-        for (uint32_t w = 0; w < kWaves; w++) all += lds[w];
-        part[blockIdx.x] = all;
-    }
-}
-
-__global__ __launch_bounds__(kThreads) void grid_edit_chunk_offsets_kernel(const Diff* d, const uint32_t* order, uint32_t n, const uint64_t* part,
-                                                                           uint64_t* offset) {
-    __shared__ uint64_t lds[kWaves];
-    uint64_t at = part[blockIdx.x];
-#pragma unroll 1
-    for (uint32_t j = 0; j < kChunkItems; j++) {
-        const uint32_t i = blockIdx.x * kChunk + j * kThreads + threadIdx.x;
-        const uint64_t c = i < n ? packed(d[order[i]]) : 0ull;
-        uint64_t total;
-        const uint64_t o = at + block_exclusive<uint64_t, kWaves>(c, lds, &total);
-        at += total;
-        if (i < n) offset[i] = o;
-    }
+    block_tile_stat(v, true, lds, out + blockIdx.x);
 }
 
 // ---- emit ----------------------------------------------------------------------------------------------------------------------
 // Workgroup b: the b-th active tile in path order (order[b]; small: the root cube of a depth < 4 tree, the only tile).  Its cells'
-// actions are staged in LDS at their in-tile Morton index m; cell m = 256 j + 64 wave + lane is ranked in round j by the wave's
-// ballot, the rounds and waves in that order by one wave-wide scan of the 64 (round, wave) counts of each list.
+// actions are staged in LDS at their in-tile Morton index and each list ranked by tile_rank; offset[b] packs the tile's first clear
+// (low) and first set (high).
 __global__ __launch_bounds__(kThreads) void grid_edit_emit_kernel(const GridEdit e, const uint32_t* pal, const uint32_t* order,
                                                                   const uint64_t* offset, uint64_t n_clear, uint64_t n_set, uint64_t* ckeys,
                                                                   uint64_t* skeys, int32_t* swords) {
     __shared__ uint32_t s_word[kTileCells];
     __shared__ uint8_t s_act[kTileCells];          // 1: clear, 2: set
-    __shared__ uint32_t s_offc[kTileCells / 64], s_offs[kTileCells / 64];
-    const uint32_t t = threadIdx.x, lane = t & 63u, wave = t >> 6;
+    __shared__ uint32_t s_off[2][kTileRounds * kWaves];
+    const uint32_t t = threadIdx.x;
     int p0[3];
     uint64_t code = 0, cat = 0, sat = 0;
     if (e.small) {
-        tile_origin(e, 0, p0);
+        tile_origin(e.g, 1u, e.depth, 0u, p0);
     } else {
         const uint32_t tile = order[blockIdx.x];
-        tile_origin(e, tile, p0);
-        const int shift = 1 << (e.depth - 4u);
-        code = morton_tile(uint32_t(p0[0] / 16 + shift), uint32_t(p0[1] / 16 + shift), uint32_t(p0[2] / 16 + shift), e.depth - 3u);
+        tile_origin(e.g, 0u, e.depth, tile, p0);
+        code = tile_code(e.g, tile, e.depth);
         const uint64_t o = offset[blockIdx.x];
         cat = o & 0xffffffffull;
         sat = o >> 32;
@@ -243,34 +123,20 @@ __global__ __launch_bounds__(kThreads) void grid_edit_emit_kernel(const GridEdit
         s_act[mi] = uint8_t((clears >> z & 1u) | (sets >> z & 1u) << 1);
     }
     __syncthreads();
+    tile_rank_scan<2>([&](uint32_t j, uint32_t k) { return s_act[j * kThreads + t] == k + 1u; }, s_off);
 #pragma unroll
-    for (uint32_t j = 0; j < kTileCells / kThreads; j++) {
-        const uint32_t act = s_act[j * kThreads + t];
-        const uint64_t cb = __ballot(act == 1u), sb = __ballot(act == 2u);
-        if (lane == 0u) { s_offc[j * kWaves + wave] = uint32_t(__popcll(cb)); s_offs[j * kWaves + wave] = uint32_t(__popcll(sb)); }
-    }
-    __syncthreads();
-    if (wave == 0u) {
-        const uint32_t c = s_offc[lane], s = s_offs[lane];
-        s_offc[lane] = wave_inclusive(c, lane) - c;
-        s_offs[lane] = wave_inclusive(s, lane) - s;
-    }
-    __syncthreads();
-#pragma unroll
-    for (uint32_t j = 0; j < kTileCells / kThreads; j++) {
+    for (uint32_t j = 0; j < kTileRounds; j++) {
         const uint32_t mi = j * kThreads + t;
         const uint32_t act = s_act[mi];
-        const uint64_t cb = __ballot(act == 1u), sb = __ballot(act == 2u);
         const uint64_t key = code << 12 | mi;
+        const uint64_t oc = cat + tile_rank(s_off[0], j, act == 1u), os = sat + tile_rank(s_off[1], j, act == 2u);
         // o < n unless the grid changed between the passes (a race of the caller's): then nothing past the lists is written
         if (act == 1u) {
-            const uint64_t o = cat + s_offc[j * kWaves + wave] + __builtin_amdgcn_mbcnt_hi(uint32_t(cb >> 32), __builtin_amdgcn_mbcnt_lo(uint32_t(cb), 0u));
-            if (o < n_clear) ckeys[o] = key;
+            if (oc < n_clear) ckeys[oc] = key;
         } else if (act == 2u) {
-            const uint64_t o = sat + s_offs[j * kWaves + wave] + __builtin_amdgcn_mbcnt_hi(uint32_t(sb >> 32), __builtin_amdgcn_mbcnt_lo(uint32_t(sb), 0u));
-            if (o < n_set) {
-                skeys[o] = key;
-                swords[o] = int32_t(s_word[mi]);
+            if (os < n_set) {
+                skeys[os] = key;
+                swords[os] = int32_t(s_word[mi]);
             }
         }
     }
@@ -363,17 +229,6 @@ __global__ __launch_bounds__(kThreads) void cut_write_kernel(const uint64_t* key
     }
 }
 
-hipError_t alloc(ScratchBuffer* b, size_t bytes) {
-    const hipError_t e = b->alloc(bytes ? bytes : 16);
-    if (e != hipSuccess) { (void)hipGetLastError(); b->p = nullptr; }
-    return e;
-}
-
-int fail(hipError_t e, const char* what) {
-    set_error(std::string("vxrt_edit_voxel_grid: allocating ") + what + ": " + hipGetErrorString(e));
-    return VXRT_E_DEVICE;
-}
-
 size_t align16(size_t v) { return (v + 15) & ~size_t(15); }
 
 }  // namespace
@@ -384,12 +239,13 @@ int diff_grid_device(const GridEdit& e, const uint32_t* pal, const uint64_t (*ou
     if (ntiles64 >= (uint64_t(1) << 31)) { set_error("vxrt_edit_voxel_grid: 2^31 tiles or more"); return VXRT_E_SCENE; }
     const uint32_t ntiles = uint32_t(ntiles64);
     const uint32_t L = e.depth;
+    const char* who = "vxrt_edit_voxel_grid";
 
     // outside the cube, then the tile diff -> one read-back
     ScratchBuffer diff, red;
-    if (hipError_t err = alloc(&diff, size_t(ntiles) * sizeof(Diff)); err != hipSuccess) return fail(err, "the tile counts");
-    if (hipError_t err = alloc(&red, kReduceBlocks * sizeof(Diff) + sizeof(Readback)); err != hipSuccess) return fail(err, "the tile counts");
-    Readback* rb = reinterpret_cast<Readback*>(red.as<Diff>() + kReduceBlocks);
+    if (int rc = alloc_scratch(&diff, size_t(ntiles) * sizeof(TileStat), who, "the tile counts")) return rc;
+    if (int rc = alloc_scratch(&red, kTileReduceBlocks * sizeof(TileStat) + sizeof(Readback), who, "the tile counts")) return rc;
+    Readback* rb = reinterpret_cast<Readback*>(red.as<TileStat>() + kTileReduceBlocks);
     HIP_TRY(hipMemsetAsync(rb, 0, sizeof(Readback), s));
     for (uint32_t b = 0; b < n_outside; b++) {
         const uint64_t* o = outside[b];
@@ -400,73 +256,41 @@ int diff_grid_device(const GridEdit& e, const uint32_t* pal, const uint64_t (*ou
         HIP_TRY(hipGetLastError());
     }
     if (ntiles) {
-        hipLaunchKernelGGL(grid_edit_diff_kernel, dim3(ntiles), dim3(kThreads), 0, s, e, pal, diff.as<Diff>());
+        hipLaunchKernelGGL(grid_edit_diff_kernel, dim3(ntiles), dim3(kThreads), 0, s, e, pal, diff.as<TileStat>());
         HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(grid_edit_reduce_kernel, dim3(kReduceBlocks), dim3(kThreads), 0, s, diff.as<Diff>(), ntiles, red.as<Diff>());
-        HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(grid_edit_reduce_kernel, dim3(1), dim3(kThreads), 0, s, red.as<Diff>(), kReduceBlocks, &rb->all);
-        HIP_TRY(hipGetLastError());
+        HIP_TRY(launch_tile_reduce(diff.as<TileStat>(), ntiles, red.as<TileStat>(), &rb->all, s));
     }
     Readback all;
     HIP_TRY(hipMemcpyAsync(&all, rb, sizeof all, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     if (all.outside) { set_error("vxrt_edit_voxel_grid: an occupied cell lies outside the scene's root cube"); return VXRT_E_SCENE; }
-    if (all.all.set >= (uint64_t(1) << 32) || all.all.clear >= (uint64_t(1) << 32)) {
+    const uint64_t n_clear64 = all.all.count[0], n_set64 = all.all.count[1];
+    if (n_set64 >= (uint64_t(1) << 32) || n_clear64 >= (uint64_t(1) << 32)) {
         set_error("vxrt_edit_voxel_grid: 2^32 sets or clears or more");
         return VXRT_E_SCENE;
     }
-    out->set = all.all.set;
-    out->cleared = all.all.clear;
-    if (all.all.set == 0 && all.all.clear == 0) return VXRT_OK;
-    const uint32_t n_clear = uint32_t(all.all.clear), n_set = uint32_t(all.all.set), active = all.all.tiles;
+    out->set = n_set64;
+    out->cleared = n_clear64;
+    if (n_set64 == 0 && n_clear64 == 0) return VXRT_OK;
+    const uint32_t n_clear = uint32_t(n_clear64), n_set = uint32_t(n_set64), active = all.all.active;
 
     // the lists: keys of both, the sets' words
     ScratchBuffer& lists = out->buf[0];
     const size_t o_skeys = align16(size_t(n_clear) * 8), o_words = o_skeys + align16(size_t(n_set) * 8);
-    if (hipError_t err = alloc(&lists, o_words + size_t(n_set) * 4); err != hipSuccess) return fail(err, "the lists");
+    if (int rc = alloc_scratch(&lists, o_words + size_t(n_set) * 4, who, "the lists")) return rc;
     uint64_t* ckeys = lists.as<uint64_t>();
     uint64_t* skeys = reinterpret_cast<uint64_t*>(lists.as<char>() + o_skeys);
     int32_t* swords = reinterpret_cast<int32_t*>(lists.as<char>() + o_words);
+    TileOrder tiles;
     if (e.small) {   // the root cube is the one tile
-        const uint64_t zero = 0;
-        ScratchBuffer off;
-        if (hipError_t err = alloc(&off, sizeof zero); err != hipSuccess) return fail(err, "the tile offsets");
-        HIP_TRY(hipMemsetAsync(off.p, 0, sizeof zero, s));
-        hipLaunchKernelGGL(grid_edit_emit_kernel, dim3(1), dim3(kThreads), 0, s, e, pal, nullptr, off.as<uint64_t>(), uint64_t(n_clear),
-                           uint64_t(n_set), ckeys, skeys, swords);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipStreamSynchronize(s));   // `off` is freed on return
+        hipLaunchKernelGGL(grid_edit_emit_kernel, dim3(1), dim3(kThreads), 0, s, e, pal, nullptr, nullptr, uint64_t(n_clear), uint64_t(n_set),
+                           ckeys, skeys, swords);
     } else {
-        ScratchBuffer keys[2], vals[2], hist, totals, cpart, offset;
-        for (int b = 0; b < 2; b++) {
-            if (hipError_t err = alloc(&keys[b], size_t(ntiles) * sizeof(uint64_t)); err != hipSuccess) return fail(err, "the tile codes");
-            if (hipError_t err = alloc(&vals[b], size_t(ntiles) * sizeof(uint32_t)); err != hipSuccess) return fail(err, "the tile codes");
-        }
-        const uint32_t chunks = (active + kChunk - 1) / kChunk;
-        if (hipError_t err = alloc(&hist, radix_hist_entries(ntiles) * sizeof(uint32_t)); err != hipSuccess) return fail(err, "the digit counts");
-        if (hipError_t err = alloc(&totals, 256 * sizeof(uint32_t)); err != hipSuccess) return fail(err, "the digit counts");
-        if (hipError_t err = alloc(&cpart, (size_t(chunks) + 1) * sizeof(uint64_t)); err != hipSuccess) return fail(err, "the tile offsets");
-        if (hipError_t err = alloc(&offset, size_t(active) * sizeof(uint64_t)); err != hipSuccess) return fail(err, "the tile offsets");
-        const uint32_t bits = 3u * (L - 3u);
-        hipLaunchKernelGGL(grid_edit_code_kernel, dim3((ntiles + kThreads - 1) / kThreads), dim3(kThreads), 0, s, e, diff.as<Diff>(), ntiles,
-                           bits, keys[0].as<uint64_t>(), vals[0].as<uint32_t>());
-        HIP_TRY(hipGetLastError());
-        uint64_t* kp[2] = {keys[0].as<uint64_t>(), keys[1].as<uint64_t>()};
-        uint32_t* vp[2] = {vals[0].as<uint32_t>(), vals[1].as<uint32_t>()};
-        int cur = 0;
-        HIP_TRY(radix_sort_pairs(kp, vp, ntiles, bits + 1u, hist.as<uint32_t>(), totals.as<uint32_t>(), s, &cur));
-        const uint32_t* order = vp[cur];
-        hipLaunchKernelGGL(grid_edit_chunk_sum_kernel, dim3(chunks), dim3(kThreads), 0, s, diff.as<Diff>(), order, active, cpart.as<uint64_t>());
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(launch_extract_scan(cpart.as<uint64_t>(), chunks, s));
-        hipLaunchKernelGGL(grid_edit_chunk_offsets_kernel, dim3(chunks), dim3(kThreads), 0, s, diff.as<Diff>(), order, active,
-                           cpart.as<uint64_t>(), offset.as<uint64_t>());
-        HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(grid_edit_emit_kernel, dim3(active), dim3(kThreads), 0, s, e, pal, order, offset.as<uint64_t>(), uint64_t(n_clear),
-                           uint64_t(n_set), ckeys, skeys, swords);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipStreamSynchronize(s));   // the scratch above is freed on return
+        if (int rc = order_active_tiles(e.g, diff.as<TileStat>(), ntiles, active, L, s, who, &tiles)) return rc;
+        hipLaunchKernelGGL(grid_edit_emit_kernel, dim3(active), dim3(kThreads), 0, s, e, pal, tiles.order, tiles.offset.as<uint64_t>(),
+                           uint64_t(n_clear), uint64_t(n_set), ckeys, skeys, swords);
     }
+    HIP_TRY(hipGetLastError());
 
     // the cut of both lists: counts per level and chunk, one flat scan each -> one read-back of both lists' seg_off
     const uint32_t levels = L + 2u;
@@ -480,15 +304,15 @@ int diff_grid_device(const GridEdit& e, const uint32_t* pal, const uint64_t (*ou
         part_bytes += align16((size_t(levels) * chunks[b] + 1) * sizeof(uint64_t));
     }
     ScratchBuffer part, segs;
-    if (hipError_t err = alloc(&part, part_bytes); err != hipSuccess) return fail(err, "the level counts");
-    if (hipError_t err = alloc(&segs, 2 * 32 * sizeof(uint32_t)); err != hipSuccess) return fail(err, "the level counts");
+    if (int rc = alloc_scratch(&part, part_bytes, who, "the level counts")) return rc;
+    if (int rc = alloc_scratch(&segs, 2 * 32 * sizeof(uint32_t), who, "the level counts")) return rc;
     HIP_TRY(hipMemsetAsync(segs.p, 0, 2 * 32 * sizeof(uint32_t), s));
     for (int b = 0; b < 2; b++) {
         if (m[b] == 0) continue;
         uint64_t* p = reinterpret_cast<uint64_t*>(part.as<char>() + o_part[b]);
         hipLaunchKernelGGL(cut_count_kernel, dim3(chunks[b]), dim3(kThreads), 0, s, lkeys[b], m[b], L, chunks[b], p);
         HIP_TRY(hipGetLastError());
-        HIP_TRY(launch_extract_scan(p, levels * chunks[b], s));
+        HIP_TRY(launch_exclusive_scan(p, levels * chunks[b], s));
         hipLaunchKernelGGL(cut_offsets_kernel, dim3(1), dim3(64), 0, s, p, L, chunks[b], segs.as<uint32_t>() + 32 * b);
         HIP_TRY(hipGetLastError());
     }
@@ -508,7 +332,7 @@ int diff_grid_device(const GridEdit& e, const uint32_t* pal, const uint64_t (*ou
     }
     const size_t o_node = bytes, o_flag = o_node + align16(node_max * 4), o_out = o_flag + align16(node_max);
     ScratchBuffer& batch = out->buf[1];
-    if (hipError_t err = alloc(&batch, o_out + 8 * 4); err != hipSuccess) return fail(err, "the edit batches");
+    if (int rc = alloc_scratch(&batch, o_out + 8 * 4, who, "the edit batches")) return rc;
     char* base = batch.as<char>();
     for (int b = 0; b < 2; b++) {
         if (m[b] == 0) continue;
@@ -527,7 +351,7 @@ int diff_grid_device(const GridEdit& e, const uint32_t* pal, const uint64_t (*ou
         eb.out = reinterpret_cast<uint32_t*>(base + o_out);
         for (int a = 0; a < 3; a++) { eb.lo[a] = all.all.lo[a]; eb.hi[a] = all.all.hi[a]; }
     }
-    HIP_TRY(hipStreamSynchronize(s));   // `part` is freed on return
+    HIP_TRY(hipStreamSynchronize(s));   // `part` and `tiles` are freed on return
     return VXRT_OK;
 }
 

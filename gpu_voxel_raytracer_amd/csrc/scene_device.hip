@@ -16,6 +16,7 @@
 #include <cstdint>
 #include <vector>
 
+#include "ctx.h"
 #include "kernels.h"
 #include "scene_host.h"
 
@@ -228,13 +229,6 @@ __global__ __launch_bounds__(256) void treelet_kernel(const SvoRecord* old, SvoR
     }
 }
 
-struct DevBuf {
-    void* p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 1); }
-    template <typename T> T* as() const { return static_cast<T*>(p); }
-};
-
 #define DEV_TRY(expr)                                                                   \
     do {                                                                                \
         hipError_t e_ = (expr);                                                         \
@@ -267,18 +261,18 @@ int build_menger_svo_device(uint32_t level, uint32_t clip, const uint8_t mrgb[4]
         for (uint32_t k = 0; k < level; k++) { if (v % 3 == 1) m |= 1u << k; v /= 3; }
         ones[c] = uint16_t(m);
     }
-    DevBuf d_ones;
-    DEV_TRY(d_ones.alloc(ones.size() * sizeof(uint16_t)));
+    ScratchBuffer d_ones;
+    if (int rc = alloc_scratch(&d_ones, ones.size() * sizeof(uint16_t), "menger", "the digit table")) return rc;
     DEV_TRY(hipMemcpyAsync(d_ones.p, ones.data(), ones.size() * sizeof(uint16_t), hipMemcpyHostToDevice, stream));
     const SpongeDev sp{d_ones.as<uint16_t>(), side, mrgb[0], mrgb[1], mrgb[2], mrgb[3], emissive_period};
 
     // ---- sweep 1: dense masks, bottom-up.  Tree level l (1 .. depth) has cubes of side 2^(depth+1-l) and (2^(l-1))^3 potential nodes
-    std::vector<DevBuf> dense(depth + 1);
+    std::vector<ScratchBuffer> dense(depth + 1);
     std::vector<uint32_t> dim(depth + 1, 0);
     for (uint32_t l = depth; l >= 1; l--) {
         dim[l] = 1u << (l - 1);
         const size_t n3 = size_t(dim[l]) * dim[l] * dim[l];
-        DEV_TRY(dense[l].alloc(n3));
+        if (int rc = alloc_scratch(&dense[l], n3, "menger", "the dense masks")) return rc;
         const unsigned blocks = unsigned((n3 + 255) / 256);
         if (l == depth)
             hipLaunchKernelGGL(dense_leaf_masks_kernel, dim3(blocks), dim3(256), 0, stream, sp, dim[l], dense[l].as<uint8_t>());
@@ -287,8 +281,8 @@ int build_menger_svo_device(uint32_t level, uint32_t clip, const uint8_t mrgb[4]
         DEV_TRY(hipGetLastError());
     }
     // level sizes: nodes of level l = non-empty entries of dense level l; leaf words = set bits of the last level
-    DevBuf d_totals;
-    DEV_TRY(d_totals.alloc((depth + 1) * 2 * sizeof(unsigned long long)));
+    ScratchBuffer d_totals;
+    if (int rc = alloc_scratch(&d_totals, (depth + 1) * 2 * sizeof(unsigned long long), "menger", "the level totals")) return rc;
     DEV_TRY(hipMemsetAsync(d_totals.p, 0, (depth + 1) * 2 * sizeof(unsigned long long), stream));
     for (uint32_t l = 1; l <= depth; l++) {
         const size_t n3 = size_t(dim[l]) * dim[l] * dim[l];
@@ -304,12 +298,12 @@ int build_menger_svo_device(uint32_t level, uint32_t clip, const uint8_t mrgb[4]
     const bool any = totals[2] != 0;
     if (nodes >= (size_t(1) << 32) || nleaves >= (size_t(1) << 32)) { set_error("menger: too many nodes"); return VXRT_E_SCENE; }
 
-    DevBuf svo, leaves, coords_a, coords_b, tile_sums;
-    DEV_TRY(svo.alloc(nodes * sizeof(SvoRecord)));
-    DEV_TRY(leaves.alloc((nleaves ? nleaves : 1) * sizeof(int32_t)));
-    DEV_TRY(coords_a.alloc(max_level * sizeof(uint32_t)));
-    DEV_TRY(coords_b.alloc(max_level * sizeof(uint32_t)));
-    DEV_TRY(tile_sums.alloc(((max_level + kScanTile - 1) / kScanTile + 1) * sizeof(uint32_t)));
+    ScratchBuffer svo, leaves, coords_a, coords_b, tile_sums;
+    if (int rc = alloc_scratch(&svo, nodes * sizeof(SvoRecord), "menger", "the records")) return rc;
+    if (int rc = alloc_scratch(&leaves, (nleaves ? nleaves : 1) * sizeof(int32_t), "menger", "the leaf words")) return rc;
+    if (int rc = alloc_scratch(&coords_a, max_level * sizeof(uint32_t), "menger", "the node coordinates")) return rc;
+    if (int rc = alloc_scratch(&coords_b, max_level * sizeof(uint32_t), "menger", "the node coordinates")) return rc;
+    if (int rc = alloc_scratch(&tile_sums, ((max_level + kScanTile - 1) / kScanTile + 1) * sizeof(uint32_t), "menger", "the scan partials")) return rc;
     // root: centre 0, everything lives in its slot 7 (x, y, z >= 0); its one child is record 1
     *root = SvoRecord{any ? 0x80u : 0u, 1u};
     DEV_TRY(hipMemcpyAsync(svo.p, root, sizeof(SvoRecord), hipMemcpyHostToDevice, stream));
@@ -353,8 +347,8 @@ int reorder_bottom_treelets(SvoRecord** d_svo, size_t n, const std::vector<size_
     }
     const uint32_t fp = uint32_t(level_first[depth - 3]), fa = uint32_t(level_first[depth - 2]), fb = uint32_t(level_first[depth - 1]), fc = uint32_t(level_first[depth]);
     if (!(fp < fa && fa < fb && fb < fc && fc < n)) { set_error("treelets: level starts out of order"); return VXRT_E_INVALID; }
-    DevBuf out;
-    DEV_TRY(out.alloc(n * sizeof(SvoRecord)));
+    ScratchBuffer out;
+    if (int rc = alloc_scratch(&out, n * sizeof(SvoRecord), "treelets", "the records")) return rc;
     const uint32_t keep = levels == 3 ? fp : fa;        // the levels above the treelets' parents: as they are
     DEV_TRY(hipMemcpyAsync(out.p, *d_svo, size_t(keep) * sizeof(SvoRecord), hipMemcpyDeviceToDevice, stream));
     if (levels == 3)

@@ -542,29 +542,15 @@ class Context:
         (GRID_WORD32: bit 31 set = a voxel).  The context's stream first waits for torch's current stream.  Same records, stats and
         frames as recreate_octree of the occupied cells as a list."""
         import torch
-        dev = torch.device("cuda", self.device)
-        cells = torch.as_tensor(cells, device=dev) if isinstance(cells, np.ndarray) else cells
-        if not isinstance(cells, torch.Tensor) or cells.dim() != 3:
-            raise TypeError("cells must be a 3-D torch tensor or numpy array")
-        if cells.device != dev:
-            raise ValueError(f"cells must be on {dev}")
-        fmt = {torch.uint8: GRID_PALETTE8, torch.int32: GRID_WORD32}.get(cells.dtype)
-        if fmt is None:
-            raise ValueError("cells must be uint8 (palette indices) or int32 (leaf words)")
-        cells = cells.contiguous()
-        pal = None if palette is None else np.ascontiguousarray(np.asarray(palette, np.uint8).reshape(256, 4))
-        dims = (C.c_uint32 * 3)(*cells.shape)
-        org = (C.c_int32 * 3)(*(int(v) for v in origin))
-        self.context_wait_stream(torch.cuda.current_stream(dev).cuda_stream)
+        cells, fmt, pal, dims, org, _ = self._grid_args(cells, origin, palette)
+        self.context_wait_stream(torch.cuda.current_stream(cells.device).cuda_stream)
         self._chk(self._L.vxrt_set_voxel_grid(self._h, C.c_void_p(cells.data_ptr() if cells.numel() else None), C.c_int(fmt), dims, org,
                                               _p(pal)), "vxrt_set_voxel_grid")
 
-    def edit_voxel_grid(self, cells, origin=(0, 0, 0), palette=None, mode="replace"):
-        """vxrt_edit_voxel_grid (include/vxrt_grid_edit.h): write the grid into the box origin + [0, cells.shape) of the scene in place,
-        on the device.  cells and palette as set_voxel_grid; mode "replace" (every cell of the box becomes the grid's), "set" (occupied
-        cells are set) or "clear" (occupied cells are cleared), or a GRID_EDIT_* value.  Exactly clear_voxels(clears) then
-        edit_voxels(sets) of the cells that change; the temporal history is kept.  The context's stream first waits for torch's
-        current stream.  -> (cells set, cells cleared)."""
+    def _grid_args(self, cells, origin, palette, edit=False, mode=None):
+        """set_voxel_grid's and edit_voxel_grid's arguments -> (contiguous tensor on the context's device, format, palette array or
+        None, dims, origin, and for edit_voxel_grid its mode as a GRID_EDIT_* value), checked in that order but with the mode right
+        after the format."""
         import torch
         dev = torch.device("cuda", self.device)
         cells = torch.as_tensor(cells, device=dev) if isinstance(cells, np.ndarray) else cells
@@ -575,15 +561,26 @@ class Context:
         fmt = {torch.uint8: GRID_PALETTE8, torch.int32: GRID_WORD32}.get(cells.dtype)
         if fmt is None:
             raise ValueError("cells must be uint8 (palette indices) or int32 (leaf words)")
-        m = GRID_EDIT_MODES.get(mode, mode) if isinstance(mode, str) else int(mode)
-        if isinstance(m, str):
-            raise ValueError(f"mode must be one of {sorted(GRID_EDIT_MODES)}")
+        if edit:
+            mode = GRID_EDIT_MODES.get(mode, mode) if isinstance(mode, str) else int(mode)
+            if isinstance(mode, str):
+                raise ValueError(f"mode must be one of {sorted(GRID_EDIT_MODES)}")
         cells = cells.contiguous()
         pal = None if palette is None else np.ascontiguousarray(np.asarray(palette, np.uint8).reshape(256, 4))
         dims = (C.c_uint32 * 3)(*cells.shape)
         org = (C.c_int32 * 3)(*(int(v) for v in origin))
+        return cells, fmt, pal, dims, org, mode
+
+    def edit_voxel_grid(self, cells, origin=(0, 0, 0), palette=None, mode="replace"):
+        """vxrt_edit_voxel_grid (include/vxrt_grid_edit.h): write the grid into the box origin + [0, cells.shape) of the scene in place,
+        on the device.  cells and palette as set_voxel_grid; mode "replace" (every cell of the box becomes the grid's), "set" (occupied
+        cells are set) or "clear" (occupied cells are cleared), or a GRID_EDIT_* value.  Exactly clear_voxels(clears) then
+        edit_voxels(sets) of the cells that change; the temporal history is kept.  The context's stream first waits for torch's
+        current stream.  -> (cells set, cells cleared)."""
+        import torch
+        cells, fmt, pal, dims, org, m = self._grid_args(cells, origin, palette, edit=True, mode=mode)
         counts = (C.c_uint64 * 2)()
-        self.context_wait_stream(torch.cuda.current_stream(dev).cuda_stream)
+        self.context_wait_stream(torch.cuda.current_stream(cells.device).cuda_stream)
         self._chk(self._L.vxrt_edit_voxel_grid(self._h, C.c_void_p(cells.data_ptr() if cells.numel() else None), C.c_int(fmt), dims, org,
                                                _p(pal), C.c_int(m), counts), "vxrt_edit_voxel_grid")
         return int(counts[0]), int(counts[1])

@@ -28,7 +28,7 @@ from gpu_voxel_raytracer_amd import Context, scenes  # noqa: E402
 from gpu_voxel_raytracer_amd.scenes import CONFIG5  # noqa: E402
 
 KERNELS = ("bounds_kernel", "bounds_reduce_kernel", "keys_kernel", "radix_hist_kernel", "radix_scan_kernel", "radix_scatter_kernel",
-           "flag_count_kernel", "extract_scan_kernel", "dedupe_write_kernel", "level_hist_kernel", "level_sum_kernel", "level_write_kernel")
+           "flag_count_kernel", "exclusive_scan_kernel", "dedupe_write_kernel", "level_hist_kernel", "level_sum_kernel", "level_write_kernel")
 
 
 def stats_ms(samples):

@@ -8,7 +8,7 @@ scenes.CONFIG5; count, and fetch when the host has the memory for its 10.5 GB), 
     python scripts/extract_latency.py [--out profiles/extract/latency.json]      all cases, host clock
     python scripts/extract_latency.py --case c5_box16_fetch --repeats 20        one case (the kernel-trace runs, one process per case:
                                                                                  rocprofv3 --kernel-trace --stats -d DIR/c5_box16 -- python ...)
-    python scripts/extract_latency.py --summarize DIR [--out kernel_times.json]  per-call device time of the extract_* kernels of those runs
+    python scripts/extract_latency.py --summarize DIR [--out kernel_times.json]  per-call device time of the extract_* kernels (and their scan) of those runs
 """
 import argparse
 import csv
@@ -117,7 +117,7 @@ def summarize(root):
         for f in files:
             with open(f) as fh:
                 for r in csv.DictReader(fh):
-                    if "extract_" in r["Kernel_Name"]:
+                    if "extract_" in r["Kernel_Name"] or "exclusive_scan" in r["Kernel_Name"]:
                         rows.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r["Kernel_Name"]))
         rows.sort()
         rows = rows[info["skip_dispatches"]:]
@@ -129,7 +129,7 @@ def summarize(root):
         span = [(rows[(i + 1) * per - 1][1] - rows[i * per][0]) / 1e3 for i in range(calls)]
         by_kernel = {}
         for s, e, k in rows:
-            name = next(n for n in ("extract_count", "extract_scan", "extract_expand") if n in k)
+            name = next(n for n in ("extract_count", "exclusive_scan", "extract_expand") if n in k)
             by_kernel.setdefault(name, []).append((e - s) / 1e3)
         out[os.path.basename(case_dir)] = {
             "calls": calls, "dispatches_per_call": per,

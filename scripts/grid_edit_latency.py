@@ -26,8 +26,8 @@ from gpu_voxel_raytracer_amd import Context, scenes  # noqa: E402
 from gpu_voxel_raytracer_amd.scenes import CONFIG5  # noqa: E402
 
 DEV = torch.device("cuda", 0)
-KERNELS = ("grid_edit_outside_kernel", "grid_edit_diff_kernel", "grid_edit_reduce_kernel", "grid_edit_code_kernel", "radix_hist_kernel",
-           "radix_scan_kernel", "radix_scatter_kernel", "grid_edit_chunk_sum_kernel", "extract_scan_kernel", "grid_edit_chunk_offsets_kernel",
+KERNELS = ("grid_edit_outside_kernel", "grid_edit_diff_kernel", "grid_tile_reduce_kernel", "grid_tile_code_kernel", "radix_hist_kernel",
+           "radix_scan_kernel", "radix_scatter_kernel", "grid_chunk_sum_kernel", "exclusive_scan_kernel", "grid_chunk_offsets_kernel",
            "grid_edit_emit_kernel", "cut_count_kernel", "cut_offsets_kernel", "cut_write_kernel", "edit_kernel")
 
 

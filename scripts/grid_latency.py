@@ -35,8 +35,8 @@ from gpu_voxel_raytracer_amd.scenes import CONFIG5  # noqa: E402
 from device_build_latency import scratch_bytes as list_scratch_bytes, stats_ms, timed  # noqa: E402
 
 DEV = torch.device("cuda", 0)
-KERNELS = ("grid_tile_stats_kernel", "grid_stat_reduce_kernel", "grid_tile_code_kernel", "radix_hist_kernel", "radix_scan_kernel",
-           "radix_scatter_kernel", "grid_chunk_sum_kernel", "extract_scan_kernel", "grid_chunk_offsets_kernel", "grid_emit_kernel",
+KERNELS = ("grid_tile_stats_kernel", "grid_tile_reduce_kernel", "grid_tile_code_kernel", "radix_hist_kernel", "radix_scan_kernel",
+           "radix_scatter_kernel", "grid_chunk_sum_kernel", "exclusive_scan_kernel", "grid_chunk_offsets_kernel", "grid_emit_kernel",
            "level_hist_kernel", "level_sum_kernel", "flag_count_kernel", "level_write_kernel")
 SLAB = 64
 
@@ -46,7 +46,7 @@ def grid_scratch_bytes(cells, m):
     voxel, and at most as much again for the leaf parents' keys; the level scan's partials and bins."""
     tiles = (cells + 4095) // 4096
     blocks = (m + 4095) // 4096
-    return tiles * (16 + 24 + 8 + 4) + 16 * m + (blocks + 1) * 8 + (17 * blocks + 17) * 8 + 1025 * 16
+    return tiles * (48 + 24 + 8 + 4) + 16 * m + (blocks + 1) * 8 + (17 * blocks + 17) * 8 + 1025 * 48
 
 
 def palette_of(seed=3):
