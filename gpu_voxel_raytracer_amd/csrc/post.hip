@@ -613,7 +613,9 @@ hipError_t launch_denoise(const DenoiseArgs& args, hipStream_t s) {
     // The fast form's premise: a tap of another material or normal weighs exactly nothing — factor_range >= 1e4 / sigma_range_2 > 100
     // puts the exponent far below vx_exp's -87.3 (and v_exp_f32's -126 in units of log 2).  Holds for every sigma_range < 7.07; the
     // reference's GUI offers 0.1 .. 5 (src/context.rs:1798).  NaN / non-positive sigma_range_2: the generic form, which says what the shader says.
-    const bool fast = (a.mode & 2) == 0 && 1e4f / a.sigma_range_2 > 100.0f && a.sigma_range_2 > 0.0f;
+    // So does a sigma_distance_2 that is NaN or 0 (a sigma_distance of 0, or one whose square underflows): the centre tap's distance
+    // term is then 0 / 0 = NaN, and the fast exact tap hands its argument to vx_exp_in_range, which must not be given a NaN.
+    const bool fast = (a.mode & 2) == 0 && 1e4f / a.sigma_range_2 > 100.0f && a.sigma_range_2 > 0.0f && a.sigma_distance_2 > 0.0f;
     if (fast) {
         dim3 grid((a.band.width + 31) / 32, tile_rows);
         const size_t lds = size_t(32 + 2 * r) * size_t(16 + 2 * r) * 20;

@@ -210,9 +210,14 @@ typedef struct vxrt_stats {
  *   VXRT_OPT_DENOISE_MODE  0 (default): denoise.comp evaluated exactly as the oracle restates it (bit-identical).
  *                          1: tolerant — the per-tap weight exp(-(..)/sigma_range_2 - (..)/sigma_distance_2) (denoise.comp:64-80)
  *                             with a reciprocal multiply and the hardware's exp2; within BASELINE's RMSE <= 1e-3 of mode 0
- *                             (tests/test_gpu_pipeline.py, test_gpu_denoise.py), 1.7 - 2.6 x as fast.
+ *                             (tests/test_gpu_pipeline.py, test_gpu_denoise.py), 1.7 - 2.6 x as fast.  The same pixels are NaN,
+ *                             +inf and -inf (per channel) as in mode 0, and in the fast kernel a pixel whose own colour or
+ *                             log|depth| is not finite, or whose normal is not an axis vector or the sky's 2^30, is made by the
+ *                             exact formula and equals mode 0 bit for bit.
  *                          + 2: the generic kernel (the full formula for every tap) instead of the fast one — a cross-check; the
- *                             library takes it by itself when sigma_range > 7 (the GUI of the reference offers 0.1 .. 5).
+ *                             library takes it by itself when 1e4 / (2 sigma_range^2) > 100 does not hold in binary32 (|sigma_range|
+ *                             above 7.0710673; the GUI of the reference offers 0.1 .. 5), and when sigma_range or sigma_distance is
+ *                             0, NaN or a value whose square underflows to 0.
  *   VXRT_OPT_TAIL_CAPACITY records per shard of the compacted tail's path queue (test hook: a small value forces the
  *                          queue-full path); 0 = back to automatic sizing.
  *   VXRT_OPT_SCENE_FORMAT  which scene records tracers 1 and 4 walk: 0 (default) the 8-byte records, one tree level each; 1 the wide

@@ -20,6 +20,17 @@ NOISE_LEN = 512 * 128 * 128
 NOISE_SEED = 0x5EED0001
 
 
+def default_threads():
+    """Host threads an oracle call uses when it is given none: the CPUs this process may run on (not the machine's count, which
+    can be many times more), and no more than OMP_NUM_THREADS when that is set."""
+    n = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
+    try:
+        omp = int(os.environ.get("OMP_NUM_THREADS", "").split(",")[0])
+    except ValueError:
+        omp = 0
+    return max(1, min(n, omp) if omp > 0 else n)
+
+
 def build(force=False):
     """Compile the oracle with g++ (make).  Building the checker is not using it."""
     subprocess.check_call(["make", "-s", "-C", _HERE] + (["-B"] if force else []))
@@ -253,7 +264,7 @@ def trace(octree, noise, uniforms, width, height, max_bounces=3, crop=None, nthr
     color = np.zeros((h, w, 4), np.float32)
     nd = np.zeros((h, w, 4), np.float32)
     alb = np.zeros((h, w, 4), np.float32)
-    nthreads = nthreads or os.cpu_count() or 1
+    nthreads = nthreads or default_threads()
     rays = lib().orc_trace(_p(octree), _p(noise), C.byref(uniforms), C.c_int(max_bounces), C.c_int(x0), C.c_int(y0),
                            C.c_int(x1), C.c_int(y1), _p(color), _p(nd), _p(alb), C.c_int(nthreads))
     return color, nd, alb, int(rays)
@@ -270,7 +281,7 @@ def trace_menger(level, clip, mrgb, emissive_period, noise, uniforms, max_bounce
     color = np.zeros((h, w, 4), np.float32)
     nd = np.zeros((h, w, 4), np.float32)
     alb = np.zeros((h, w, 4), np.float32)
-    nthreads = nthreads or min(os.cpu_count() or 1, 32)
+    nthreads = nthreads or min(default_threads(), 32)
     rays = lib().orc_trace_menger(*_menger_args(level, clip, mrgb, emissive_period), _p(noise), C.byref(uniforms), C.c_int(max_bounces),
                                   C.c_int(x0), C.c_int(y0), C.c_int(x1), C.c_int(y1), _p(color), _p(nd), _p(alb), C.c_int(nthreads))
     return color, nd, alb, int(rays)
@@ -285,7 +296,7 @@ def cast_rays_menger(level, clip, mrgb, emissive_period, origins, dirs, max_dist
     node = np.zeros(n, np.int32)
     normal = np.zeros((n, 3), np.float32)
     iters = np.zeros(n, np.int32)
-    nthreads = nthreads or min(os.cpu_count() or 1, 32)
+    nthreads = nthreads or min(default_threads(), 32)
     lib().orc_cast_rays_menger(*_menger_args(level, clip, mrgb, emissive_period), _p(origins), _p(dirs), C.c_size_t(n),
                                C.c_float(max_distance), _p(hit), _p(time), _p(node), _p(normal), _p(iters), C.c_int(nthreads))
     return hit.astype(bool), time, node, normal, iters
@@ -300,7 +311,7 @@ def dda_menger(level, clip, origins, dirs, nthreads=None):
     time = np.zeros(n, np.float64)
     axis = np.zeros(n, np.int32)
     cell = np.zeros((n, 3), np.int32)
-    nthreads = nthreads or os.cpu_count() or 1
+    nthreads = nthreads or default_threads()
     lib().orc_dda_menger(C.c_uint32(level), C.c_uint32(clip), _p(origins), _p(dirs), C.c_size_t(n), _p(hit), _p(time), _p(axis),
                          _p(cell), C.c_int(nthreads))
     return hit.astype(bool), time, axis, cell
@@ -347,7 +358,7 @@ def cast_rays(octree, origins, dirs, max_distance=float(1 << 30)):
 def temporal(sampled_color, new_nd, old_color, old_nd, cam16, old_cam16, tu, has_history, nthreads=None):
     h, w = sampled_color.shape[:2]
     out = np.zeros((h, w, 4), np.float32)
-    nthreads = nthreads or os.cpu_count() or 1
+    nthreads = nthreads or default_threads()
     args = [np.ascontiguousarray(a, np.float32) for a in (sampled_color, new_nd, old_color, old_nd, cam16, old_cam16)]
     lib().orc_temporal(*[_p(a) for a in args], C.byref(tu), C.c_int(int(has_history)), C.c_int(w), C.c_int(h),
                        _p(out), C.c_int(nthreads))
@@ -357,7 +368,7 @@ def temporal(sampled_color, new_nd, old_color, old_nd, cam16, old_cam16, tu, has
 def denoise(colors, normals_depths, albedo, cam16, du, nthreads=None):
     h, w = colors.shape[:2]
     out = np.zeros((h, w, 4), np.float32)
-    nthreads = nthreads or os.cpu_count() or 1
+    nthreads = nthreads or default_threads()
     args = [np.ascontiguousarray(a, np.float32) for a in (colors, normals_depths, albedo, cam16)]
     lib().orc_denoise(*[_p(a) for a in args], C.byref(du), C.c_int(w), C.c_int(h), _p(out), C.c_int(nthreads))
     return out
@@ -408,7 +419,7 @@ class CpuRsBackend:
         pixels = np.zeros((height, width, 3), np.uint8)
         pos = np.asarray(cam_pos, np.float32)
         b9 = np.asarray(basis9, np.float32)
-        nthreads = nthreads or os.cpu_count() or 1
+        nthreads = nthreads or default_threads()
         lib().orc_cpu_rs_render_frame(self._h, _p(pos), _p(b9), C.c_int(width), C.c_int(height), C.c_float(time), _p(pixels),
                                       None, None, None, C.c_int(nthreads))
         return pixels
@@ -489,7 +500,7 @@ def spirv_dispatch(module_bytes, bindings, x0, y0, x1, y1, flags=0, nthreads=Non
     L.orc_spirv_error.restype = C.c_char_p
     n = C.c_uint64(0)
     rc = L.orc_spirv_dispatch(_p(words), C.c_size_t(len(words)), arr, C.c_int(len(bindings)), C.c_uint32(x0), C.c_uint32(y0), C.c_uint32(x1),
-                              C.c_uint32(y1), C.c_uint32(flags), C.c_int(nthreads or os.cpu_count() or 1), C.byref(n))
+                              C.c_uint32(y1), C.c_uint32(flags), C.c_int(nthreads or default_threads()), C.byref(n))
     if rc != 0:
         raise SpirvError(L.orc_spirv_error().decode())
     return n.value
