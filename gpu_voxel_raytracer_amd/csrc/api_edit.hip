@@ -58,8 +58,6 @@ size_t grown_capacity(size_t cap, size_t need) { return std::max(need, cap + cap
 
 }  // namespace
 
-namespace {
-
 // the storage for `svo_need` records and `leaf_need` leaf words: fresh arrays (*new_svo / *new_leaves, at the capacities *svo_grow /
 // *leaf_grow) where the current ones are too small, nullptr where they are not.  Nothing changes in the context; nothing is left
 // allocated on failure.
@@ -85,8 +83,6 @@ void commit_storage(vxrt_ctx* c, SvoRecord* new_svo, int32_t* new_leaves, size_t
     if (new_svo) { (void)hipFree(c->d_svo); c->d_svo = new_svo; c->svo_cap = svo_grow; }
     if (new_leaves) { (void)hipFree(c->d_leaves); c->d_leaves = new_leaves; c->leaf_cap = leaf_grow; }
 }
-
-}  // namespace
 
 int reserve_edit_storage(vxrt_ctx* c, size_t nodes, size_t parents) {
     SvoRecord* new_svo;

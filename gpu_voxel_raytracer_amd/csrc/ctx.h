@@ -10,6 +10,7 @@
 //   api_edit.hip     in-place scene edits and the pick query (vxrt_edit.h)
 //   api_extract.hip  the scene's voxels read back from the device, whole or by box (vxrt_extract.h)
 //   api_device_scene.hip  a scene built on the device from a voxel list in device memory (vxrt_device_scene.h)
+//   api_scene_depth.hip   the octree depth of a loaded scene changed in place (vxrt_scene_depth.h)
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -49,6 +49,14 @@ struct EditBatch {
     uint32_t* out = nullptr;
 };
 
+// The storage for `svo_need` records and `leaf_need` leaf words: fresh arrays (*new_svo / *new_leaves, at the capacities *svo_grow /
+// *leaf_grow, holding the arrays in use and zeros after them) where the current ones are too small (x 1.5), nullptr where they are not.
+// Nothing changes in the context; nothing is left allocated on failure.  VXRT_E_SCENE: 2^32 records or leaf words.
+int grow_storage(vxrt_ctx* c, size_t svo_need, size_t leaf_need, SvoRecord** new_svo, int32_t** new_leaves, size_t* svo_grow,
+                 size_t* leaf_grow);
+// ... and the grown storage replaces the old
+void commit_storage(vxrt_ctx* c, SvoRecord* new_svo, int32_t* new_leaves, size_t svo_grow, size_t leaf_grow);
+
 // Room for a set batch with `nodes` segments on node levels 0 .. depth - 1 and `parents` leaf parents: the storage grows
 // (geometrically) when it has to.  VXRT_E_SCENE: 2^32 records or leaf words; VXRT_E_DEVICE: the storage could not grow (nothing
 // changed).  Call after sync_all.
@@ -58,5 +66,20 @@ int reserve_edit_storage(vxrt_ctx* c, size_t nodes, size_t parents);
 // counters, the touch maps and the sky cull's box.  Drains the frames in flight first; waits for the edit.  All or nothing.
 int apply_edit_batch(vxrt_ctx* c, const EditBatch& b);
 hipError_t launch_pick(const TraceArgs& a, const float* origins, const float* dirs, vxrt_pick_hit* out, unsigned n, hipStream_t s);
+
+// vxrt_scene_depth.h (scene_depth.hip; api_scene_depth.hip): one wave each, lane o < 8 takes octant o of the root (record `root`,
+// d_svo[0], at depth `depth`, child mask non-zero).
+//   probe   out[0] = the levels the scene can lose: the least, over the root's children o, of the levels 1, 2, ... whose node on o's
+//           path has slot o ^ 7 only; out[1] = 1 when the scene is the one voxel (-2^t, -2^t, -2^t) of depth t = depth - out[0]
+//   grow    `levels` levels on top: the root keeps its mask and gets an 8-entry block at svo_end; its child o becomes a chain of
+//           `levels` nodes with slot o ^ 7 only, each with an 8-entry block of its own (records from svo_end + 8, chain by chain,
+//           in octant order; with depth 0 the chain's last block is 8 leaf words from leaf_end), the last holding the old child o
+//   shrink  `levels` levels off the top (the probe allowed it): slot o of the root's block takes the record `levels` levels below it
+//           on o's path; with levels == depth the root becomes a leaf parent of an 8-entry leaf block at leaf_end
+hipError_t launch_depth_probe(const SvoRecord* svo, SvoRecord root, uint32_t depth, uint32_t* out, hipStream_t s);
+hipError_t launch_depth_grow(SvoRecord* svo, int32_t* leaves, SvoRecord root, uint32_t depth, uint32_t levels, uint32_t svo_end,
+                             uint32_t leaf_end, hipStream_t s);
+hipError_t launch_depth_shrink(SvoRecord* svo, int32_t* leaves, SvoRecord root, uint32_t depth, uint32_t levels, uint32_t leaf_end,
+                               hipStream_t s);
 
 }  // namespace vxrt

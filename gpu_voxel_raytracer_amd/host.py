@@ -307,6 +307,29 @@ def build_records(pos, mrgb):
     return svo, wide, leaves, int(depth.value)
 
 
+def _ceil_log2(v):
+    """u16::next_power_of_two().trailing_zeros() (0 for 0 and 1)."""
+    return (int(v) - 1).bit_length() if v > 1 else 0
+
+
+def scene_depth_for(pos):
+    """The octree depth vxrt_set_voxels gives a voxel list (build_octree's rule, src/context.rs:813-834): the least d whose root cube
+    [-2^d, 2^d)^3 holds every position, except that the list of the one voxel (-2^k, -2^k, -2^k) gets k + 1 (the rule takes |max| + 1
+    of the greatest coordinate).  An empty list gets 0; 16 (the voxel (-32768)^3 alone) is refused by every build."""
+    pos = np.asarray(pos, np.int64).reshape(-1, 3)
+    if len(pos) == 0:
+        return 0
+    lo, hi = int(pos.min()), int(pos.max())
+    return max(_ceil_log2(abs(lo) & 0xFFFF), _ceil_log2((abs(hi) + 1) & 0xFFFF))
+
+
+def cube_depth(lo, hi):
+    """The least depth whose root cube [-2^d, 2^d)^3 holds the box of positions [lo, hi] (per axis, inclusive): what
+    Context.edit_voxels(grow=True) grows to."""
+    lo, hi = np.asarray(lo, np.int64).reshape(-1), np.asarray(hi, np.int64).reshape(-1)
+    return max([_ceil_log2(-int(v)) for v in lo] + [_ceil_log2(int(v) + 1) for v in hi])
+
+
 def halo_rows_for_motion(cam_a, cam_b, width, height, near, band_rows):
     """vxrt_halo_rows_for_motion: cam_a / cam_b are Camera objects with the same fov (see distributed.halo_rows_for_motion)."""
     rows = C.c_uint32(0)
@@ -571,14 +594,31 @@ class Context:
         org = (C.c_int32 * 3)(*(int(v) for v in origin))
         return cells, fmt, pal, dims, org, mode
 
-    def edit_voxel_grid(self, cells, origin=(0, 0, 0), palette=None, mode="replace"):
+    def edit_voxel_grid(self, cells, origin=(0, 0, 0), palette=None, mode="replace", grow=False):
         """vxrt_edit_voxel_grid (include/vxrt_grid_edit.h): write the grid into the box origin + [0, cells.shape) of the scene in place,
         on the device.  cells and palette as set_voxel_grid; mode "replace" (every cell of the box becomes the grid's), "set" (occupied
         cells are set) or "clear" (occupied cells are cleared), or a GRID_EDIT_* value.  Exactly clear_voxels(clears) then
         edit_voxels(sets) of the cells that change; the temporal history is kept.  The context's stream first waits for torch's
-        current stream.  -> (cells set, cells cleared)."""
+        current stream.  -> (cells set, cells cleared).
+        grow=True: under "set" and "replace" the scene first grows (set_scene_depth, never shrinking) to the least depth whose root
+        cube holds every occupied cell (their bounds are found with torch on the device); occupied cells beyond depth 15's cube raise
+        VxrtError(E_SCENE) before anything changes."""
         import torch
         cells, fmt, pal, dims, org, m = self._grid_args(cells, origin, palette, edit=True, mode=mode)
+        if grow and m in (GRID_EDIT_SET, GRID_EDIT_REPLACE) and cells.numel():
+            occupied = cells != 0 if fmt == GRID_PALETTE8 else cells < 0
+            bounds = []
+            for ax in range(3):
+                hit = torch.nonzero(occupied.any(dim=[d for d in range(3) if d != ax])).flatten()
+                bounds.append((hit.min(), hit.max()) if hit.numel() else None)
+            if bounds[0] is not None:
+                lo = [int(origin[ax]) + int(bounds[ax][0]) for ax in range(3)]
+                hi = [int(origin[ax]) + int(bounds[ax][1]) for ax in range(3)]
+                if min(lo) < -(1 << 15) or max(hi) >= 1 << 15:
+                    raise VxrtError(E_SCENE, "edit_voxel_grid", "an occupied cell lies outside the root cube of depth 15")
+                need = cube_depth(lo, hi)
+                if need > self.scene_depth:
+                    self.set_scene_depth(need)
         counts = (C.c_uint64 * 2)()
         self.context_wait_stream(torch.cuda.current_stream(cells.device).cuda_stream)
         self._chk(self._L.vxrt_edit_voxel_grid(self._h, C.c_void_p(cells.data_ptr() if cells.numel() else None), C.c_int(fmt), dims, org,
@@ -620,20 +660,46 @@ class Context:
                "vxrt_debug_read_scene")
         return svo, leaves
 
-    def edit_voxels(self, pos, mrgb):
+    def edit_voxels(self, pos, mrgb, grow=False):
         """vxrt_edit_voxels: set (insert or overwrite) voxels of the scene in place, on the device; the last entry for a position wins.
         Same positions and words as recreate_octree; the octree depth never changes (positions outside the root cube are refused);
-        the temporal history is kept.  Multi-GPU: apply the same edits on every rank's context (each holds the whole scene)."""
+        the temporal history is kept.  Multi-GPU: apply the same edits on every rank's context (each holds the whole scene).
+        grow=True: the scene first grows (set_scene_depth, never shrinking) to the least depth whose root cube holds the positions;
+        fit_scene_depth() afterwards gives the depth, and so the frames, of a rebuild."""
         pos = np.ascontiguousarray(pos, np.int16).reshape(-1, 3)
         mrgb = np.ascontiguousarray(mrgb, np.uint8).reshape(-1, 4)
         if len(mrgb) != len(pos):
             raise ValueError("one mrgb per position")
+        if grow and len(pos):
+            need = cube_depth(pos.min(axis=0), pos.max(axis=0))
+            if need > self.scene_depth:
+                self.set_scene_depth(need)
         self._chk(self._L.vxrt_edit_voxels(self._h, _p(pos), _p(mrgb), C.c_size_t(len(pos))), "vxrt_edit_voxels")
 
     def clear_voxels(self, pos):
         """vxrt_edit_voxels without words: remove voxels of the scene in place (absent positions are ignored)."""
         pos = np.ascontiguousarray(pos, np.int16).reshape(-1, 3)
         self._chk(self._L.vxrt_edit_voxels(self._h, _p(pos), None, C.c_size_t(len(pos))), "vxrt_edit_voxels")
+
+    def set_scene_depth(self, depth):
+        """vxrt_set_scene_depth (include/vxrt_scene_depth.h): change the octree depth of the scene in place, on the device; the root
+        cube becomes [-2^depth, 2^depth)^3 (0 <= depth <= 15).  Growing always works; shrinking only while every voxel lies in the
+        smaller cube (E_SCENE otherwise).  The voxels, their read-back order and the temporal history stay."""
+        if not 0 <= int(depth) <= 0xFFFFFFFF:
+            raise ValueError("depth must be a uint32")
+        self._chk(self._L.vxrt_set_scene_depth(self._h, C.c_uint32(int(depth))), "vxrt_set_scene_depth")
+
+    def fit_scene_depth(self):
+        """vxrt_fit_scene_depth: give the scene the depth recreate_octree of its voxel list would (scene_depth_for of get_voxels) ->
+        that depth.  Afterwards every frame equals a rebuild's."""
+        d = C.c_uint32(0)
+        self._chk(self._L.vxrt_fit_scene_depth(self._h, C.byref(d)), "vxrt_fit_scene_depth")
+        return int(d.value)
+
+    @property
+    def scene_depth(self):
+        """The scene's octree depth (stats().octree_depth): the root cube is [-2^d, 2^d)^3."""
+        return int(self.stats().octree_depth)
 
     def pick(self, origins, dirs):
         """vxrt_pick: cast rays against the scene as it stands after everything enqueued so far -> dict of numpy arrays

@@ -22,6 +22,7 @@
 #include "vxrt_grid.h"
 #include "vxrt_grid_edit.h"
 #include "vxrt_host.h"
+#include "vxrt_scene_depth.h"
 
 namespace vxrt {
 
@@ -214,6 +215,14 @@ class Context {
         vxrt_grid_edit_counts counts{0, 0};
         check(vxrt_edit_voxel_grid(ctx_, cells, format, dims.data(), origin.data(), palette, mode, &counts), "vxrt_edit_voxel_grid");
         return counts;
+    }
+    // vxrt_scene_depth.h: the scene's octree depth changed in place (root cube [-2^depth, 2^depth)^3; a shrink that would drop a voxel
+    // throws VXRT_E_SCENE), or set to what a rebuild of its voxels would give (returned)
+    void set_scene_depth(uint32_t depth) { check(vxrt_set_scene_depth(ctx_, depth), "vxrt_set_scene_depth"); }
+    uint32_t fit_scene_depth() {
+        uint32_t depth = 0;
+        check(vxrt_fit_scene_depth(ctx_, &depth), "vxrt_fit_scene_depth");
+        return depth;
     }
     void set_menger(uint32_t level, uint32_t clip, std::array<uint8_t, 4> mrgb, uint32_t emissive_period) {
         check(vxrt_set_menger(ctx_, level, clip, mrgb.data(), emissive_period), "vxrt_set_menger");
