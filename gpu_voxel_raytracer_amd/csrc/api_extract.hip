@@ -1,12 +1,15 @@
 // api_extract.hip — host side of vxrt_extract.h: the scene's voxels, whole or by box, decoded on the device (extract.hip).
 // The host runs the levels (extract.h) and reads back one number per level, the size of the next frontier, so that the scratch can
-// grow to it; the output goes to device buffers and comes back in one copy per array.  DESIGN.md "Reading the scene back".
+// grow to it; the output goes to device buffers and comes back in one copy per array (vxrt_get_voxels), or straight into the caller's
+// device arrays (vxrt_get_voxels_device).  DESIGN.md "Reading the scene back", §15.
 #include <algorithm>
+#include <string>
 
 #include "ctx.h"
 #include "device_build.h"
 #include "extract.h"
 #include "scene_args.h"
+#include "../../include/vxrt_device_edit.h"
 #include "../../include/vxrt_extract.h"
 
 namespace vxrt {
@@ -45,12 +48,9 @@ void free_extract(vxrt_ctx* c) {
     x.front_cap[0] = x.front_cap[1] = x.part_cap = x.pos_cap = x.mrgb_cap = 0;
 }
 
-}  // namespace vxrt
-
-extern "C" {
-
-int vxrt_get_voxels(vxrt_ctx* c, const int32_t box_min[3], const int32_t box_max[3], int16_t (*pos)[3], uint8_t (*mrgb)[4], size_t cap,
-                    size_t* n) try {
+// vxrt_get_voxels (device = false: pos / mrgb are host arrays) and vxrt_get_voxels_device (device memory of the context's device)
+static int get_voxels(vxrt_ctx* c, const int32_t box_min[3], const int32_t box_max[3], int16_t (*pos)[3], uint8_t (*mrgb)[4], size_t cap, size_t* n,
+                      bool device, const char* who) {
     if (!valid_ctx(c) || !n) { set_error("null argument"); return VXRT_E_INVALID; }
     if ((box_min == nullptr) != (box_max == nullptr)) { set_error("box_min and box_max: both or neither"); return VXRT_E_INVALID; }
     if ((pos == nullptr) != (mrgb == nullptr)) { set_error("pos and mrgb: both or neither"); return VXRT_E_INVALID; }
@@ -74,9 +74,13 @@ int vxrt_get_voxels(vxrt_ctx* c, const int32_t box_min[3], const int32_t box_max
     a.half = uint32_t(half);
 
     HIP_TRY(hipSetDevice(c->cfg.device));
+    if (device && !count_only && cap != 0) {
+        if (int rc = check_device_array(c, pos, cap * 3 * sizeof(int16_t), who, "pos")) return rc;
+        if (int rc = check_device_array(c, mrgb, cap * 4, who, "mrgb")) return rc;
+    }
     vxrt_ctx::ExtractScratch& x = c->extract;
     // the root: record 0 at cell 0 (the decode runs on the context's stream, behind everything enqueued on it)
-    if (hipError_t e = ensure(&x.front[0], &x.front_cap[0], sizeof(uint4)); e != hipSuccess) return alloc_failed(e, "vxrt_get_voxels", "the frontier");
+    if (hipError_t e = ensure(&x.front[0], &x.front_cap[0], sizeof(uint4)); e != hipSuccess) return alloc_failed(e, who, "the frontier");
     HIP_TRY(hipMemsetAsync(x.front[0], 0, sizeof(uint4), c->stream));
     int cur = 0;
     uint64_t count = 0;
@@ -88,7 +92,7 @@ int vxrt_get_voxels(vxrt_ctx* c, const int32_t box_min[3], const int32_t box_max
         a.n = frontier;
         const uint32_t blocks = extract_blocks(frontier);
         if (hipError_t e = ensure(&x.part, &x.part_cap, (size_t(blocks) + 1) * sizeof(uint64_t)); e != hipSuccess)
-            return alloc_failed(e, "vxrt_get_voxels", "the scan partials");
+            return alloc_failed(e, who, "the scan partials");
         a.part = static_cast<uint64_t*>(x.part);
         HIP_TRY(launch_extract_count(a, c->stream));
         HIP_TRY(launch_exclusive_scan(a.part, blocks, c->stream));
@@ -97,9 +101,9 @@ int vxrt_get_voxels(vxrt_ctx* c, const int32_t box_min[3], const int32_t box_max
         HIP_TRY(hipStreamSynchronize(c->stream));
         if (total == 0) break;
         if (a.leaf) { count = total; break; }
-        if (total >= (uint64_t(1) << 32)) { set_error("vxrt_get_voxels: a tree level of 2^32 nodes or more"); return VXRT_E_INVALID; }
+        if (total >= (uint64_t(1) << 32)) { set_error(std::string(who) + ": a tree level of 2^32 nodes or more"); return VXRT_E_INVALID; }
         if (hipError_t e = ensure(&x.front[cur ^ 1], &x.front_cap[cur ^ 1], size_t(total) * sizeof(uint4)); e != hipSuccess)
-            return alloc_failed(e, "vxrt_get_voxels", "the frontier");
+            return alloc_failed(e, who, "the frontier");
         a.next = static_cast<uint4*>(x.front[cur ^ 1]);
         HIP_TRY(launch_extract_expand(a, c->stream));
         a.next = nullptr;
@@ -109,20 +113,45 @@ int vxrt_get_voxels(vxrt_ctx* c, const int32_t box_min[3], const int32_t box_max
     if (count_only || count == 0) { *n = size_t(count); return VXRT_OK; }
     if (cap < count) {
         *n = size_t(count);
-        set_error("vxrt_get_voxels: " + std::to_string(count) + " voxels, room for " + std::to_string(cap));
+        set_error(std::string(who) + ": " + std::to_string(count) + " voxels, room for " + std::to_string(cap));
         return VXRT_E_INVALID;
     }
-    // the leaf parents' frontier is still in place (a.front, a.n, a.part): write the voxels at their offsets
-    if (hipError_t e = ensure(&x.pos, &x.pos_cap, size_t(count) * 3 * sizeof(int16_t)); e != hipSuccess) return alloc_failed(e, "vxrt_get_voxels", "the positions");
-    if (hipError_t e = ensure(&x.mrgb, &x.mrgb_cap, size_t(count) * 4); e != hipSuccess) return alloc_failed(e, "vxrt_get_voxels", "the leaf words");
-    a.pos = static_cast<int16_t*>(x.pos);
-    a.mrgb = static_cast<uint32_t*>(x.mrgb);
+    // the leaf parents' frontier is still in place (a.front, a.n, a.part): write the voxels at their offsets.  A device destination
+    // is written in place where the kernel's stores fit its alignment (2 bytes per coordinate, 4 per mrgb word); otherwise, and for
+    // the host, the voxels are staged in the context's buffers and copied out.
+    const bool direct = device && (reinterpret_cast<uintptr_t>(pos) & 1u) == 0u && (reinterpret_cast<uintptr_t>(mrgb) & 3u) == 0u;
+    if (direct) {
+        a.pos = reinterpret_cast<int16_t*>(pos);
+        a.mrgb = reinterpret_cast<uint32_t*>(mrgb);
+    } else {
+        if (hipError_t e = ensure(&x.pos, &x.pos_cap, size_t(count) * 3 * sizeof(int16_t)); e != hipSuccess) return alloc_failed(e, who, "the positions");
+        if (hipError_t e = ensure(&x.mrgb, &x.mrgb_cap, size_t(count) * 4); e != hipSuccess) return alloc_failed(e, who, "the leaf words");
+        a.pos = static_cast<int16_t*>(x.pos);
+        a.mrgb = static_cast<uint32_t*>(x.mrgb);
+    }
     HIP_TRY(launch_extract_expand(a, c->stream));
-    HIP_TRY(hipMemcpyAsync(pos, x.pos, size_t(count) * 3 * sizeof(int16_t), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(mrgb, x.mrgb, size_t(count) * 4, hipMemcpyDeviceToHost, c->stream));
+    if (!direct) {
+        const hipMemcpyKind kind = device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+        HIP_TRY(hipMemcpyAsync(pos, x.pos, size_t(count) * 3 * sizeof(int16_t), kind, c->stream));
+        HIP_TRY(hipMemcpyAsync(mrgb, x.mrgb, size_t(count) * 4, kind, c->stream));
+    }
     HIP_TRY(hipStreamSynchronize(c->stream));
     *n = size_t(count);
     return VXRT_OK;
+}
+
+}  // namespace vxrt
+
+extern "C" {
+
+int vxrt_get_voxels(vxrt_ctx* c, const int32_t box_min[3], const int32_t box_max[3], int16_t (*pos)[3], uint8_t (*mrgb)[4], size_t cap,
+                    size_t* n) try {
+    return vxrt::get_voxels(c, box_min, box_max, pos, mrgb, cap, n, false, "vxrt_get_voxels");
+} VXRT_CATCH
+
+int vxrt_get_voxels_device(vxrt_ctx* c, const int32_t box_min[3], const int32_t box_max[3], int16_t (*pos)[3], uint8_t (*mrgb)[4], size_t cap,
+                           size_t* n) try {
+    return vxrt::get_voxels(c, box_min, box_max, pos, mrgb, cap, n, true, "vxrt_get_voxels_device");
 } VXRT_CATCH
 
 }  // extern "C"

@@ -1,6 +1,7 @@
 // device_build.h — what api_device_scene.hip (host side of vxrt_device_scene.h), device_build.hip (the list builder), grid_build.hip
-// (the dense-grid builder), grid_edit.hip (the grid editor) and api_grid.hip (host side of vxrt_grid.h) share, and the device
-// primitives they and api_extract.hip use: lanes_below, the exclusive scan and the radix sort (device_build.hip).
+// (the dense-grid builder), grid_edit.hip (the grid editor), api_grid.hip (host side of vxrt_grid.h) and api_device_edit.hip /
+// device_edit.hip (vxrt_device_edit.h) share, and the device primitives they and api_extract.hip use: the path key and leaf word,
+// lanes_below, the exclusive scan, the radix sort and the sort-and-dedupe front of a list (device_build.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -36,14 +37,40 @@ __device__ __forceinline__ uint32_t lanes_below(uint64_t m) {
     return __builtin_amdgcn_mbcnt_hi(uint32_t(m >> 32), __builtin_amdgcn_mbcnt_lo(uint32_t(m), 0u));
 }
 
+// A voxel's path key at depth d, u = p + 2^d per axis: bit k of u lands at bits 3k + 2 (x), 3k + 1 (y), 3k (z), k = 0 .. d — the key
+// vxrt_edit_voxels sorts by (api_edit.hip: path_key) and the order of the records (vxrt_extract.h).
+__device__ __forceinline__ uint64_t path_key_of(uint32_t ux, uint32_t uy, uint32_t uz, uint32_t depth) {
+    uint64_t key = 0;
+    for (uint32_t k = 0; k <= depth; k++)
+        key |= uint64_t(((ux >> k) & 1u) << 2 | ((uy >> k) & 1u) << 1 | ((uz >> k) & 1u)) << (3u * k);
+    return key;
+}
+
+// scene_host.cpp: build_octree's leaf word of (material, r, g, b)
+__device__ __forceinline__ uint32_t leaf_word_of(uint32_t m, uint32_t r, uint32_t g, uint32_t b) {
+    return 0x80000000u | (m & 0x7fu) << 24 | r << 16 | g << 8 | b;
+}
+
 // One workgroup: part[0 .. blocks) -> its exclusive prefix sums in place, part[blocks] = the total.
 hipError_t launch_exclusive_scan(uint64_t* part, uint32_t blocks, hipStream_t stream);
 
 // Stable LSD radix sort of (keys, vals), n entries, over the low `bits` key bits, 8 per pass, ping-ponging between keys[0] / vals[0]
-// and keys[1] / vals[1] starting at [*cur]; the result is in [*cur] on return.  hist: radix_hist_entries(n) words; totals: 256 words.
+// and keys[1] / vals[1] starting at [*cur]; the result is in [*cur] on return.  vals[0] == nullptr: keys only.  hist: radix_hist_entries(n) words; totals: 256 words.
 size_t radix_hist_entries(size_t n);
 hipError_t radix_sort_pairs(uint64_t* keys[2], uint32_t* vals[2], uint32_t n, uint32_t bits, uint32_t* hist, uint32_t* totals,
                             hipStream_t stream, int* cur);
+
+// The front half the list builder and vxrt_edit_voxels_device share, behind their own key pass: the scratch of a list of n entries
+// (keys and, with_vals, leaf words, double-buffered; the digit counts; the scan partials: about 24 bytes per entry), then the stable
+// sort of keys[0] / vals[0] over the 3(depth + 1) key bits and the keep-last dedupe.  On return the m unique keys are ascending in
+// keys[*cur], keys[*cur ^ 1] is free, and with values *leaves holds their m leaf words (exactly sized); a list without values (vals
+// not allocated) leaves *leaves alone.  Waits for the count.  VXRT_E_DEVICE: an allocation failed.
+struct ListScratch {
+    ScratchBuffer keys[2], vals[2], hist, totals, part;
+};
+int alloc_list_scratch(size_t n, bool with_vals, const char* who, ListScratch* ls);
+int sort_unique_list(ListScratch* ls, uint32_t n, uint32_t depth, ScratchBuffer* leaves, hipStream_t stream, const char* who, size_t* m,
+                     int* cur);
 
 // The back half of both builders: the node levels over m > 0 unique path keys in ascending order (ukeys, m < 2^32) and their leaf
 // words (*leaves, exactly m int32, handed to *out on success) -> the records, one exact allocation.  ukeys is overwritten; spare

@@ -15,6 +15,7 @@
 //                 scan (one workgroup per digit over the blocks), scatter (rank in the block by wave ballots + LDS, stage the block
 //                 sorted in LDS, write runs of one digit contiguously)
 //   dedupe        the last entry of every run of equal keys, compacted by a scan: its leaf word is d_leaves, its key the unique list
+//                 (radix sort and dedupe are sort_unique_list, which vxrt_edit_voxels_device runs at a loaded scene's depth)
 //   level counts  per unique key, the number of levels at which it opens a node (from the highest bit in which it differs from
 //                 its predecessor) -> every level's node count -> the exact record count, one allocation
 //   levels        bottom-up, per level: count / scan / write the runs of key >> 3 of the level below (each run at most 8 long):
@@ -109,9 +110,6 @@ __global__ __launch_bounds__(kThreads) void keys_kernel(const int16_t* pos, cons
     if (i >= n) return;
     const int half = 1 << depth;
     const uint32_t ux = uint32_t(int(pos[3 * i + 0]) + half), uy = uint32_t(int(pos[3 * i + 1]) + half), uz = uint32_t(int(pos[3 * i + 2]) + half);
-    uint64_t key = 0;
-    for (uint32_t k = 0; k <= depth; k++)
-        key |= uint64_t(((ux >> k) & 1u) << 2 | ((uy >> k) & 1u) << 1 | ((uz >> k) & 1u)) << (3u * k);
     uint32_t m, r, g, b;
     if (words) {
         const uint32_t w = reinterpret_cast<const uint32_t*>(mrgb)[i];
@@ -119,8 +117,8 @@ __global__ __launch_bounds__(kThreads) void keys_kernel(const int16_t* pos, cons
     } else {
         m = mrgb[4 * i + 0]; r = mrgb[4 * i + 1]; g = mrgb[4 * i + 2]; b = mrgb[4 * i + 3];
     }
-    keys[i] = key;
-    vals[i] = 0x80000000u | (m & 0x7fu) << 24 | r << 16 | g << 8 | b;   // scene_host.cpp: build_octree's leaf word
+    keys[i] = path_key_of(ux, uy, uz, depth);
+    vals[i] = leaf_word_of(m, r, g, b);
 }
 
 // ---- radix sort ----------------------------------------------------------------------------------------------------------------
@@ -160,11 +158,13 @@ __global__ __launch_bounds__(kRowThreads) void radix_scan_kernel(uint32_t* hist,
 
 // Stable: the tile's entries are ranked in input order (round j, then wave, then lane), staged digit-sorted in LDS and written out
 // so that each digit's entries of the tile form one contiguous run at hist's offset.
+// kVals: the keys carry values (a clear list of vxrt_edit_voxels_device has none: vals_in / vals_out are null and never touched).
+template <bool kVals>
 __global__ __launch_bounds__(kThreads) void radix_scatter_kernel(const uint64_t* keys_in, const uint32_t* vals_in, uint64_t* keys_out,
                                                                  uint32_t* vals_out, uint32_t n, uint32_t shift, uint32_t blocks,
                                                                  const uint32_t* hist, const uint32_t* totals) {
     __shared__ uint64_t s_key[kTile];
-    __shared__ uint32_t s_val[kTile];
+    __shared__ uint32_t s_val[kVals ? kTile : 1];
     __shared__ uint32_t s_wave[2][kWaves][kDigits];   // per round (double-buffered): entries of a digit per wave -> their offsets
     __shared__ uint32_t s_start[kDigits];             // a digit's first entry in the staged tile
     __shared__ uint32_t s_dst[kDigits];               // ... and in the output
@@ -172,7 +172,7 @@ __global__ __launch_bounds__(kThreads) void radix_scatter_kernel(const uint64_t*
     const uint32_t t = threadIdx.x, wave = t >> 6;
     const size_t base = size_t(blockIdx.x) * kTile;
     uint64_t key[kItems];
-    uint32_t val[kItems], rank[kItems];
+    uint32_t val[kVals ? kItems : 1], rank[kItems];
 #pragma unroll
     for (uint32_t w = 0; w < kWaves; w++) s_wave[0][w][t] = 0u;
     __syncthreads();
@@ -183,7 +183,7 @@ __global__ __launch_bounds__(kThreads) void radix_scatter_kernel(const uint64_t*
         const size_t i = base + j * kThreads + t;
         const bool ok = i < n;
         key[j] = ok ? keys_in[i] : 0ull;
-        val[j] = ok ? vals_in[i] : 0u;
+        if (kVals) val[j] = ok ? vals_in[i] : 0u;
         const uint32_t d = uint32_t(key[j] >> shift) & 0xffu;
         const uint64_t peers = digit_peers(d, ok);
         const uint32_t below = lanes_below(peers);
@@ -209,7 +209,7 @@ __global__ __launch_bounds__(kThreads) void radix_scatter_kernel(const uint64_t*
         if (base + j * kThreads + t < n) {
             const uint32_t p = s_start[uint32_t(key[j] >> shift) & 0xffu] + rank[j];
             s_key[p] = key[j];
-            s_val[p] = val[j];
+            if (kVals) s_val[p] = val[j];
         }
     }
     __syncthreads();
@@ -219,7 +219,7 @@ __global__ __launch_bounds__(kThreads) void radix_scatter_kernel(const uint64_t*
         const uint32_t d = uint32_t(k >> shift) & 0xffu;
         const uint32_t dst = s_dst[d] + (p - s_start[d]);
         keys_out[dst] = k;
-        vals_out[dst] = s_val[p];
+        if (kVals) vals_out[dst] = s_val[p];
     }
 }
 
@@ -263,7 +263,7 @@ __global__ __launch_bounds__(kThreads) void dedupe_write_kernel(const uint64_t* 
         at += total;
         if (keep) {
             ukeys[o] = keys[i];
-            leaves[o] = int32_t(vals[i]);
+            if (vals) leaves[o] = int32_t(vals[i]);   // uniform: a clear list has no values
         }
     }
 }
@@ -385,8 +385,12 @@ hipError_t radix_sort_pairs(uint64_t* keys[2], uint32_t* vals[2], uint32_t n, ui
         if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
         hipLaunchKernelGGL(radix_scan_kernel, dim3(kDigits), dim3(kRowThreads), 0, s, hist, blocks, totals);
         if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
-        hipLaunchKernelGGL(radix_scatter_kernel, dim3(blocks), dim3(kThreads), 0, s, keys[c], vals[c], keys[c ^ 1], vals[c ^ 1], n, shift,
-                           blocks, hist, totals);
+        if (vals[0] != nullptr)
+            hipLaunchKernelGGL(radix_scatter_kernel<true>, dim3(blocks), dim3(kThreads), 0, s, keys[c], vals[c], keys[c ^ 1], vals[c ^ 1], n,
+                               shift, blocks, hist, totals);
+        else
+            hipLaunchKernelGGL(radix_scatter_kernel<false>, dim3(blocks), dim3(kThreads), 0, s, keys[c], nullptr, keys[c ^ 1], nullptr, n,
+                               shift, blocks, hist, totals);
         if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
         *cur = c ^ 1;
     }
@@ -469,6 +473,46 @@ int build_empty_tree(hipStream_t s, const char* who, DeviceTree* out) {
     return VXRT_OK;
 }
 
+int alloc_list_scratch(size_t n, bool with_vals, const char* who, ListScratch* ls) {
+    const uint32_t blocks = tiles(n);
+    for (int b = 0; b < 2; b++) {
+        if (int rc = alloc_scratch(&ls->keys[b], n * sizeof(uint64_t), who, "the keys")) return rc;
+        if (with_vals)
+            if (int rc = alloc_scratch(&ls->vals[b], n * sizeof(uint32_t), who, "the leaf words")) return rc;
+    }
+    if (int rc = alloc_scratch(&ls->hist, size_t(kDigits) * blocks * sizeof(uint32_t), who, "the digit counts")) return rc;
+    if (int rc = alloc_scratch(&ls->totals, kDigits * sizeof(uint32_t), who, "the digit counts")) return rc;
+    return alloc_scratch(&ls->part, (size_t(blocks) + 1) * sizeof(uint64_t), who, "the scan partials");
+}
+
+int sort_unique_list(ListScratch* ls, uint32_t n, uint32_t depth, ScratchBuffer* leaves, hipStream_t s, const char* who, size_t* m_out,
+                     int* cur_out) {
+    const uint32_t blocks = tiles(n);
+    const bool with_vals = ls->vals[0].p != nullptr;
+    // stable LSD radix sort over the key's 3(depth + 1) bits
+    uint64_t* kp[2] = {ls->keys[0].as<uint64_t>(), ls->keys[1].as<uint64_t>()};
+    uint32_t* vp[2] = {ls->vals[0].as<uint32_t>(), ls->vals[1].as<uint32_t>()};
+    int cur = 0;
+    HIP_TRY(radix_sort_pairs(kp, vp, n, 3u * (depth + 1u), ls->hist.as<uint32_t>(), ls->totals.as<uint32_t>(), s, &cur));
+
+    // dedupe: the last entry of each key -> the leaf words (exactly sized) and the unique keys (keys[cur ^ 1])
+    uint64_t* part = ls->part.as<uint64_t>();
+    hipLaunchKernelGGL(flag_count_kernel<true>, dim3(blocks), dim3(kThreads), 0, s, kp[cur], n, part);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(launch_exclusive_scan(part, blocks, s));
+    uint64_t m = 0;
+    HIP_TRY(hipMemcpyAsync(&m, part + blocks, sizeof m, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (with_vals)
+        if (int rc = alloc_scratch(leaves, size_t(m) * sizeof(int32_t), who, "the leaf words")) return rc;
+    hipLaunchKernelGGL(dedupe_write_kernel, dim3(blocks), dim3(kThreads), 0, s, kp[cur], with_vals ? vp[cur] : nullptr, n, part, kp[cur ^ 1],
+                       with_vals ? leaves->as<int32_t>() : nullptr);
+    HIP_TRY(hipGetLastError());
+    *m_out = size_t(m);
+    *cur_out = cur ^ 1;
+    return VXRT_OK;
+}
+
 int build_svo_device_list(const int16_t* pos, const uint8_t* mrgb, size_t n, hipStream_t s, DeviceTree* out) {
     *out = DeviceTree{};
     const char* who = "vxrt_set_voxels_device";
@@ -492,41 +536,20 @@ int build_svo_device_list(const int16_t* pos, const uint8_t* mrgb, size_t n, hip
 
     // scratch: keys and leaf words double-buffered, the digit counts, the scan partials, the level bins
     const uint32_t blocks = tiles(n);
-    ScratchBuffer keys[2], vals[2], hist, totals, part, bins;
-    for (int b = 0; b < 2; b++) {
-        if (int rc = alloc_scratch(&keys[b], n * sizeof(uint64_t), who, "the keys")) return rc;
-        if (int rc = alloc_scratch(&vals[b], n * sizeof(uint32_t), who, "the leaf words")) return rc;
-    }
-    if (int rc = alloc_scratch(&hist, size_t(kDigits) * blocks * sizeof(uint32_t), who, "the digit counts")) return rc;
-    if (int rc = alloc_scratch(&totals, kDigits * sizeof(uint32_t), who, "the digit counts")) return rc;
-    if (int rc = alloc_scratch(&part, (size_t(blocks) + 1) * sizeof(uint64_t), who, "the scan partials")) return rc;
+    ListScratch ls;
+    ScratchBuffer bins;
+    if (int rc = alloc_list_scratch(n, true, who, &ls)) return rc;
     if (int rc = alloc_scratch(&bins, (size_t(kLevelBins) * blocks + kLevelBins) * sizeof(uint64_t), who, "the level counts")) return rc;
 
     const uint32_t words = (reinterpret_cast<uintptr_t>(mrgb) & 3u) == 0u ? 1u : 0u;
     hipLaunchKernelGGL(keys_kernel, dim3(uint32_t((n + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, pos, mrgb, n, depth, words,
-                       keys[0].as<uint64_t>(), vals[0].as<uint32_t>());
+                       ls.keys[0].as<uint64_t>(), ls.vals[0].as<uint32_t>());
     HIP_TRY(hipGetLastError());
 
-    // stable LSD radix sort over the key's 3(depth + 1) bits
-    uint64_t* kp[2] = {keys[0].as<uint64_t>(), keys[1].as<uint64_t>()};
-    uint32_t* vp[2] = {vals[0].as<uint32_t>(), vals[1].as<uint32_t>()};
+    size_t m = 0;
     int cur = 0;
-    HIP_TRY(radix_sort_pairs(kp, vp, nn, 3u * (depth + 1u), hist.as<uint32_t>(), totals.as<uint32_t>(), s, &cur));
-
-    // dedupe: the last entry of each key -> the leaf words (exactly sized) and the unique keys (keys[cur ^ 1])
-    hipLaunchKernelGGL(flag_count_kernel<true>, dim3(blocks), dim3(kThreads), 0, s, keys[cur].as<uint64_t>(), nn, part.as<uint64_t>());
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(launch_exclusive_scan(part.as<uint64_t>(), blocks, s));
-    uint64_t m = 0;
-    HIP_TRY(hipMemcpyAsync(&m, part.as<uint64_t>() + blocks, sizeof m, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    if (int rc = alloc_scratch(&leaves, size_t(m) * sizeof(int32_t), who, "the leaf words")) return rc;
-    hipLaunchKernelGGL(dedupe_write_kernel, dim3(blocks), dim3(kThreads), 0, s, keys[cur].as<uint64_t>(), vals[cur].as<uint32_t>(), nn,
-                       part.as<uint64_t>(), keys[cur ^ 1].as<uint64_t>(), leaves.as<int32_t>());
-    HIP_TRY(hipGetLastError());
-    cur ^= 1;
-
-    return build_levels(keys[cur].as<uint64_t>(), keys[cur ^ 1].as<uint64_t>(), size_t(m), part.as<uint64_t>(), bins.as<uint64_t>(), depth,
+    if (int rc = sort_unique_list(&ls, nn, depth, &leaves, s, who, &m, &cur)) return rc;
+    return build_levels(ls.keys[cur].as<uint64_t>(), ls.keys[cur ^ 1].as<uint64_t>(), m, ls.part.as<uint64_t>(), bins.as<uint64_t>(), depth,
                         &leaves, s, who, out);
 }
 

@@ -1,4 +1,5 @@
-// edit.h — what api_edit.hip (host side of vxrt_edit.h) and edit.hip (its kernels) share.
+// edit.h — what api_edit.hip (host side of vxrt_edit.h) and edit.hip (its kernels) share, and what the device-side editors
+// (grid_edit.hip, api_device_edit.hip / device_edit.hip) add in front of the same tail.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -8,6 +9,8 @@
 #include "kernels.h"
 
 namespace vxrt {
+
+struct ScratchBuffer;   // ctx.h
 
 // A batch as edit_kernel walks it: the entries, sorted by octree path and one per position, cut into "segments" per tree level —
 // segment = one node on the path of at least one entry.  Node levels run 0 (the root: one segment) .. depth (the leaf parents);
@@ -34,7 +37,8 @@ hipError_t launch_edit(const EditArgs& a, hipStream_t s);
 
 // A batch cut into segments, as the tail of an edit takes it (api_edit.hip: apply_edit_batch).  vxrt_edit_voxels cuts on the host
 // and hands the arrays over in `host` (child_begin | words | oct, uploaded in one copy); vxrt_edit_voxel_grid cuts on the device
-// and gives the device arrays and the kernel's scratch (node, flag: seg_off[depth + 1] entries each; out: 8 words) itself.
+// and gives the device arrays and the kernel's scratch (node, flag: seg_off[depth + 1] entries each; out: 8 words) itself, and so
+// does vxrt_edit_voxels_device (cut_edit_lists below).
 struct EditBatch {
     uint32_t seg_off[18];                       // as EditArgs, levels 0 .. depth + 1 and the end
     bool clear = false;
@@ -49,6 +53,23 @@ struct EditBatch {
     uint32_t* out = nullptr;
 };
 
+// The cut, on the device (grid_edit.hip), of `count` (1 or 2) lists of path keys at depth L, each ascending and unique (m[b] < 2^32
+// entries, none when 0), into edit_kernel's segments.  For every non-empty list, *out[b] gets seg_off, child_begin, oct and the
+// kernel's scratch (node, flag, out: one set, shared by the lists, which are applied one after the other); clear, words, lo and hi
+// stay the caller's to fill.  Every device array lives in *batch.  Runs on `stream` and waits.  VXRT_E_DEVICE: an allocation failed.
+int cut_edit_lists(const uint64_t* const* keys, const uint32_t* m, int count, uint32_t L, hipStream_t stream, const char* who,
+                   ScratchBuffer* batch, EditBatch* const* out);
+
+// One pass over a device voxel list at the scene's depth (device_edit.hip): keys[i] = entry i's path key, vals[i] = its leaf word
+// (mrgb and vals null: a clear), and the list's least and greatest position per axis and whether any lies outside the root cube
+// [-2^depth, 2^depth)^3, reduced on the device and read back once.  n > 0.  Waits.  VXRT_E_DEVICE: an allocation failed.
+struct ListBounds {
+    int32_t lo[3], hi[3];
+    uint32_t outside, pad;
+};
+int edit_keys_device(const int16_t* pos, const uint8_t* mrgb, size_t n, uint32_t depth, uint64_t* keys, uint32_t* vals, hipStream_t stream,
+                     const char* who, ListBounds* out);
+
 // The storage for `svo_need` records and `leaf_need` leaf words: fresh arrays (*new_svo / *new_leaves, at the capacities *svo_grow /
 // *leaf_grow, holding the arrays in use and zeros after them) where the current ones are too small (x 1.5), nullptr where they are not.
 // Nothing changes in the context; nothing is left allocated on failure.  VXRT_E_SCENE: 2^32 records or leaf words.
@@ -62,7 +83,7 @@ void commit_storage(vxrt_ctx* c, SvoRecord* new_svo, int32_t* new_leaves, size_t
 // changed).  Call after sync_all.
 int reserve_edit_storage(vxrt_ctx* c, size_t nodes, size_t parents);
 
-// The tail of an edit, shared by vxrt_edit_voxels and vxrt_edit_voxel_grid: storage growth, the `edited` bookkeeping, the launch, the
+// The tail of an edit, shared by vxrt_edit_voxels, vxrt_edit_voxel_grid and vxrt_edit_voxels_device: storage growth, the `edited` bookkeeping, the launch, the
 // counters, the touch maps and the sky cull's box.  Drains the frames in flight first; waits for the edit.  All or nothing.
 int apply_edit_batch(vxrt_ctx* c, const EditBatch& b);
 hipError_t launch_pick(const TraceArgs& a, const float* origins, const float* dirs, vxrt_pick_hit* out, unsigned n, hipStream_t s);

@@ -14,10 +14,13 @@
 //                 order give each list sorted and unique by path key, as api_edit.hip's host sort does
 //   cut           per list: the run starts of every level (key >> 3 (L + 1 - l) differs from the previous entry's) counted per chunk
 //                 of 4096 entries and level, one flat exclusive scan over [level][chunk] (which is also seg_off), one read-back of
-//                 the level counts for both lists, then child_begin and oct written by rank
+//                 the level counts for both lists, then child_begin and oct written by rank (cut_edit_lists, which
+//                 vxrt_edit_voxels_device uses for its one list)
 // Every position is a prefix sum; nothing is decided by an atomic, so two calls write the same bytes.
 #include <algorithm>
 #include <climits>
+#include <cstring>
+#include <string>
 
 #include "block_scan.h"
 #include "ctx.h"
@@ -233,6 +236,67 @@ size_t align16(size_t v) { return (v + 15) & ~size_t(15); }
 
 }  // namespace
 
+int cut_edit_lists(const uint64_t* const* lkeys, const uint32_t* m, int count, uint32_t L, hipStream_t s, const char* who, ScratchBuffer* batch,
+                   EditBatch* const* out) {
+    // counts per level and chunk, one flat scan per list -> one read-back of every list's seg_off
+    constexpr int kMaxLists = 2;
+    if (count < 1 || count > kMaxLists) { set_error(std::string(who) + ": internal error: bad list count"); return VXRT_E_INVALID; }
+    const uint32_t levels = L + 2u;
+    uint32_t chunks[kMaxLists];
+    size_t o_part[kMaxLists], part_bytes = 0;
+    for (int b = 0; b < count; b++) {
+        chunks[b] = (m[b] + kChunk - 1) / kChunk;
+        o_part[b] = part_bytes;
+        part_bytes += align16((size_t(levels) * chunks[b] + 1) * sizeof(uint64_t));
+    }
+    ScratchBuffer part, segs;
+    if (int rc = alloc_scratch(&part, part_bytes, who, "the level counts")) return rc;
+    if (int rc = alloc_scratch(&segs, size_t(count) * 32 * sizeof(uint32_t), who, "the level counts")) return rc;
+    HIP_TRY(hipMemsetAsync(segs.p, 0, size_t(count) * 32 * sizeof(uint32_t), s));
+    for (int b = 0; b < count; b++) {
+        if (m[b] == 0) continue;
+        uint64_t* p = reinterpret_cast<uint64_t*>(part.as<char>() + o_part[b]);
+        hipLaunchKernelGGL(cut_count_kernel, dim3(chunks[b]), dim3(kThreads), 0, s, lkeys[b], m[b], L, chunks[b], p);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(launch_exclusive_scan(p, levels * chunks[b], s));
+        hipLaunchKernelGGL(cut_offsets_kernel, dim3(1), dim3(64), 0, s, p, L, chunks[b], segs.as<uint32_t>() + 32 * b);
+        HIP_TRY(hipGetLastError());
+    }
+    uint32_t seg_off[kMaxLists][32];
+    HIP_TRY(hipMemcpyAsync(seg_off, segs.p, size_t(count) * 32 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+
+    // child_begin | oct of every list, then the edit kernel's scratch (node | flag | out), shared by the launches
+    size_t o_cb[kMaxLists], o_oct[kMaxLists], bytes = 0, node_max = 0;
+    for (int b = 0; b < count; b++) {
+        const size_t node_segs = seg_off[b][L + 1], total = seg_off[b][L + 2];
+        o_cb[b] = bytes;
+        bytes += align16((node_segs + 1) * 4);
+        o_oct[b] = bytes;
+        bytes += align16(total);
+        node_max = std::max(node_max, node_segs);
+    }
+    const size_t o_node = bytes, o_flag = o_node + align16(node_max * 4), o_out = o_flag + align16(node_max);
+    if (int rc = alloc_scratch(batch, o_out + 8 * 4, who, "the edit batches")) return rc;
+    char* base = batch->as<char>();
+    for (int b = 0; b < count; b++) {
+        if (m[b] == 0) continue;
+        const uint64_t* p = reinterpret_cast<const uint64_t*>(part.as<char>() + o_part[b]);
+        hipLaunchKernelGGL(cut_write_kernel, dim3(chunks[b]), dim3(kThreads), 0, s, lkeys[b], m[b], L, chunks[b], p,
+                           reinterpret_cast<uint32_t*>(base + o_cb[b]), reinterpret_cast<uint8_t*>(base + o_oct[b]));
+        HIP_TRY(hipGetLastError());
+        EditBatch& eb = *out[b];
+        memcpy(eb.seg_off, seg_off[b], sizeof eb.seg_off);
+        eb.child_begin = reinterpret_cast<const uint32_t*>(base + o_cb[b]);
+        eb.oct = reinterpret_cast<const uint8_t*>(base + o_oct[b]);
+        eb.node = reinterpret_cast<uint32_t*>(base + o_node);
+        eb.flag = reinterpret_cast<uint8_t*>(base + o_flag);
+        eb.out = reinterpret_cast<uint32_t*>(base + o_out);
+    }
+    HIP_TRY(hipStreamSynchronize(s));   // `part` is freed on return
+    return VXRT_OK;
+}
+
 int diff_grid_device(const GridEdit& e, const uint32_t* pal, const uint64_t (*outside)[6], uint32_t n_outside, hipStream_t s,
                      GridEditLists* out) {
     const uint64_t ntiles64 = uint64_t(e.g.nt[0]) * e.g.nt[1] * e.g.nt[2];
@@ -292,66 +356,18 @@ int diff_grid_device(const GridEdit& e, const uint32_t* pal, const uint64_t (*ou
     }
     HIP_TRY(hipGetLastError());
 
-    // the cut of both lists: counts per level and chunk, one flat scan each -> one read-back of both lists' seg_off
-    const uint32_t levels = L + 2u;
+    // the cut of both lists -> the two batches
     const uint32_t m[2] = {n_clear, n_set};
     const uint64_t* lkeys[2] = {ckeys, skeys};
-    uint32_t chunks[2];
-    size_t o_part[2], part_bytes = 0;
-    for (int b = 0; b < 2; b++) {
-        chunks[b] = (m[b] + kChunk - 1) / kChunk;
-        o_part[b] = part_bytes;
-        part_bytes += align16((size_t(levels) * chunks[b] + 1) * sizeof(uint64_t));
-    }
-    ScratchBuffer part, segs;
-    if (int rc = alloc_scratch(&part, part_bytes, who, "the level counts")) return rc;
-    if (int rc = alloc_scratch(&segs, 2 * 32 * sizeof(uint32_t), who, "the level counts")) return rc;
-    HIP_TRY(hipMemsetAsync(segs.p, 0, 2 * 32 * sizeof(uint32_t), s));
+    EditBatch* eb[2] = {&out->clears, &out->sets};
+    if (int rc = cut_edit_lists(lkeys, m, 2, L, s, who, &out->buf[1], eb)) return rc;
     for (int b = 0; b < 2; b++) {
         if (m[b] == 0) continue;
-        uint64_t* p = reinterpret_cast<uint64_t*>(part.as<char>() + o_part[b]);
-        hipLaunchKernelGGL(cut_count_kernel, dim3(chunks[b]), dim3(kThreads), 0, s, lkeys[b], m[b], L, chunks[b], p);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(launch_exclusive_scan(p, levels * chunks[b], s));
-        hipLaunchKernelGGL(cut_offsets_kernel, dim3(1), dim3(64), 0, s, p, L, chunks[b], segs.as<uint32_t>() + 32 * b);
-        HIP_TRY(hipGetLastError());
+        eb[b]->clear = b == 0;
+        eb[b]->words = b == 0 ? nullptr : swords;
+        for (int a = 0; a < 3; a++) { eb[b]->lo[a] = all.all.lo[a]; eb[b]->hi[a] = all.all.hi[a]; }
     }
-    uint32_t seg_off[2][32];
-    HIP_TRY(hipMemcpyAsync(seg_off, segs.p, sizeof seg_off, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-
-    // child_begin | oct of both lists, then the edit kernel's scratch (node | flag | out), shared by the two launches
-    size_t o_cb[2], o_oct[2], bytes = 0, node_max = 0;
-    for (int b = 0; b < 2; b++) {
-        const size_t node_segs = seg_off[b][L + 1], total = seg_off[b][L + 2];
-        o_cb[b] = bytes;
-        bytes += align16((node_segs + 1) * 4);
-        o_oct[b] = bytes;
-        bytes += align16(total);
-        node_max = std::max(node_max, node_segs);
-    }
-    const size_t o_node = bytes, o_flag = o_node + align16(node_max * 4), o_out = o_flag + align16(node_max);
-    ScratchBuffer& batch = out->buf[1];
-    if (int rc = alloc_scratch(&batch, o_out + 8 * 4, who, "the edit batches")) return rc;
-    char* base = batch.as<char>();
-    for (int b = 0; b < 2; b++) {
-        if (m[b] == 0) continue;
-        const uint64_t* p = reinterpret_cast<const uint64_t*>(part.as<char>() + o_part[b]);
-        hipLaunchKernelGGL(cut_write_kernel, dim3(chunks[b]), dim3(kThreads), 0, s, lkeys[b], m[b], L, chunks[b], p,
-                           reinterpret_cast<uint32_t*>(base + o_cb[b]), reinterpret_cast<uint8_t*>(base + o_oct[b]));
-        HIP_TRY(hipGetLastError());
-        EditBatch& eb = b == 0 ? out->clears : out->sets;
-        memcpy(eb.seg_off, seg_off[b], sizeof eb.seg_off);
-        eb.clear = b == 0;
-        eb.child_begin = reinterpret_cast<const uint32_t*>(base + o_cb[b]);
-        eb.oct = reinterpret_cast<const uint8_t*>(base + o_oct[b]);
-        eb.words = b == 0 ? nullptr : swords;
-        eb.node = reinterpret_cast<uint32_t*>(base + o_node);
-        eb.flag = reinterpret_cast<uint8_t*>(base + o_flag);
-        eb.out = reinterpret_cast<uint32_t*>(base + o_out);
-        for (int a = 0; a < 3; a++) { eb.lo[a] = all.all.lo[a]; eb.hi[a] = all.all.hi[a]; }
-    }
-    HIP_TRY(hipStreamSynchronize(s));   // `part` and `tiles` are freed on return
+    HIP_TRY(hipStreamSynchronize(s));   // `tiles` is freed on return
     return VXRT_OK;
 }
 

@@ -681,6 +681,78 @@ class Context:
         pos = np.ascontiguousarray(pos, np.int16).reshape(-1, 3)
         self._chk(self._L.vxrt_edit_voxels(self._h, _p(pos), None, C.c_size_t(len(pos))), "vxrt_edit_voxels")
 
+    def _device_list(self, pos, mrgb, clear=False):
+        """edit_voxels_device's and clear_voxels_device's arguments -> (pos int16 [n,3], mrgb uint8 [n,4] or None) as contiguous
+        tensors on the context's device.  Checked as set_voxels_device checks its own, and before anything is uploaded: numpy arrays
+        go to the device with torch once everything holds."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        given = [(pos, "pos", torch.int16, 3)] + ([] if clear else [(mrgb, "mrgb", torch.uint8, 4)])
+        if not all(isinstance(a, (np.ndarray, torch.Tensor)) for a, *_ in given):
+            raise TypeError("pos and mrgb must be torch tensors or numpy arrays")
+        counts = []
+        for a, name, dtype, width in given:
+            if isinstance(a, np.ndarray):
+                ok, size = a.dtype == np.dtype(str(dtype).split(".")[1]), a.size
+            else:
+                ok, size = a.dtype == dtype, a.numel()
+            if not ok:
+                raise ValueError("pos must be int16 and mrgb uint8")
+            if size % width:
+                raise ValueError(f"{name} must be [n,{width}]")
+            if isinstance(a, torch.Tensor) and a.device != dev:
+                raise ValueError(f"pos and mrgb must be on {dev}")
+            counts.append(size // width)
+        if len(set(counts)) != 1:
+            raise ValueError("one mrgb per position")
+        out = [(torch.as_tensor(a, device=dev) if isinstance(a, np.ndarray) else a).reshape(-1, width).contiguous() for a, _, _, width in given]
+        return out[0], (None if clear else out[1])
+
+    def edit_voxels_device(self, pos, mrgb, grow=False):
+        """vxrt_edit_voxels_device (include/vxrt_device_edit.h): edit_voxels with the list in device memory, keyed, sorted and cut into
+        the edit's segments on the device.  pos / mrgb are torch tensors on the context's device (int16 [n,3], uint8 [n,4]), or numpy
+        arrays, which are uploaded with torch first.  The context's stream first waits for torch's current stream, so a tensor just
+        written there is read whole.  Same records, stats and frames as edit_voxels of the same list.
+        grow=True: as edit_voxels, with the positions' bounds taken with torch on the device."""
+        import torch
+        pos, mrgb = self._device_list(pos, mrgb)
+        if grow and len(pos):
+            lo, hi = pos.amin(dim=0).cpu().numpy(), pos.amax(dim=0).cpu().numpy()
+            need = cube_depth(lo, hi)
+            if need > self.scene_depth:
+                self.set_scene_depth(need)
+        self.context_wait_stream(torch.cuda.current_stream(pos.device).cuda_stream)
+        self._chk(self._L.vxrt_edit_voxels_device(self._h, C.c_void_p(pos.data_ptr() if len(pos) else None),
+                                                  C.c_void_p(mrgb.data_ptr() if len(pos) else None), C.c_size_t(len(pos))),
+                  "vxrt_edit_voxels_device")
+
+    def clear_voxels_device(self, pos):
+        """vxrt_edit_voxels_device without words: clear_voxels with the positions (int16 [n,3]) in device memory."""
+        import torch
+        pos, _ = self._device_list(pos, None, clear=True)
+        self.context_wait_stream(torch.cuda.current_stream(pos.device).cuda_stream)
+        self._chk(self._L.vxrt_edit_voxels_device(self._h, C.c_void_p(pos.data_ptr() if len(pos) else None), None, C.c_size_t(len(pos))),
+                  "vxrt_edit_voxels_device")
+
+    def get_voxels_device(self, box_min=None, box_max=None):
+        """vxrt_get_voxels_device: get_voxels into torch tensors on the context's device -> (pos int16[n,3], mrgb uint8[n,4]), the same
+        voxels in the same order; only the count crosses to the host.  Ordered on both sides against torch's current stream."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        lo, hi = self._box(box_min, box_max)
+        got = C.c_size_t(0)
+        self._chk(self._L.vxrt_get_voxels_device(self._h, _p(lo), _p(hi), None, None, C.c_size_t(0), C.byref(got)), "vxrt_get_voxels_device")
+        n = int(got.value)
+        pos, mrgb = torch.empty((n, 3), dtype=torch.int16, device=dev), torch.empty((n, 4), dtype=torch.uint8, device=dev)
+        if n:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            self.context_wait_stream(stream)
+            self._chk(self._L.vxrt_get_voxels_device(self._h, _p(lo), _p(hi), C.c_void_p(pos.data_ptr()), C.c_void_p(mrgb.data_ptr()),
+                                                     C.c_size_t(n), C.byref(got)), "vxrt_get_voxels_device")
+            assert got.value == n
+            self.stream_wait_context(stream)
+        return pos, mrgb
+
     def set_scene_depth(self, depth):
         """vxrt_set_scene_depth (include/vxrt_scene_depth.h): change the octree depth of the scene in place, on the device; the root
         cube becomes [-2^depth, 2^depth)^3 (0 <= depth <= 15).  Growing always works; shrinking only while every voxel lies in the

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "vxrt.h"
+#include "vxrt_device_edit.h"
 #include "vxrt_device_scene.h"
 #include "vxrt_edit.h"
 #include "vxrt_extract.h"
@@ -195,6 +196,17 @@ class Context {
     // context's stream (a producer on another stream calls context_wait_stream first); the octree is built on the device
     void set_voxels_device(const int16_t (*pos)[3], const uint8_t (*mrgb)[4], size_t n) {
         check(vxrt_set_voxels_device(ctx_, pos, mrgb, n), "vxrt_set_voxels_device");
+    }
+    // vxrt_device_edit.h: edit_voxels / clear_voxels / get_voxels with the lists in device memory of the context's device, read and
+    // written on the context's stream.  get_voxels_device: nullptr arrays count; otherwise cap is their room, and the count returns
+    void edit_voxels_device(const int16_t (*pos)[3], const uint8_t (*mrgb)[4], size_t n) {
+        check(vxrt_edit_voxels_device(ctx_, pos, mrgb, n), "vxrt_edit_voxels_device");
+    }
+    void clear_voxels_device(const int16_t (*pos)[3], size_t n) { check(vxrt_edit_voxels_device(ctx_, pos, nullptr, n), "vxrt_edit_voxels_device"); }
+    size_t get_voxels_device(const int32_t* box_min, const int32_t* box_max, int16_t (*pos)[3], uint8_t (*mrgb)[4], size_t cap) {
+        size_t n = 0;
+        check(vxrt_get_voxels_device(ctx_, box_min, box_max, pos, mrgb, cap, &n), "vxrt_get_voxels_device");
+        return n;
     }
     // vxrt_set_voxel_grid (vxrt_grid.h): dims[0] x dims[1] x dims[2] cells in device memory of the context's device, C order
     // [x][y][z], cell (i, j, k) at origin + (i, j, k); palette: 256 entries for VXRT_GRID_PALETTE8, nullptr for VXRT_GRID_WORD32
