@@ -148,6 +148,27 @@ int apply_node_order(vxrt_ctx* c) {
     return VXRT_OK;
 }
 
+// The sky cull's box of breadth-first records in device memory, from the top of the tree: levels 0 .. 6 are a prefix of the records
+// (find where level 7 starts, copy that much, scene_box).  *valid = false, and the box untouched, for an empty scene or a prefix too
+// large to read back.  Waits for the copies; whatever wrote the records must have finished.
+int device_scene_box(const SvoRecord* svo, size_t nsvo, uint32_t depth, SvoRecord root, const float root_center[3], float root_size, bool* valid,
+                     float box_min[3], float box_max[3]) {
+    *valid = false;
+    size_t prefix = 1;
+    SvoRecord first = root;
+    for (uint32_t l = 0; l < (depth < 7u ? depth : 7u) && (first.masks & 0xffu) != 0u; l++) {
+        prefix = first.base;
+        if (prefix >= nsvo) break;
+        HIP_TRY(hipMemcpy(&first, svo + prefix, sizeof first, hipMemcpyDeviceToHost));
+    }
+    if (prefix <= nsvo && prefix <= (size_t(1) << 22)) {
+        std::vector<SvoRecord> top(prefix);
+        HIP_TRY(hipMemcpy(top.data(), svo, prefix * sizeof(SvoRecord), hipMemcpyDeviceToHost));
+        *valid = scene_box(top.data(), top.size(), depth, root_center, root_size, box_min, box_max);
+    }
+    return VXRT_OK;
+}
+
 // Device arrays built for the context become its scene (the context owns them from here; the old scene's arrays are freed): the
 // tail of every device build (vxrt_set_menger, vxrt_set_voxels_device).  The caller has drained the context (sync_all).  wide: the
 // same tree's wide records (VXRT_OPT_SCENE_FORMAT 1) or null.
@@ -166,20 +187,7 @@ int install_scene(vxrt_ctx* c, SvoRecord* svo, size_t nsvo, int32_t* lw, size_t 
     c->depth = depth;
     c->has_scene = true;
     scene_replaced(c);
-    // the sky cull's box from the top of the tree: levels 0 .. 6 are a prefix of the records (find where level 7 starts, copy that much)
-    c->box_valid = false;
-    size_t prefix = 1;
-    SvoRecord first = root;
-    for (uint32_t l = 0; l < (depth < 7u ? depth : 7u) && (first.masks & 0xffu) != 0u; l++) {
-        prefix = first.base;
-        if (prefix >= nsvo) break;
-        HIP_TRY(hipMemcpy(&first, svo + prefix, sizeof first, hipMemcpyDeviceToHost));
-    }
-    if (prefix <= nsvo && prefix <= (size_t(1) << 22)) {
-        std::vector<SvoRecord> top(prefix);
-        HIP_TRY(hipMemcpy(top.data(), svo, prefix * sizeof(SvoRecord), hipMemcpyDeviceToHost));
-        c->box_valid = scene_box(top.data(), top.size(), depth, c->root_center, c->root_size, c->box_min, c->box_max);
-    }
+    if (int rc = device_scene_box(svo, nsvo, depth, root, c->root_center, c->root_size, &c->box_valid, c->box_min, c->box_max)) return rc;
     return c->scene_format == 1 ? VXRT_OK : apply_node_order(c);
 }
 

@@ -11,6 +11,7 @@
 //   api_extract.hip  the scene's voxels read back from the device, whole or by box (vxrt_extract.h)
 //   api_device_scene.hip  a scene built on the device from a voxel list in device memory (vxrt_device_scene.h)
 //   api_scene_depth.hip   the octree depth of a loaded scene changed in place (vxrt_scene_depth.h)
+//   api_compact.hip  an edited scene re-laid as a fresh build lies, and the storage counts (vxrt_compact.h)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -321,6 +322,9 @@ bool use_wide(const vxrt_ctx* c);
 // the smallest box of cells of tree level min(depth, 7) that holds every voxel; recs: the first records of the tree, breadth first,
 // at least those of levels 0 .. min(depth, 7) - 1.  false: no voxel at all
 bool scene_box(const SvoRecord* recs, size_t count, uint32_t depth, const float root_center[3], float root_size, float box_min[3], float box_max[3]);
+// the same box for breadth-first records in device memory (root = svo[0]): reads the prefix back.  *valid as scene_box's result
+int device_scene_box(const SvoRecord* svo, size_t nsvo, uint32_t depth, SvoRecord root, const float root_center[3], float root_size, bool* valid,
+                     float box_min[3], float box_max[3]);
 // device arrays built for the context become its scene (frees the old one; sets the counts, the sky cull's box, the node order)
 int install_scene(vxrt_ctx* c, SvoRecord* svo, size_t nsvo, int32_t* lw, size_t nlw, uint32_t depth, SvoRecord root, WideRec* wide,
                   size_t nwide, WideRec wide_root);

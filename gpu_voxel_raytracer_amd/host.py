@@ -171,6 +171,12 @@ class HaloInfo(C.Structure):
                 ("edge_tile_rows", C.c_uint32), ("max_rows", C.c_uint32), ("message_bytes", C.c_uint64)]
 
 
+class SceneStorage(C.Structure):
+    """vxrt_scene_storage (include/vxrt_compact.h)."""
+    _fields_ = [("records_live", C.c_uint64), ("records_used", C.c_uint64), ("records_capacity", C.c_uint64),
+                ("leaves_used", C.c_uint64), ("leaves_capacity", C.c_uint64)]
+
+
 # vxrt_pick_hit (include/vxrt_edit.h)
 PICK_HIT_DTYPE = np.dtype([("status", np.uint32), ("time", np.float32), ("normal", np.float32, (3,)), ("voxel", np.int32, (3,)),
                            ("leaf", np.int32)])
@@ -767,6 +773,20 @@ class Context:
         d = C.c_uint32(0)
         self._chk(self._L.vxrt_fit_scene_depth(self._h, C.byref(d)), "vxrt_fit_scene_depth")
         return int(d.value)
+
+    def compact_scene(self):
+        """vxrt_compact_scene (include/vxrt_compact.h): re-lay the edited scene, on the device, as a fresh build of the same tree lies;
+        the holes edits left are given back and the storage is exactly the live tree again.  The voxels, their read-back order, every
+        frame and the temporal history stay; the sky cull's box becomes a fresh build's.  A never-edited scene is left as it is."""
+        self._chk(self._L.vxrt_compact_scene(self._h), "vxrt_compact_scene")
+
+    def scene_storage(self):
+        """vxrt_get_scene_storage: the scene's storage as the context counts it -> dict of records_live / records_used /
+        records_capacity (8-byte records: in the tree, up to the end in use, allocated) and leaves_used / leaves_capacity (leaf
+        words).  records_used - records_live are holes; no device work."""
+        s = SceneStorage()
+        self._chk(self._L.vxrt_get_scene_storage(self._h, C.byref(s)), "vxrt_get_scene_storage")
+        return {name: int(getattr(s, name)) for name, _ in SceneStorage._fields_}
 
     @property
     def scene_depth(self):

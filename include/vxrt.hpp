@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "vxrt.h"
+#include "vxrt_compact.h"
 #include "vxrt_device_edit.h"
 #include "vxrt_device_scene.h"
 #include "vxrt_edit.h"
@@ -235,6 +236,14 @@ class Context {
         uint32_t depth = 0;
         check(vxrt_fit_scene_depth(ctx_, &depth), "vxrt_fit_scene_depth");
         return depth;
+    }
+    // vxrt_compact.h: the edited scene re-laid as a fresh build of the same tree lies (the holes edits left are given back), and
+    // the storage counts a host decides by
+    void compact_scene() { check(vxrt_compact_scene(ctx_), "vxrt_compact_scene"); }
+    vxrt_scene_storage scene_storage() {
+        vxrt_scene_storage s{};
+        check(vxrt_get_scene_storage(ctx_, &s), "vxrt_get_scene_storage");
+        return s;
     }
     void set_menger(uint32_t level, uint32_t clip, std::array<uint8_t, 4> mrgb, uint32_t emissive_period) {
         check(vxrt_set_menger(ctx_, level, clip, mrgb.data(), emissive_period), "vxrt_set_menger");
