@@ -759,6 +759,95 @@ class Context:
             self.stream_wait_context(stream)
         return pos, mrgb
 
+    def _mesh(self, verts, tris, mrgb):
+        """voxelize_mesh's arguments -> (verts float32 [v,3], tris uint32 [t,3], mrgb uint8 [t,4]) as contiguous tensors on the
+        context's device.  Checked before anything is uploaded or any library call is made.  tris may be int32 or uint32 (torch has
+        little arithmetic for uint32; the bits are the same and a negative index is refused as out of range by the library), or
+        int64, which is converted.  A single mrgb (4 values) is broadcast to all triangles."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        if not all(isinstance(a, (np.ndarray, torch.Tensor)) for a in (verts, tris)):
+            raise TypeError("verts and tris must be torch tensors or numpy arrays")
+        if not isinstance(mrgb, (np.ndarray, torch.Tensor)):
+            if not (isinstance(mrgb, (tuple, list)) and len(mrgb) == 4 and all(isinstance(b, (int, np.integer)) and 0 <= b <= 255 for b in mrgb)):
+                raise TypeError("mrgb must be a torch tensor, a numpy array or one (m, r, g, b) of bytes")
+            mrgb = np.array(mrgb, np.uint8)
+
+        def name(a):
+            return str(a.dtype).replace("torch.", "")
+        if name(verts) != "float32":
+            raise ValueError("verts must be float32")
+        if name(tris) not in ("uint32", "int32", "int64"):
+            raise ValueError("tris must be uint32, int32 or int64")
+        if name(mrgb) != "uint8":
+            raise ValueError("mrgb must be uint8")
+        size = lambda a: a.size if isinstance(a, np.ndarray) else a.numel()   # noqa: E731
+        for a, what, width in ((verts, "verts", 3), (tris, "tris", 3), (mrgb, "mrgb", 4)):
+            if size(a) % width or (a.ndim > 1 and a.shape[-1] != width) or a.ndim > 2:
+                raise ValueError(f"{what} must be [n,{width}]")
+            if isinstance(a, torch.Tensor) and a.device != dev:
+                raise ValueError(f"verts, tris and mrgb must be on {dev}")
+        n_tris = size(tris) // 3
+        if size(mrgb) != 4 and size(mrgb) != 4 * n_tris:
+            raise ValueError("one mrgb per triangle, or a single one for all")
+        if name(tris) == "int64":
+            if bool((tris < 0).any()) or bool((tris >= (1 << 32)).any()):
+                raise ValueError("a triangle index is outside [0, 2^32)")
+            if isinstance(tris, np.ndarray):
+                tris = tris.astype(np.uint32)
+            else:
+                tris = torch.where(tris >= (1 << 31), tris - (1 << 32), tris).to(torch.int32)
+        if isinstance(tris, np.ndarray) and tris.dtype == np.uint32:
+            tris = np.ascontiguousarray(tris).view(np.int32)                    # the same bits: torch uploads int32
+        to_dev = lambda a: torch.as_tensor(a, device=dev) if isinstance(a, np.ndarray) else a   # noqa: E731
+        verts, tris, mrgb = to_dev(verts).reshape(-1, 3).contiguous(), to_dev(tris).reshape(-1, 3).contiguous(), to_dev(mrgb).reshape(-1, 4)
+        if len(mrgb) != n_tris:
+            mrgb = mrgb.expand(n_tris, 4)
+        return verts, tris, mrgb.contiguous()
+
+    def voxelize_mesh(self, verts, tris, mrgb, cap=None):
+        """vxrt_voxelize_mesh_device (include/vxrt_voxelize.h): the voxels a triangle mesh's surface meets -> (pos int16[n,3], mrgb
+        uint8[n,4]) as torch tensors on the context's device, each voxel once, in the order of get_voxels; a voxel met by several
+        triangles takes the mrgb of the highest triangle index.  verts (float32 [v,3], in voxel units: the voxel at p is the cube
+        [p, p+1)^3), tris (uint32 / int32 / int64 [t,3]) and mrgb (uint8 [t,4], or a single (m, r, g, b) for all triangles) are torch
+        tensors on the context's device, or numpy arrays, which are uploaded with torch first.  Ordered on both sides against torch's
+        current stream.  No scene is needed and none is touched.
+        cap=None: the mesh is voxelised twice, once to count and once into tensors of exactly that size (about twice the time of one
+        run: DESIGN.md §17).  cap=k: one run into tensors with room for k voxels, cut to the count; more than k voxels is an error
+        (VXRT_E_INVALID)."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        if cap is not None and (not isinstance(cap, (int, np.integer)) or isinstance(cap, bool) or cap < 0):
+            raise ValueError("cap must be a count of voxels")
+        verts, tris, mrgb = self._mesh(verts, tris, mrgb)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        self.context_wait_stream(stream)
+        args = (self._h, C.c_void_p(verts.data_ptr() if len(verts) else None), C.c_size_t(len(verts)),
+                C.c_void_p(tris.data_ptr() if len(tris) else None), C.c_void_p(mrgb.data_ptr() if len(tris) else None), C.c_size_t(len(tris)))
+        got = C.c_size_t(0)
+        if cap is None:
+            self._chk(self._L.vxrt_voxelize_mesh_device(*args, None, None, C.c_size_t(0), C.byref(got)), "vxrt_voxelize_mesh_device")
+            cap = int(got.value)
+        pos, out = torch.empty((cap, 3), dtype=torch.int16, device=dev), torch.empty((cap, 4), dtype=torch.uint8, device=dev)
+        if cap:
+            self.context_wait_stream(stream)      # the allocator may hand out memory that work on torch's stream still uses
+            self._chk(self._L.vxrt_voxelize_mesh_device(*args, C.c_void_p(pos.data_ptr()), C.c_void_p(out.data_ptr()), C.c_size_t(cap),
+                                                        C.byref(got)), "vxrt_voxelize_mesh_device")
+            self.stream_wait_context(stream)
+        n = int(got.value)
+        return pos[:n], out[:n]
+
+    def set_mesh(self, verts, tris, mrgb, cap=None):
+        """voxelize_mesh, then set_voxels_device of its list: the scene becomes the mesh's surface, built on the device end to end."""
+        pos, out = self.voxelize_mesh(verts, tris, mrgb, cap=cap)
+        self.set_voxels_device(pos, out)
+
+    def edit_mesh(self, verts, tris, mrgb, grow=False, cap=None):
+        """voxelize_mesh, then edit_voxels_device of its list: the mesh's surface is set into the loaded scene in place.  grow: as
+        edit_voxels_device."""
+        pos, out = self.voxelize_mesh(verts, tris, mrgb, cap=cap)
+        self.edit_voxels_device(pos, out, grow=grow)
+
     def set_scene_depth(self, depth):
         """vxrt_set_scene_depth (include/vxrt_scene_depth.h): change the octree depth of the scene in place, on the device; the root
         cube becomes [-2^depth, 2^depth)^3 (0 <= depth <= 15).  Growing always works; shrinking only while every voxel lies in the

@@ -25,6 +25,7 @@
 #include "vxrt_grid_edit.h"
 #include "vxrt_host.h"
 #include "vxrt_scene_depth.h"
+#include "vxrt_voxelize.h"
 
 namespace vxrt {
 
@@ -207,6 +208,14 @@ class Context {
     size_t get_voxels_device(const int32_t* box_min, const int32_t* box_max, int16_t (*pos)[3], uint8_t (*mrgb)[4], size_t cap) {
         size_t n = 0;
         check(vxrt_get_voxels_device(ctx_, box_min, box_max, pos, mrgb, cap, &n), "vxrt_get_voxels_device");
+        return n;
+    }
+    // vxrt_voxelize.h: the voxels a triangle mesh's surface meets, mesh and list in device memory of the context's device.  nullptr
+    // pos / mrgb count; otherwise cap is their room, and the count returns.  The list is what set_voxels_device / edit_voxels_device take
+    size_t voxelize_mesh_device(const float (*verts)[3], size_t n_verts, const uint32_t (*tris)[3], const uint8_t (*tri_mrgb)[4], size_t n_tris,
+                                int16_t (*pos)[3], uint8_t (*mrgb)[4], size_t cap) {
+        size_t n = 0;
+        check(vxrt_voxelize_mesh_device(ctx_, verts, n_verts, tris, tri_mrgb, n_tris, pos, mrgb, cap, &n), "vxrt_voxelize_mesh_device");
         return n;
     }
     // vxrt_set_voxel_grid (vxrt_grid.h): dims[0] x dims[1] x dims[2] cells in device memory of the context's device, C order
