@@ -5,6 +5,8 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "ctx.h"
+
 namespace vxrt {
 
 // A work item is one (triangle, column) pair: a column is a line of candidate cells along the first axis of greatest |n_a| of the
@@ -54,5 +56,27 @@ hipError_t voxelize_emit(const VoxTri* tq, const uint64_t* off, uint32_t n_tris,
 // 4-byte aligned), as vxrt_get_voxels gives them.
 hipError_t voxelize_decode(const uint64_t* keys, const int32_t* words, uint32_t m, uint32_t depth, int16_t* pos, uint32_t* mrgb,
                            hipStream_t stream);
+
+// ---- api_voxelize.hip: what the entry points that take a mesh share (vxrt_voxelize_mesh_device, vxrt_voxelize_solid_device)
+// The checks of a mesh's arrays and of the output arrays, n_tris > 0: null and misaligned pointers, then check_device_array on each
+// array given (tri_mrgb may be null; pos and mrgb are looked at when pos is not null and cap != 0).  who: the API call.
+int voxelize_check_args(vxrt_ctx* c, const char* who, const void* verts, size_t n_verts, const void* tris, const void* tri_mrgb, size_t n_tris,
+                        const void* pos, const void* mrgb, size_t cap);
+
+// The setup pass with its scratch and its three refusals (a bad index, a vertex that is not finite, a vertex out of range).
+struct MeshFront {
+    ScratchBuffer tq, off, tpart, bounds;
+    MeshSummary ms;
+    uint64_t columns = 0;
+};
+int voxelize_front(const char* who, const void* verts, size_t n_verts, const void* tris, size_t n_tris, hipStream_t stream, MeshFront* f);
+
+// The least depth whose cube [-2^depth, 2^depth)^3 holds the candidate cells of all triangles (rule 5): at most 15.
+uint32_t voxelize_depth(const MeshSummary& ms);
+
+// The way out: m unique keys at `depth` and their leaf words -> *n and, with pos, the caller's arrays by the cap rule (decoded in
+// place, or through staging buffers where pos or mrgb is not aligned for the kernel's stores).  Waits for the stream.
+int voxelize_output(const char* who, const uint64_t* keys, const int32_t* words, size_t m, uint32_t depth, void* pos, void* mrgb, size_t cap,
+                    hipStream_t stream, size_t* n);
 
 }  // namespace vxrt

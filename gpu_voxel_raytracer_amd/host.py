@@ -41,6 +41,8 @@ E_VOX_MATERIAL, E_VOX_NOMATL, E_VOX_NOMODEL, E_IO, E_SCENE, E_NOSCENE, E_NOISE =
 
 # vxrt_grid_format (include/vxrt_grid.h)
 GRID_PALETTE8, GRID_WORD32 = 1, 2
+# vxrt_solid_mode (include/vxrt_solid.h)
+SOLID_UNION, SOLID_INTERIOR = 0, 1
 # vxrt_grid_edit_mode (include/vxrt_grid_edit.h)
 GRID_EDIT_REPLACE, GRID_EDIT_SET, GRID_EDIT_CLEAR = 1, 2, 3
 GRID_EDIT_MODES = {"replace": GRID_EDIT_REPLACE, "set": GRID_EDIT_SET, "clear": GRID_EDIT_CLEAR}
@@ -847,6 +849,64 @@ class Context:
         edit_voxels_device."""
         pos, out = self.voxelize_mesh(verts, tris, mrgb, cap=cap)
         self.edit_voxels_device(pos, out, grow=grow)
+
+    def voxelize_solid(self, verts, tris, mrgb, fill, interior_only=False, cap=None):
+        """vxrt_voxelize_solid_device (include/vxrt_solid.h): a closed triangle mesh as a solid -> (pos int16[n,3], mrgb uint8[n,4]) as
+        torch tensors on the context's device, each voxel once, in the order of get_voxels.  interior_only=False (VXRT_SOLID_UNION):
+        the voxels of voxelize_mesh with their bytes, and the cells inside the mesh that are not among them with the bytes of fill.
+        interior_only=True (VXRT_SOLID_INTERIOR): the cells inside the mesh and nothing else, with the bytes of fill; mrgb may be
+        None.  Inside is decided by crossing parity along z: a mesh that is not closed is refused (VXRT_E_SCENE),
+        overlapping shells XOR and a shell inside a shell is a cavity.  verts, tris, mrgb and cap: as voxelize_mesh takes them;
+        fill: one (m, r, g, b) of bytes."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        if cap is not None and (not isinstance(cap, (int, np.integer)) or isinstance(cap, bool) or cap < 0):
+            raise ValueError("cap must be a count of voxels")
+        if isinstance(fill, np.ndarray):
+            if fill.dtype != np.uint8 or fill.size != 4:
+                raise ValueError("fill must be one (m, r, g, b) of uint8")
+            fill = [int(b) for b in fill.reshape(4)]
+        if not (isinstance(fill, (tuple, list)) and len(fill) == 4 and all(isinstance(b, (int, np.integer)) and not isinstance(b, bool) and 0 <= b <= 255 for b in fill)):
+            raise TypeError("fill must be one (m, r, g, b) of bytes")
+        if not isinstance(interior_only, (bool, np.bool_)):
+            raise TypeError("interior_only must be a bool")
+        without_colours = mrgb is None and interior_only
+        verts, tris, mrgb = self._mesh(verts, tris, (0, 0, 0, 0) if without_colours else mrgb)
+        fill4 = (C.c_uint8 * 4)(*[int(b) for b in fill])
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        self.context_wait_stream(stream)
+        args = (self._h, C.c_void_p(verts.data_ptr() if len(verts) else None), C.c_size_t(len(verts)),
+                C.c_void_p(tris.data_ptr() if len(tris) else None), C.c_void_p(mrgb.data_ptr() if len(tris) and not without_colours else None),
+                C.c_size_t(len(tris)), fill4, C.c_uint32(SOLID_INTERIOR if interior_only else SOLID_UNION))
+        got = C.c_size_t(0)
+        if cap is None:
+            self._chk(self._L.vxrt_voxelize_solid_device(*args, None, None, C.c_size_t(0), C.byref(got)), "vxrt_voxelize_solid_device")
+            cap = int(got.value)
+        pos, out = torch.empty((cap, 3), dtype=torch.int16, device=dev), torch.empty((cap, 4), dtype=torch.uint8, device=dev)
+        if cap:
+            self.context_wait_stream(stream)      # the allocator may hand out memory that work on torch's stream still uses
+            self._chk(self._L.vxrt_voxelize_solid_device(*args, C.c_void_p(pos.data_ptr()), C.c_void_p(out.data_ptr()), C.c_size_t(cap),
+                                                         C.byref(got)), "vxrt_voxelize_solid_device")
+            self.stream_wait_context(stream)
+        n = int(got.value)
+        return pos[:n], out[:n]
+
+    def set_solid(self, verts, tris, mrgb, fill, cap=None):
+        """voxelize_solid, then set_voxels_device of its list: the scene becomes the mesh as a solid, built on the device end to end."""
+        pos, out = self.voxelize_solid(verts, tris, mrgb, fill, cap=cap)
+        self.set_voxels_device(pos, out)
+
+    def edit_solid(self, verts, tris, mrgb, fill, grow=False, cap=None):
+        """voxelize_solid, then edit_voxels_device of its list: the mesh is set into the loaded scene as a solid, in place.  grow: as
+        edit_voxels_device."""
+        pos, out = self.voxelize_solid(verts, tris, mrgb, fill, cap=cap)
+        self.edit_voxels_device(pos, out, grow=grow)
+
+    def carve_solid(self, verts, tris):
+        """voxelize_solid's interior-only list, then clear_voxels_device of it: the cells inside the mesh are cleared from the loaded
+        scene in place (the voxels its surface meets outside that interior stay)."""
+        pos, _ = self.voxelize_solid(verts, tris, None, (0, 0, 0, 0), interior_only=True)
+        self.clear_voxels_device(pos)
 
     def set_scene_depth(self, depth):
         """vxrt_set_scene_depth (include/vxrt_scene_depth.h): change the octree depth of the scene in place, on the device; the root

@@ -25,6 +25,7 @@
 #include "vxrt_grid_edit.h"
 #include "vxrt_host.h"
 #include "vxrt_scene_depth.h"
+#include "vxrt_solid.h"
 #include "vxrt_voxelize.h"
 
 namespace vxrt {
@@ -216,6 +217,15 @@ class Context {
                                 int16_t (*pos)[3], uint8_t (*mrgb)[4], size_t cap) {
         size_t n = 0;
         check(vxrt_voxelize_mesh_device(ctx_, verts, n_verts, tris, tri_mrgb, n_tris, pos, mrgb, cap, &n), "vxrt_voxelize_mesh_device");
+        return n;
+    }
+    // vxrt_solid.h: the interior of a closed mesh (VXRT_SOLID_INTERIOR) or its surface and interior (VXRT_SOLID_UNION), as above;
+    // fill_mrgb is host memory
+    size_t voxelize_solid_device(const float (*verts)[3], size_t n_verts, const uint32_t (*tris)[3], const uint8_t (*tri_mrgb)[4], size_t n_tris,
+                                 const uint8_t fill_mrgb[4], vxrt_solid_mode mode, int16_t (*pos)[3], uint8_t (*mrgb)[4], size_t cap) {
+        size_t n = 0;
+        check(vxrt_voxelize_solid_device(ctx_, verts, n_verts, tris, tri_mrgb, n_tris, fill_mrgb, uint32_t(mode), pos, mrgb, cap, &n),
+              "vxrt_voxelize_solid_device");
         return n;
     }
     // vxrt_set_voxel_grid (vxrt_grid.h): dims[0] x dims[1] x dims[2] cells in device memory of the context's device, C order

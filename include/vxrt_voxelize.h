@@ -14,7 +14,7 @@
  *      snapped triangle and the cell's cube; touching counts as overlap.  A triangle that is a segment or a point takes the same
  *      tests and sets the cells the segment or point meets
  *   4. a voxel that several triangles set takes the mrgb of the highest triangle index
- * Interiors are not filled, and there are no vertex transforms or textures.
+ * Interiors are not filled here (vxrt_solid.h fills them), and there are no vertex transforms or textures.
  *
  * Multi-GPU: every rank holds the whole scene; voxelise on each rank's context, in its own device's memory.
  */
