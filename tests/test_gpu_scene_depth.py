@@ -10,6 +10,7 @@ import torch   # before the first context: one HIP runtime in the process (host.
 
 import edit_model as M
 import scene_depth_model as SD
+import scene_invariants as SI
 from conftest import assert_bits_equal, require_variants
 from test_gpu_edit import CONFIGS, H_, SCENES, W, assert_same_frames, base_scene, batches, fresh, make_ctx, trace_images
 
@@ -167,6 +168,7 @@ def test_random_edits_after_growing_an_edited_scene_equal_rebuilds(H, scenes):
         for t in tracked:
             assert t.call(grown) == grown
         assert SD.block_owners(tracked[0].model())
+        SI.check(*contexts[0].read_scene(), grown, contexts[0].scene_storage(), contexts[0].stats().octree_nodes, built=tracked[0].built)
         anchor = np.array([[-(1 << grown)] * 3], np.int16)       # pins every rebuild below at the grown depth
         for c in contexts:
             c.edit_voxels(anchor, [[3, 40, 50, 60]])
