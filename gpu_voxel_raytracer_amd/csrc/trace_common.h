@@ -183,9 +183,22 @@ __device__ __forceinline__ int walk_step(Walk& w, const SceneView& sc, float max
 
 // ---- the walk for regular rays ---------------------------------------------------------------------------------
 // A ray is "regular" when every component of 1/dir is finite and non-zero (all but ~1e-7 of the rays: a direction
-// component that is exactly 0 needs an exactly-0.5 noise sample).  For such rays no NaN can arise in the walk — every
-// time is fl(fl(plane - origin) * inv) with finite inv — so GLSL's min/max (vx_min / vx_max, compare + select) equal the
-// hardware's v_min3 / v_max3, the transition of voxels.comp:198-201 is never 0, and dir_mask agrees with sign(inv).
+// component that is exactly 0 needs an exactly-0.5 noise sample).  For such rays with a FINITE origin no NaN can arise in the
+// walk — every time is fl(fl(plane - origin) * inv) with finite inv — so GLSL's min/max (vx_min / vx_max, compare + select)
+// equal the hardware's v_min3 / v_max3 up to the sign of a zero, the transition of voxels.comp:198-201 is never 0, and dir_mask
+// agrees with sign(inv).
+// The origin is not this walk's to choose (vxrt_pick, a camera position), and a non-finite one does put NaN or infinities into the
+// plane times.  What the shader makes of it is decided by the ROOT test alone (walkf_begin), which therefore takes max / min by
+// compare + select in the shader's operand order, x first: an infinite coordinate makes entry >= exit or exit < 0, and a NaN in
+// origin.x makes entry and exit NaN (max(NaN, b) = NaN: the first operand stays) — a miss either way, where v_max3 / v_min3 would
+// drop the NaN and let the ray in.  A NaN in origin.y or .z alone is dropped by the shader too (max(a, NaN) = a): such a ray enters
+// on its other axes, and from then on every min / max over its times has that axis' NaN as a later operand, which compare + select
+// and the hardware's min3 / max3 both ignore, and current_octant's strict > sends it to the low side of that axis at every level.
+// The sign of a zero: when an origin lies exactly on two planes at once, the times a min is taken over can hold both +0 and -0;
+// v_min3 then returns -0 where the shader's min keeps its first operand.  No decision of the walk sees the sign of a zero time, but
+// the time it returns (voxels.comp:222-224 and :236 assign such a minimum to `time`) can be -0 where the shader's is +0.  Selecting the
+// first equal operand instead costs two to four instructions in walkf_step's sibling step and pop and measured 1-2 % slower, so the
+// loop stays and tests/test_gpu_ray_walk.py pins the difference to exactly that.
 //
 // On top of that, a descend needs no arithmetic for its slab test: all cube planes are dyadic, so the time at which the
 // ray crosses a plane, fl(fl(p - o) * inv), depends on the plane's coordinate p only — not on the node whose test
@@ -229,8 +242,8 @@ __device__ __forceinline__ bool walkf_begin(WalkF& w, const SceneView& sc, f3 o,
     w.inv = inv;
     w.dir_mask = (d.x < 0.0f ? 4u : 0u) | (d.y < 0.0f ? 2u : 0u) | (d.z < 0.0f ? 1u : 0u);
     plane_times(o, inv, sc.root_center, 0.5f * sc.root_size, w.en, w.ex);
-    const float entry = vx_max3(w.en.x, w.en.y, w.en.z);
-    w.exit = vx_min3(w.ex.x, w.ex.y, w.ex.z);
+    const float entry = vx_max(vx_max(w.en.x, w.en.y), w.en.z);   // compare + select, x first: a NaN in origin.x stays (see above)
+    w.exit = vx_min(vx_min(w.ex.x, w.ex.y), w.ex.z);
     if (!(w.exit >= 0.0f && entry < w.exit)) return false;
     w.time = vx_max(0.0f, entry);
     w.center = sc.root_center;

@@ -86,8 +86,8 @@ __device__ __forceinline__ bool walkw_begin(WalkW<true>& w, const SceneW& sc, f3
     w.o = o; w.d = d; w.inv = inv;
     w.dir_mask = (d.x < 0.0f ? 4u : 0u) | (d.y < 0.0f ? 2u : 0u) | (d.z < 0.0f ? 1u : 0u);
     plane_times(o, inv, sc.root_center, 0.5f * sc.root_size, w.en, w.ex);
-    const float entry = vx_max3(w.en.x, w.en.y, w.en.z);
-    w.exit = vx_min3(w.ex.x, w.ex.y, w.ex.z);
+    const float entry = vx_max(vx_max(w.en.x, w.en.y), w.en.z);   // compare + select, x first: a NaN in origin.x stays (see WalkF)
+    w.exit = vx_min(vx_min(w.ex.x, w.ex.y), w.ex.z);
     if (!(w.exit >= 0.0f && entry < w.exit)) return false;
     w.time = vx_max(0.0f, entry);
     w.center = sc.root_center;

@@ -42,7 +42,10 @@ typedef struct vxrt_pick_hit {
 } vxrt_pick_hit;
 
 /* Cast n rays (origins, directions in world units, as the tracers cast them) against the scene as it stands after everything
- * enqueued so far; waits for the result.  status, time, normal and leaf are those of the tracers' own walk, bit for bit. */
+ * enqueued so far; waits for the result.  status, time, normal and leaf are those of the tracers' own walk, bit for bit.
+ * A non-finite origin means what the shader's root test makes of it by compare and select, x first: an infinite
+ * coordinate or a NaN in origin[0] is a miss with time 0; a NaN in origin[1] or [2] alone is dropped and the ray stays on that axis' low side.
+ * A time of zero may come back as -0 where the shader's is +0 (an origin exactly on a voxel plane); nothing else ever differs. */
 int vxrt_pick(vxrt_ctx* ctx, const float (*origins)[3], const float (*dirs)[3], size_t n, vxrt_pick_hit* out);
 
 #ifdef __cplusplus
