@@ -89,10 +89,18 @@ def solid(verts, tris, mrgb, fill, interior_only=False):
         return np.zeros((0, 3), np.int16), np.zeros((0, 4), np.uint8)
     snapped(verts, tris)                                             # the surface's refusals come first
     inner = interior(verts, tris)
-    if interior_only:
+    return compose(None if interior_only else M.voxelize(verts, tris, mrgb), inner, fill)
+
+
+def compose(surface, inner, fill):
+    """The list of solid() from its two parts: the surface's list (pos, mrgb), or None for the interior alone, and the interior's
+    cells int64 [n, 3]."""
+    fill = np.array(fill, np.uint8).reshape(4).copy()
+    fill[0] &= 0x7f
+    if surface is None:
         pos, out = inner, np.broadcast_to(fill, (len(inner), 4))
     else:
-        spos, smrgb = M.voxelize(verts, tris, mrgb)
+        spos, smrgb = surface
         have = set(map(tuple, spos.astype(np.int64).tolist()))
         extra = np.array([c for c in map(tuple, inner.tolist()) if c not in have], np.int64).reshape(-1, 3)
         pos = np.concatenate([spos.astype(np.int64), extra])

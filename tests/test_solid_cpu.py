@@ -245,33 +245,44 @@ RAY = ((1 << 40), (1 << 40) + (1 << 20), (1 << 40) + 1)
 
 
 def ray_says_inside(name, cells):
-    """For each cell (int64 [n, 3]): does the ray from its centre along RAY cross the snapped mesh an odd number of times?  Exact:
-    Moller-Trumbore in integers (sixteenths) for every (cell, triangle) pair, vectorised, which leaves u = U / det, v = V / det and
-    t = T / det as integer pairs; the pairs that can be hits at all (|U|, |V| <= |det|) are then decided as fractions.Fraction.  A
-    ray through an edge or a vertex would be counted by both neighbours; that is asserted not to happen."""
+    """For each cell (int64 [n, 3]) and a mesh of the table: ray_crossings_are_odd, within the bounds the table's meshes keep."""
     verts, tris = TABLE[name][0]
+    assert np.abs(M.snap(verts)[0][tris.astype(np.int64)]).max() + 24 < 362 and np.abs(cells).max() < 20
+    return ray_crossings_are_odd(verts, tris, cells)
+
+
+def ray_crossings_are_odd(verts, tris, cells, chunk=256):
+    """For each cell (int64 [n, 3]): does the ray from its centre along RAY cross the snapped mesh an odd number of times?  Exact:
+    Moller-Trumbore in integers (sixteenths) for every (cell, triangle) pair, vectorised `chunk` cells at a time, which leaves
+    u = U / det, v = V / det and t = T / det as integer pairs; the pairs that can be hits at all (|U|, |V| <= |det|) are then decided
+    as fractions.Fraction.  A ray through an edge or a vertex would be counted by both neighbours; that is asserted not to happen."""
     q, finite, ok = M.snap(verts)
-    tri = q[tris.astype(np.int64)]                                   # [t, 3, 3] int64
-    assert np.abs(tri).max() + 24 < 362 and np.abs(cells).max() < 20      # 362^2 < 2^17: the sums below stay under 2^63
+    tri = q[np.asarray(tris).astype(np.int64)]                       # [t, 3, 3] int64
     d = np.array(RAY, np.int64)
     e1, e2 = tri[:, 1] - tri[:, 0], tri[:, 2] - tri[:, 0]
+    origin = 16 * np.asarray(cells, np.int64) + 8                    # [n, 3]
+    # with E the longest edge component and S the longest cell-to-vertex component, |s x e| <= 2 E S per component: below 2^19 that
+    # is RAY's condition, and every sum below stays under 3 * 2^41 * 2^19 < 2^63
+    E = int(max(np.abs(e1).max(), np.abs(e2).max()))
+    S_ = int(max(np.abs(origin.max(axis=0) - tri.min(axis=(0, 1))).max(), np.abs(origin.min(axis=0) - tri.max(axis=(0, 1))).max()))
+    assert 2 * E * max(E, S_) < 1 << 19, (E, S_)
     h = np.cross(d, e2)                                              # [t, 3]
     det = (e1 * h).sum(axis=1)                                       # [t]
     assert (det != 0).all(), "a triangle is parallel to the ray"
-    origin = 16 * np.asarray(cells, np.int64) + 8                    # [n, 3]
-    s = origin[:, None, :] - tri[None, :, 0, :]                      # [n, t, 3]
-    U = (s * h[None]).sum(axis=2)
-    qv = np.cross(s, e1[None])
-    V = (qv * d).sum(axis=2)
-    T = (qv * e2[None]).sum(axis=2)
-    maybe = (np.abs(U) <= np.abs(det)[None]) & (np.abs(V) <= np.abs(det)[None])
     crossings = np.zeros(len(origin), np.int64)
-    for i, t in zip(*np.nonzero(maybe)):
-        u, v, w = Fraction(int(U[i, t]), int(det[t])), Fraction(int(V[i, t]), int(det[t])), Fraction(int(T[i, t]), int(det[t]))
-        if u < 0 or v < 0 or u + v > 1 or w < 0:
-            continue
-        assert u > 0 and v > 0 and u + v < 1 and w > 0, "the ray meets an edge, a vertex or starts on the surface"
-        crossings[i] += 1
+    for c0 in range(0, len(origin), chunk):
+        s = origin[c0:c0 + chunk, None, :] - tri[None, :, 0, :]      # [n, t, 3]
+        U = (s * h[None]).sum(axis=2)
+        qv = np.cross(s, e1[None])
+        V = (qv * d).sum(axis=2)
+        T = (qv * e2[None]).sum(axis=2)
+        maybe = (np.abs(U) <= np.abs(det)[None]) & (np.abs(V) <= np.abs(det)[None])
+        for i, t in zip(*np.nonzero(maybe)):
+            u, v, w = Fraction(int(U[i, t]), int(det[t])), Fraction(int(V[i, t]), int(det[t])), Fraction(int(T[i, t]), int(det[t]))
+            if u < 0 or v < 0 or u + v > 1 or w < 0:
+                continue
+            assert u > 0 and v > 0 and u + v < 1 and w > 0, "the ray meets an edge, a vertex or starts on the surface"
+            crossings[c0 + i] += 1
     return crossings % 2 == 1
 
 
