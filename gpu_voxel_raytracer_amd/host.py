@@ -908,6 +908,69 @@ class Context:
         pos, _ = self.voxelize_solid(verts, tris, None, (0, 0, 0, 0), interior_only=True)
         self.clear_voxels_device(pos)
 
+    @staticmethod
+    def _connectivity(connectivity):
+        if isinstance(connectivity, bool) or not isinstance(connectivity, (int, np.integer)) or int(connectivity) not in (6, 18, 26):
+            raise ValueError("connectivity must be 6, 18 or 26")
+        return C.c_uint32(int(connectivity))
+
+    def label_components(self, pos, connectivity=6):
+        """vxrt_label_components_device (include/vxrt_components.h): the connected components of a voxel list -> (label, n_components),
+        label a uint32 [n] torch tensor on the context's device: label[i] is the least index of an entry in i's component, by faces
+        (connectivity 6), faces and edges (18) or faces, edges and corners (26).  pos (int16 [n,3]) is a torch tensor on the
+        context's device, or a numpy array, which is uploaded with torch first; it may be in any order and hold a position more
+        than once.  Ordered on both sides against torch's current stream.  No scene is needed and none is touched."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        conn = self._connectivity(connectivity)
+        pos, _ = self._device_list(pos, None, clear=True)
+        label = torch.empty(len(pos), dtype=torch.uint32, device=dev)
+        got = C.c_size_t(0)
+        if len(pos):
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            self.context_wait_stream(stream)
+            self._chk(self._L.vxrt_label_components_device(self._h, C.c_void_p(pos.data_ptr()), C.c_size_t(len(pos)), conn,
+                                                           C.c_void_p(label.data_ptr()), C.byref(got)), "vxrt_label_components_device")
+            self.stream_wait_context(stream)
+        return label, int(got.value)
+
+    def detached_voxels(self, anchor_min, anchor_max, connectivity=6, cap=None):
+        """vxrt_detached_voxels_device (include/vxrt_components.h): the voxels of the scene as it stands whose component (by
+        connectivity 6, 18 or 26, over the whole scene) holds no voxel in the half-open box [anchor_min, anchor_max) -> (pos
+        int16[n,3], mrgb uint8[n,4]) as torch tensors on the context's device, in the order and with the bytes of get_voxels.
+        cap=None: two calls, one to count and one into tensors of exactly that size.  cap=k: one call into tensors with room for k
+        voxels, cut to the count; more than k voxels is an error (VXRT_E_INVALID)."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        conn = self._connectivity(connectivity)
+        if cap is not None and (not isinstance(cap, (int, np.integer)) or isinstance(cap, bool) or cap < 0):
+            raise ValueError("cap must be a count of voxels")
+        if anchor_min is None or anchor_max is None:
+            raise ValueError("anchor_min and anchor_max: three integers each")
+        lo, hi = self._box(anchor_min, anchor_max)
+        got = C.c_size_t(0)
+        if cap is None:
+            self._chk(self._L.vxrt_detached_voxels_device(self._h, _p(lo), _p(hi), conn, None, None, C.c_size_t(0), C.byref(got)),
+                      "vxrt_detached_voxels_device")
+            cap = int(got.value)
+        pos, mrgb = torch.empty((cap, 3), dtype=torch.int16, device=dev), torch.empty((cap, 4), dtype=torch.uint8, device=dev)
+        if cap:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            self.context_wait_stream(stream)      # the allocator may hand out memory that work on torch's stream still uses
+            self._chk(self._L.vxrt_detached_voxels_device(self._h, _p(lo), _p(hi), conn, C.c_void_p(pos.data_ptr()), C.c_void_p(mrgb.data_ptr()),
+                                                          C.c_size_t(cap), C.byref(got)), "vxrt_detached_voxels_device")
+            self.stream_wait_context(stream)
+        n = int(got.value)
+        return pos[:n], mrgb[:n]
+
+    def drop_detached(self, anchor_min, anchor_max, connectivity=6):
+        """detached_voxels, then clear_voxels_device of its list: what no longer hangs on a voxel in the anchor box is removed from the
+        loaded scene in place.  Returns the removed list (pos, mrgb), which a host re-emits as debris."""
+        pos, mrgb = self.detached_voxels(anchor_min, anchor_max, connectivity=connectivity)
+        if len(pos):
+            self.clear_voxels_device(pos)
+        return pos, mrgb
+
     def set_scene_depth(self, depth):
         """vxrt_set_scene_depth (include/vxrt_scene_depth.h): change the octree depth of the scene in place, on the device; the root
         cube becomes [-2^depth, 2^depth)^3 (0 <= depth <= 15).  Growing always works; shrinking only while every voxel lies in the

@@ -17,6 +17,7 @@
 
 #include "vxrt.h"
 #include "vxrt_compact.h"
+#include "vxrt_components.h"
 #include "vxrt_device_edit.h"
 #include "vxrt_device_scene.h"
 #include "vxrt_edit.h"
@@ -226,6 +227,21 @@ class Context {
         size_t n = 0;
         check(vxrt_voxelize_solid_device(ctx_, verts, n_verts, tris, tri_mrgb, n_tris, fill_mrgb, uint32_t(mode), pos, mrgb, cap, &n),
               "vxrt_voxelize_solid_device");
+        return n;
+    }
+    // vxrt_components.h: the connected components of a voxel list in device memory (connectivity 6, 18 or 26): label[i] = the least
+    // index of an entry in i's component (nullptr: count only); returns the number of components
+    size_t label_components_device(const int16_t (*pos)[3], size_t n, uint32_t connectivity, uint32_t* label) {
+        size_t components = 0;
+        check(vxrt_label_components_device(ctx_, pos, n, connectivity, label, &components), "vxrt_label_components_device");
+        return components;
+    }
+    // ... and the scene's voxels whose component holds no voxel in the anchor box, as get_voxels_device gives its list; what
+    // clear_voxels_device takes to drop them
+    size_t detached_voxels_device(const std::array<int32_t, 3>& anchor_min, const std::array<int32_t, 3>& anchor_max, uint32_t connectivity,
+                                  int16_t (*pos)[3], uint8_t (*mrgb)[4], size_t cap) {
+        size_t n = 0;
+        check(vxrt_detached_voxels_device(ctx_, anchor_min.data(), anchor_max.data(), connectivity, pos, mrgb, cap, &n), "vxrt_detached_voxels_device");
         return n;
     }
     // vxrt_set_voxel_grid (vxrt_grid.h): dims[0] x dims[1] x dims[2] cells in device memory of the context's device, C order
