@@ -12,18 +12,6 @@
 #include "../../include/vxrt_device_edit.h"
 
 namespace vxrt {
-namespace {
-
-// The scratch of one labelling and what it leaves: for sorted entry i, sorted[i] is its input index and rank[i] its unique voxel;
-// for unique voxel x, comp[x] is its root and acc[comp[x]] the component's value (components.h: components_flatten).
-struct Labelling {
-    ListScratch ls;      // keys and input indices, double-buffered, and the sort's counts
-    ScratchBuffer uhead, parent, comp, acc, part;
-    const uint32_t* sorted = nullptr;
-    const uint32_t* rank = nullptr;
-    uint32_t unique = 0;
-    uint64_t components = 0;
-};
 
 // About 40 bytes per entry, all of it allocated before the first launch.
 int alloc_labelling(size_t n, const char* who, Labelling* l) {
@@ -56,6 +44,7 @@ int label_list(const int16_t* pos, uint32_t n, uint32_t axes, const CompBox& box
     HIP_TRY(launch_exclusive_scan(part, comp_blocks(mm), s));
     HIP_TRY(hipMemcpyAsync(&l->components, part + comp_blocks(mm), sizeof l->components, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
+    l->ukeys = ukeys;
     l->sorted = vp[cur];
     l->rank = rank;
     l->unique = mm;
@@ -65,7 +54,6 @@ int label_list(const int16_t* pos, uint32_t n, uint32_t axes, const CompBox& box
 // 6, 18, 26 -> the axes on which two neighbours may differ; anything else -> 0
 uint32_t axes_of(uint32_t connectivity) { return connectivity == 6u ? 1u : connectivity == 18u ? 2u : connectivity == 26u ? 3u : 0u; }
 
-}  // namespace
 }  // namespace vxrt
 
 extern "C" {

@@ -5,6 +5,9 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "ctx.h"
+#include "device_build.h"
+
 namespace vxrt {
 
 // Every kernel here runs blocks of kCompThreads threads over kCompSpan consecutive entries each, kCompItems rounds of one entry per
@@ -54,5 +57,29 @@ hipError_t components_scatter(const uint32_t* vals, const uint32_t* rank, uint32
 hipError_t components_select_count(const uint32_t* flag, uint32_t n, uint64_t* part, hipStream_t s);
 hipError_t components_select_write(const uint32_t* flag, uint32_t n, const uint64_t* part, const int16_t* src_pos, const uint32_t* src_mrgb,
                                    int16_t* dst_pos, uint32_t* dst_mrgb, hipStream_t s);
+
+// ---- api_components.hip: the labelling that vxrt_components.h's calls and vxrt_pieces.h's (api_pieces.hip) share ----------------------
+// The scratch of one labelling and what it leaves: for sorted entry i, sorted[i] is its input index and rank[i] its unique voxel;
+// for unique voxel x in key order, ukeys[x] is its path key, uhead[x] the least input index at its position, comp[x] its root and
+// acc[comp[x]] the component's value (components_flatten); part holds the flatten's root counts, scanned: part[b] = the roots before
+// block b, part[comp_blocks(unique)] = components.
+struct Labelling {
+    ListScratch ls;      // keys and input indices, double-buffered, and the sort's counts
+    ScratchBuffer uhead, parent, comp, acc, part;
+    const uint64_t* ukeys = nullptr;
+    const uint32_t* sorted = nullptr;
+    const uint32_t* rank = nullptr;
+    uint32_t unique = 0;
+    uint64_t components = 0;
+};
+
+// About 40 bytes per entry, all of it allocated before the first launch.
+int alloc_labelling(size_t n, const char* who, Labelling* l);
+
+// pos[0 .. n), 0 < n < 2^32, read on s -> *l.  axes: 1, 2 or 3.  Waits for the two counts.
+int label_list(const int16_t* pos, uint32_t n, uint32_t axes, const CompBox& box, hipStream_t s, Labelling* l);
+
+// 6, 18, 26 -> the axes on which two neighbours may differ; anything else -> 0
+uint32_t axes_of(uint32_t connectivity);
 
 }  // namespace vxrt

@@ -971,6 +971,101 @@ class Context:
             self.clear_voxels_device(pos)
         return pos, mrgb
 
+    PIECE_BYTES = 48      # sizeof(vxrt_piece), include/vxrt_pieces.h
+
+    @staticmethod
+    def _piece_table(raw, k):
+        """raw: a uint8 device tensor holding k vxrt_piece -> the table, a dict of device tensors, one per field"""
+        import torch
+        rows = raw[:k * Context.PIECE_BYTES].view(k, Context.PIECE_BYTES)
+
+        def field(lo, hi, dtype, shape):
+            return rows[:, lo:hi].contiguous().view(dtype).reshape(shape)
+        return {"first": field(0, 4, torch.uint32, (k,)), "voxels": field(4, 8, torch.uint32, (k,)),
+                "min": field(8, 14, torch.int16, (k, 3)), "max": field(14, 20, torch.int16, (k, 3)),
+                "sum": field(24, 48, torch.int64, (k, 3))}
+
+    def component_table(self, pos, connectivity=6):
+        """vxrt_component_table_device (include/vxrt_pieces.h): label_components' labelling and with it the components' table ->
+        (label, id, table).  label and id are uint32 [n] tensors on the context's device: label[i] is the least index of an entry in
+        i's component, id[i] the component's number, components being numbered 0 .. k-1 by ascending label.  table is a dict of device
+        tensors with one row per component: first (uint32 [k], the label), voxels (uint32 [k]), min and max (int16 [k,3], inclusive)
+        and sum (int64 [k,3]), all over the component's distinct positions; the centroid is sum / voxels.  pos as label_components
+        takes it.  Two calls: one to count the components, one into tensors of exactly that size."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        conn = self._connectivity(connectivity)
+        pos, _ = self._device_list(pos, None, clear=True)
+        n = len(pos)
+        label, ids = torch.empty(n, dtype=torch.uint32, device=dev), torch.empty(n, dtype=torch.uint32, device=dev)
+        got = C.c_size_t(0)
+        k = 0
+        raw = torch.empty(0, dtype=torch.uint8, device=dev)
+        if n:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            self.context_wait_stream(stream)
+            args = (self._h, C.c_void_p(pos.data_ptr()), C.c_size_t(n), conn)
+            self._chk(self._L.vxrt_component_table_device(*args, None, None, None, C.c_size_t(0), C.byref(got)), "vxrt_component_table_device")
+            k = int(got.value)
+            raw = torch.empty(k * self.PIECE_BYTES, dtype=torch.uint8, device=dev)
+            self.context_wait_stream(stream)      # the allocator may hand out memory that work on torch's stream still uses
+            self._chk(self._L.vxrt_component_table_device(*args, C.c_void_p(label.data_ptr()), C.c_void_p(ids.data_ptr()),
+                                                          C.c_void_p(raw.data_ptr()), C.c_size_t(k), C.byref(got)), "vxrt_component_table_device")
+            self.stream_wait_context(stream)
+        return label, ids, self._piece_table(raw, k)
+
+    def detached_pieces(self, anchor_min, anchor_max, connectivity=6, min_voxels=0, max_voxels=None, cap=None):
+        """vxrt_detached_pieces_device (include/vxrt_pieces.h): the detached pieces of the scene as it stands -> (pos, mrgb, piece,
+        table).  A component (by connectivity 6, 18 or 26, over the whole scene) is selected when it holds no voxel in the half-open
+        box [anchor_min, anchor_max) and min_voxels <= its voxels <= max_voxels (max_voxels=None: no upper limit; min_voxels >
+        max_voxels selects nothing).  pos (int16 [n,3]) and mrgb (uint8 [n,4]) are the selected components' voxels in the order and
+        with the bytes of get_voxels, piece (uint32 [n]) each voxel's piece number, pieces being numbered by their first voxel in
+        that order, and table as component_table gives it for pos, so table["first"][p] is the index in pos of piece p's first voxel.
+        cap=None: two calls, one to count and one into tensors of exactly that size.  cap=k: one call into tensors with room for k
+        voxels and k pieces, cut to the counts; more than k voxels is an error (VXRT_E_INVALID)."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        conn = self._connectivity(connectivity)
+        if cap is not None and (not isinstance(cap, (int, np.integer)) or isinstance(cap, bool) or cap < 0):
+            raise ValueError("cap must be a count of voxels")
+        if max_voxels is None:
+            max_voxels = 0xFFFFFFFF
+        for v in (min_voxels, max_voxels):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= int(v) <= 0xFFFFFFFF:
+                raise ValueError("min_voxels and max_voxels must be uint32 counts of voxels")
+        if anchor_min is None or anchor_max is None:
+            raise ValueError("anchor_min and anchor_max: three integers each")
+        lo, hi = self._box(anchor_min, anchor_max)
+        head = (self._h, _p(lo), _p(hi), conn, C.c_uint32(int(min_voxels)), C.c_uint32(int(max_voxels)))
+        got, pieces = C.c_size_t(0), C.c_size_t(0)
+        if cap is None:
+            self._chk(self._L.vxrt_detached_pieces_device(*head, None, None, None, C.c_size_t(0), C.byref(got), None, C.c_size_t(0),
+                                                          C.byref(pieces)), "vxrt_detached_pieces_device")
+            cap, info_cap = int(got.value), int(pieces.value)
+        else:
+            cap = info_cap = int(cap)
+        pos, mrgb = torch.empty((cap, 3), dtype=torch.int16, device=dev), torch.empty((cap, 4), dtype=torch.uint8, device=dev)
+        piece = torch.empty(cap, dtype=torch.uint32, device=dev)
+        raw = torch.empty(info_cap * self.PIECE_BYTES, dtype=torch.uint8, device=dev)
+        if cap:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            self.context_wait_stream(stream)      # the allocator may hand out memory that work on torch's stream still uses
+            self._chk(self._L.vxrt_detached_pieces_device(*head, C.c_void_p(pos.data_ptr()), C.c_void_p(mrgb.data_ptr()), C.c_void_p(piece.data_ptr()),
+                                                          C.c_size_t(cap), C.byref(got), C.c_void_p(raw.data_ptr()), C.c_size_t(info_cap),
+                                                          C.byref(pieces)), "vxrt_detached_pieces_device")
+            self.stream_wait_context(stream)
+        n, k = int(got.value), int(pieces.value)
+        return pos[:n], mrgb[:n], piece[:n], self._piece_table(raw, k)
+
+    def drop_detached_pieces(self, anchor_min, anchor_max, connectivity=6, min_voxels=0, max_voxels=None, cap=None):
+        """detached_pieces, then clear_voxels_device of its list: the detached pieces within the size range are removed from the
+        loaded scene in place; the others stay.  Returns detached_pieces' four values, which a host re-emits as debris piece by piece."""
+        pos, mrgb, piece, table = self.detached_pieces(anchor_min, anchor_max, connectivity=connectivity, min_voxels=min_voxels,
+                                                       max_voxels=max_voxels, cap=cap)
+        if len(pos):
+            self.clear_voxels_device(pos)
+        return pos, mrgb, piece, table
+
     def set_scene_depth(self, depth):
         """vxrt_set_scene_depth (include/vxrt_scene_depth.h): change the octree depth of the scene in place, on the device; the root
         cube becomes [-2^depth, 2^depth)^3 (0 <= depth <= 15).  Growing always works; shrinking only while every voxel lies in the

@@ -25,6 +25,7 @@
 #include "vxrt_grid.h"
 #include "vxrt_grid_edit.h"
 #include "vxrt_host.h"
+#include "vxrt_pieces.h"
 #include "vxrt_scene_depth.h"
 #include "vxrt_solid.h"
 #include "vxrt_voxelize.h"
@@ -243,6 +244,25 @@ class Context {
         size_t n = 0;
         check(vxrt_detached_voxels_device(ctx_, anchor_min.data(), anchor_max.data(), connectivity, pos, mrgb, cap, &n), "vxrt_detached_voxels_device");
         return n;
+    }
+    // vxrt_pieces.h: the table of a list's components: label and id per entry, info per component (each may be nullptr; info has
+    // room for info_cap entries); returns the number of components
+    size_t component_table_device(const int16_t (*pos)[3], size_t n, uint32_t connectivity, uint32_t* label, uint32_t* id, vxrt_piece* info,
+                                  size_t info_cap) {
+        size_t components = 0;
+        check(vxrt_component_table_device(ctx_, pos, n, connectivity, label, id, info, info_cap, &components), "vxrt_component_table_device");
+        return components;
+    }
+    // ... and the scene's detached pieces of min_voxels .. max_voxels voxels: their voxels as detached_voxels_device gives them, each
+    // one's piece number, and info per piece; returns {voxels, pieces}
+    std::pair<size_t, size_t> detached_pieces_device(const std::array<int32_t, 3>& anchor_min, const std::array<int32_t, 3>& anchor_max,
+                                                     uint32_t connectivity, uint32_t min_voxels, uint32_t max_voxels, int16_t (*pos)[3],
+                                                     uint8_t (*mrgb)[4], uint32_t* piece, size_t cap, vxrt_piece* info, size_t info_cap) {
+        size_t n = 0, pieces = 0;
+        check(vxrt_detached_pieces_device(ctx_, anchor_min.data(), anchor_max.data(), connectivity, min_voxels, max_voxels, pos, mrgb, piece, cap, &n,
+                                          info, info_cap, &pieces),
+              "vxrt_detached_pieces_device");
+        return {n, pieces};
     }
     // vxrt_set_voxel_grid (vxrt_grid.h): dims[0] x dims[1] x dims[2] cells in device memory of the context's device, C order
     // [x][y][z], cell (i, j, k) at origin + (i, j, k); palette: 256 entries for VXRT_GRID_PALETTE8, nullptr for VXRT_GRID_WORD32
