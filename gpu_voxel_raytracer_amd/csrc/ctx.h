@@ -12,6 +12,7 @@
 //   api_device_scene.hip  a scene built on the device from a voxel list in device memory (vxrt_device_scene.h)
 //   api_scene_depth.hip   the octree depth of a loaded scene changed in place (vxrt_scene_depth.h)
 //   api_compact.hip  an edited scene re-laid as a fresh build lies, and the storage counts (vxrt_compact.h)
+//   api_query.hip    voxel lookups and bounded ray casts against the scene from device memory (vxrt_query.h)
 #pragma once
 #include <hip/hip_runtime.h>
 

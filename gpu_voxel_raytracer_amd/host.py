@@ -1111,6 +1111,105 @@ class Context:
         self._chk(self._L.vxrt_pick(self._h, _p(o), _p(d), C.c_size_t(len(o)), _p(out)), "vxrt_pick")
         return {name: out[name].copy() for name in PICK_HIT_DTYPE.names}
 
+    def _query_check(self, a, name, dtype, width):
+        """An argument of the device queries is a tensor of the context's device or a numpy array, [n, width] (or [n] for width 0):
+        another type, dtype, shape or device is refused, and a tensor that is not contiguous.  Nothing is uploaded or called."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        if not isinstance(a, (np.ndarray, torch.Tensor)):
+            raise TypeError(f"{name} must be a torch tensor or a numpy array")
+        np_dtype = np.dtype(str(dtype).split(".")[1])
+        if (a.dtype != np_dtype) if isinstance(a, np.ndarray) else (a.dtype != dtype):
+            raise ValueError(f"{name} must be {np_dtype}")
+        if (a.ndim != 2 or a.shape[1] != width) if width else a.ndim != 1:
+            raise ValueError(f"{name} must be [n,{width}]" if width else f"{name} must be [n]")
+        if isinstance(a, torch.Tensor):
+            if not a.is_contiguous():
+                raise ValueError(f"{name} must be contiguous")
+            if a.device != dev:
+                raise ValueError(f"{name} must be on {dev}")
+
+    def _query_tensor(self, a):
+        """A checked argument on the context's device: a numpy array goes there with torch."""
+        import torch
+        return torch.as_tensor(np.ascontiguousarray(a), device=torch.device("cuda", self.device)) if isinstance(a, np.ndarray) else a
+
+    @staticmethod
+    def _query_offset(offset):
+        if offset is None:
+            return None
+        try:
+            o = [int(v) for v in np.asarray(offset).reshape(-1).tolist()]
+            exact = [float(v) for v in np.asarray(offset, np.float64).reshape(-1).tolist()] == [float(v) for v in o]
+        except (TypeError, ValueError):
+            raise ValueError("offset must be three integers") from None
+        if len(o) != 3 or not exact or not all(-2 ** 31 <= v < 2 ** 31 for v in o):
+            raise ValueError("offset must be three integers of the int32 range")
+        return (C.c_int32 * 3)(*o)
+
+    def _lookup(self, pos, offset, words):
+        import torch
+        dev = torch.device("cuda", self.device)
+        self._query_check(pos, "pos", torch.int16, 3)
+        off = self._query_offset(offset)
+        pos = self._query_tensor(pos)
+        leaf = torch.empty(len(pos), dtype=torch.int32, device=dev) if words else None
+        got = C.c_size_t(0)
+        if len(pos):
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            self.context_wait_stream(stream)
+            self._chk(self._L.vxrt_lookup_voxels_device(self._h, C.c_void_p(pos.data_ptr()), C.c_size_t(len(pos)), off,
+                                                        C.c_void_p(leaf.data_ptr()) if words else None, C.byref(got)), "vxrt_lookup_voxels_device")
+            self.stream_wait_context(stream)
+        return leaf, int(got.value)
+
+    def lookup_voxels(self, pos, offset=None):
+        """vxrt_lookup_voxels_device (include/vxrt_query.h): the scene's leaf word at pos[i] + offset per entry -> (leaf, n_present),
+        leaf an int32 [n] torch tensor on the context's device: the word vxrt_pick reports (0x80000000 | material << 24 | rgb), or 0
+        where the scene has no voxel or the position lies outside the root cube; n_present the number of nonzero words.  pos (int16
+        [n,3]) is a contiguous torch tensor on the context's device, or a numpy array, which is uploaded with torch first; offset
+        is None or three integers of the int32 range, added without wrap.  Ordered on both sides against torch's current stream."""
+        return self._lookup(pos, offset, True)
+
+    def count_present(self, pos, offset=None):
+        """lookup_voxels, counting only (the collision test): how many of pos + offset the scene holds."""
+        return self._lookup(pos, offset, False)[1]
+
+    def pick_device(self, origins, dirs, max_time=None):
+        """vxrt_pick_device (include/vxrt_query.h): pick with the rays (float32 [n,3] contiguous torch tensors on the context's device,
+        or numpy arrays, which are uploaded with torch first) and the hits in device memory, each ray bounded by max_time (float32
+        [n], or a Python float for all rays; None: unbounded, the bytes of pick) -> dict of torch tensors status (uint32), time,
+        normal [n,3], voxel [n,3], leaf, all views of one int32 [n,9] buffer of vxrt_pick_hit records.  Ordered on both sides
+        against torch's current stream; does not wait for the context's other work."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        self._query_check(origins, "origins", torch.float32, 3)
+        self._query_check(dirs, "dirs", torch.float32, 3)
+        if len(origins) != len(dirs):
+            raise ValueError("one direction per origin")
+        scalar = isinstance(max_time, (int, float, np.floating, np.integer)) and not isinstance(max_time, bool)
+        if max_time is not None and not scalar:
+            self._query_check(max_time, "max_time", torch.float32, 0)
+            if len(max_time) != len(origins):
+                raise ValueError("one max_time per ray")
+        o, d = self._query_tensor(origins), self._query_tensor(dirs)
+        if max_time is None:
+            t = None
+        elif scalar:
+            t = torch.full((len(o),), float(max_time), dtype=torch.float32, device=dev)
+        else:
+            t = self._query_tensor(max_time)
+        out = torch.empty((len(o), PICK_HIT_DTYPE.itemsize // 4), dtype=torch.int32, device=dev)   # every record is written
+        if len(o):
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            self.context_wait_stream(stream)
+            self._chk(self._L.vxrt_pick_device(self._h, C.c_void_p(o.data_ptr()), C.c_void_p(d.data_ptr()),
+                                               C.c_void_p(t.data_ptr()) if t is not None else None, C.c_size_t(len(o)),
+                                               C.c_void_p(out.data_ptr())), "vxrt_pick_device")
+            self.stream_wait_context(stream)
+        return {"status": out[:, 0].view(torch.uint32), "time": out[:, 1].view(torch.float32), "normal": out[:, 2:5].view(torch.float32),
+                "voxel": out[:, 5:8], "leaf": out[:, 8]}
+
     def _box(self, box_min, box_max):
         if (box_min is None) != (box_max is None):
             raise ValueError("box_min and box_max: both or neither")

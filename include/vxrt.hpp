@@ -26,6 +26,7 @@
 #include "vxrt_grid_edit.h"
 #include "vxrt_host.h"
 #include "vxrt_pieces.h"
+#include "vxrt_query.h"
 #include "vxrt_scene_depth.h"
 #include "vxrt_solid.h"
 #include "vxrt_voxelize.h"
@@ -263,6 +264,17 @@ class Context {
                                           info, info_cap, &pieces),
               "vxrt_detached_pieces_device");
         return {n, pieces};
+    }
+    // vxrt_query.h: the scene's leaf word at pos[i] + offset per entry (0: no voxel there, or outside the root cube), everything in
+    // device memory; leaf == nullptr counts only (the collision test).  Returns the number of nonzero answers.
+    size_t lookup_voxels_device(const int16_t (*pos)[3], size_t n, const std::array<int32_t, 3>& offset, uint32_t* leaf) {
+        size_t present = 0;
+        check(vxrt_lookup_voxels_device(ctx_, pos, n, offset.data(), leaf, &present), "vxrt_lookup_voxels_device");
+        return present;
+    }
+    // ... and pick with rays and hits in device memory, each ray bounded by max_time[i] (nullptr: unbounded, the bytes of pick)
+    void pick_device(const float (*origins)[3], const float (*dirs)[3], const float* max_time, size_t n, vxrt_pick_hit* out) {
+        check(vxrt_pick_device(ctx_, origins, dirs, max_time, n, out), "vxrt_pick_device");
     }
     // vxrt_set_voxel_grid (vxrt_grid.h): dims[0] x dims[1] x dims[2] cells in device memory of the context's device, C order
     // [x][y][z], cell (i, j, k) at origin + (i, j, k); palette: 256 entries for VXRT_GRID_PALETTE8, nullptr for VXRT_GRID_WORD32
