@@ -8,6 +8,7 @@
 
 #include "ctx.h"
 #include "edit.h"
+#include "query.h"
 #include "scene_args.h"
 
 namespace vxrt {
@@ -292,15 +293,7 @@ int vxrt_pick(vxrt_ctx* c, const float (*origins)[3], const float (*dirs)[3], si
     HIP_TRY(b_out.alloc(n * sizeof(vxrt_pick_hit)));
     HIP_TRY(hipMemcpy(b_o.p, origins, n * 12, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(b_d.p, dirs, n * 12, hipMemcpyHostToDevice));
-    TraceArgs a{};   // as vxrt_debug_cast_rays builds it, 8-byte records only
-    a.svo = c->d_svo;
-    a.leaves = c->d_leaves;
-    a.root_rec = c->root_rec;
-    a.node_levels = int(c->depth) + 1;
-    memcpy(a.root_center, c->root_center, sizeof a.root_center);
-    a.root_size = c->root_size;
-    a.stack_levels = c->depth < 1 ? 1 : int(c->depth);
-    HIP_TRY(launch_pick(a, b_o.as<float>(), b_d.as<float>(), b_out.as<vxrt_pick_hit>(), unsigned(n), c->stream));
+    HIP_TRY(launch_query_pick(pick_args(c), b_o.as<float>(), b_d.as<float>(), nullptr, b_out.as<vxrt_pick_hit>(), unsigned(n), c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     HIP_TRY(hipMemcpy(out, b_out.p, n * sizeof(vxrt_pick_hit), hipMemcpyDeviceToHost));
     return VXRT_OK;

@@ -1,7 +1,8 @@
 // api_pieces.hip — host side of vxrt_pieces.h: the table of a voxel list's connected components (size, bounding box, coordinate sums,
-// number) and the detached pieces of the loaded scene.  The labelling is api_components.hip's (components.h: label_list), unchanged;
-// what follows it is pieces.hip plus the selection kernels of components.hip.  Nothing but counts crosses to the host: the
-// labelling's two, and for the scene call the scene's, the selected voxels and the selected pieces.  DESIGN.md §21.
+// number) and the detached pieces of the loaded scene, and with them the bodies of vxrt_components.h's two calls, which ask for less
+// of the same (pieces.h).  The labelling is api_components.hip's (components.h: label_list); what follows it is pieces.hip plus the
+// scatter and selection kernels of components.hip.  Nothing but counts crosses to the host: the labelling's two, and for the scene
+// calls the scene's, the selected voxels and the selected pieces.  DESIGN.md §20, §21.
 #include <algorithm>
 #include <string>
 
@@ -30,15 +31,20 @@ int mark_pieces(Labelling* l, uint32_t n, uint32_t min_voxels, uint32_t max_voxe
 
 size_t table_bytes(size_t entries, uint64_t at_most) { return size_t(std::min<uint64_t>(entries, at_most)) * sizeof(vxrt_piece); }
 
+// The loaded scene's voxel list, in path order, into scratch: counted, then decoded (vxrt_get_voxels_device).  *total == 0: no list.
+int scene_list(vxrt_ctx* c, const char* who, ScratchBuffer* pos, ScratchBuffer* mrgb, size_t* total) {
+    if (int rc = vxrt_get_voxels_device(c, nullptr, nullptr, nullptr, nullptr, 0, total)) return rc;
+    if (*total == 0) return VXRT_OK;
+    if (int rc = alloc_scratch(pos, *total * 3 * sizeof(int16_t), who, "the scene's positions")) return rc;
+    if (int rc = alloc_scratch(mrgb, *total * 4, who, "the scene's mrgb words")) return rc;
+    size_t got = 0;
+    return vxrt_get_voxels_device(c, nullptr, nullptr, reinterpret_cast<int16_t(*)[3]>(pos->p), reinterpret_cast<uint8_t(*)[4]>(mrgb->p), *total, &got);
+}
+
 }  // namespace
-}  // namespace vxrt
 
-extern "C" {
-
-int vxrt_component_table_device(vxrt_ctx* c, const int16_t (*pos)[3], size_t n, uint32_t connectivity, uint32_t* label, uint32_t* id,
-                                vxrt_piece* info, size_t info_cap, size_t* n_components) try {
-    using namespace vxrt;
-    const char* who = "vxrt_component_table_device";
+int component_table(const char* who, vxrt_ctx* c, const int16_t (*pos)[3], size_t n, uint32_t connectivity, uint32_t* label, uint32_t* id,
+                    vxrt_piece* info, size_t info_cap, size_t* n_components) {
     if (!valid_ctx(c) || !n_components) { set_error("null argument"); return VXRT_E_INVALID; }
     if (uint64_t(n) >= (uint64_t(1) << 32)) { set_error(std::string(who) + ": 2^32 voxels or more"); return VXRT_E_INVALID; }
     const uint32_t axes = axes_of(connectivity);
@@ -68,7 +74,7 @@ int vxrt_component_table_device(vxrt_ctx* c, const int16_t (*pos)[3], size_t n, 
         set_error(std::string(who) + ": " + std::to_string(l.components) + " components, room for " + std::to_string(info_cap));
         return VXRT_E_INVALID;
     }
-    if (!id && !info) {            // vxrt_label_components_device's route
+    if (!id && !info) {            // labels only (vxrt_label_components_device asks for no more): no accumulators
         if (label) {
             HIP_TRY(components_scatter(l.sorted, l.rank, nn, l.comp.as<uint32_t>(), l.acc.as<uint32_t>(), 0u, label, s));
             HIP_TRY(hipStreamSynchronize(s));
@@ -88,14 +94,12 @@ int vxrt_component_table_device(vxrt_ctx* c, const int16_t (*pos)[3], size_t n, 
     HIP_TRY(pieces_scatter(l.sorted, l.rank, nn, l.comp.as<uint32_t>(), l.parent.as<uint32_t>(), pa, label, id, s));
     HIP_TRY(hipStreamSynchronize(s));
     return VXRT_OK;
-} VXRT_CATCH
+}
 
-int vxrt_detached_pieces_device(vxrt_ctx* c, const int32_t anchor_min[3], const int32_t anchor_max[3], uint32_t connectivity, uint32_t min_voxels,
-                                uint32_t max_voxels, int16_t (*pos)[3], uint8_t (*mrgb)[4], uint32_t* piece, size_t cap, size_t* n, vxrt_piece* info,
-                                size_t info_cap, size_t* n_pieces) try {
-    using namespace vxrt;
-    const char* who = "vxrt_detached_pieces_device";
-    if (!valid_ctx(c) || !n || !n_pieces) { set_error("null argument"); return VXRT_E_INVALID; }
+int detached_pieces(const char* who, vxrt_ctx* c, const int32_t anchor_min[3], const int32_t anchor_max[3], uint32_t connectivity,
+                    uint32_t min_voxels, uint32_t max_voxels, int16_t (*pos)[3], uint8_t (*mrgb)[4], uint32_t* piece, size_t cap, size_t* n,
+                    vxrt_piece* info, size_t info_cap, size_t* n_pieces) {
+    if (!valid_ctx(c) || !n) { set_error("null argument"); return VXRT_E_INVALID; }
     if (!anchor_min || !anchor_max) { set_error(std::string(who) + ": null anchor box"); return VXRT_E_INVALID; }
     const uint32_t axes = axes_of(connectivity);
     if (axes == 0u) { set_error(std::string(who) + ": connectivity " + std::to_string(connectivity) + " (6, 18 or 26)"); return VXRT_E_INVALID; }
@@ -116,44 +120,52 @@ int vxrt_detached_pieces_device(vxrt_ctx* c, const int32_t anchor_min[3], const 
     if (info && info_cap != 0)      // a scene holds fewer than 2^32 voxels, so fewer pieces
         if (int rc = check_device_array(c, info, table_bytes(info_cap, uint64_t(1) << 32), who, "info")) return rc;
 
-    // the scene's list, in path order, into scratch: counted, then decoded
     size_t total = 0;
-    if (int rc = vxrt_get_voxels_device(c, nullptr, nullptr, nullptr, nullptr, 0, &total)) return rc;
-    if (total == 0) { *n = 0; *n_pieces = 0; return VXRT_OK; }
+    ScratchBuffer spos, smrgb, flags, mark_part, accs;
+    if (int rc = scene_list(c, who, &spos, &smrgb, &total)) return rc;
+    if (total == 0) {
+        *n = 0;
+        if (n_pieces) *n_pieces = 0;
+        return VXRT_OK;
+    }
     const uint32_t nn = uint32_t(total);   // a scene holds fewer than 2^32 leaf words
-    ScratchBuffer spos, smrgb, pick, mark_part;
     Labelling l;
-    if (int rc = alloc_scratch(&spos, total * 3 * sizeof(int16_t), who, "the scene's positions")) return rc;
-    if (int rc = alloc_scratch(&smrgb, total * 4, who, "the scene's mrgb words")) return rc;
-    if (int rc = alloc_scratch(&pick, total * sizeof(uint32_t), who, "the flags")) return rc;
-    if (int rc = alloc_scratch(&mark_part, (size_t(comp_blocks(total)) + 1) * sizeof(uint64_t), who, "the scan partials")) return rc;
+    if (int rc = alloc_scratch(&flags, total * sizeof(uint32_t), who, "the flags")) return rc;
+    if (n_pieces)
+        if (int rc = alloc_scratch(&mark_part, (size_t(comp_blocks(total)) + 1) * sizeof(uint64_t), who, "the scan partials")) return rc;
     if (int rc = alloc_labelling(total, who, &l)) return rc;
-    size_t got = 0;
-    if (int rc = vxrt_get_voxels_device(c, nullptr, nullptr, reinterpret_cast<int16_t(*)[3]>(spos.p), reinterpret_cast<uint8_t(*)[4]>(smrgb.p), total, &got))
-        return rc;
 
     hipStream_t s = c->stream;
     CompBox box{};
     for (int ax = 0; ax < 3; ax++) { box.lo[ax] = anchor_min[ax]; box.hi[ax] = anchor_max[ax]; }
     box.on = 1u;
     if (int rc = label_list(spos.as<int16_t>(), nn, axes, box, s, &l)) return rc;
-    ScratchBuffer accs;
-    if (int rc = reduce_pieces(&l, 1u, who, &accs, s)) return rc;
-    PieceAcc* pa = accs.as<PieceAcc>();
-    if (int rc = mark_pieces(&l, nn, min_voxels, max_voxels, pa, s)) return rc;
-    const uint32_t* mark = l.uhead.as<uint32_t>();
+    // pick[i] != 0: entry i of the scene's list is returned
+    uint32_t* pick = flags.as<uint32_t>();
+    PieceAcc* pa = nullptr;
+    const uint32_t* mark = nullptr;
+    if (!n_pieces) {      // every detached voxel: the flatten's anchor marks decide, no accumulators
+        HIP_TRY(components_scatter(l.sorted, l.rank, nn, l.comp.as<uint32_t>(), l.acc.as<uint32_t>(), 1u, pick, s));
+    } else {              // the detached components within the size range
+        if (int rc = reduce_pieces(&l, 1u, who, &accs, s)) return rc;
+        pa = accs.as<PieceAcc>();
+        if (int rc = mark_pieces(&l, nn, min_voxels, max_voxels, pa, s)) return rc;
+        mark = l.uhead.as<uint32_t>();
+        HIP_TRY(pieces_pick(l.sorted, l.rank, nn, l.comp.as<uint32_t>(), l.parent.as<uint32_t>(), pa, pick, s));
+    }
     uint64_t* part = l.part.as<uint64_t>();      // the slots have read the root counts
-    HIP_TRY(pieces_pick(l.sorted, l.rank, nn, l.comp.as<uint32_t>(), l.parent.as<uint32_t>(), pa, pick.as<uint32_t>(), s));
-    HIP_TRY(components_select_count(pick.as<uint32_t>(), nn, part, s));
-    HIP_TRY(launch_exclusive_scan(part, comp_blocks(nn), s));
-    HIP_TRY(components_select_count(mark, nn, mark_part.as<uint64_t>(), s));
-    HIP_TRY(launch_exclusive_scan(mark_part.as<uint64_t>(), comp_blocks(nn), s));
     uint64_t count = 0, pieces = 0;
+    HIP_TRY(components_select_count(pick, nn, part, s));
+    HIP_TRY(launch_exclusive_scan(part, comp_blocks(nn), s));
+    if (n_pieces) {
+        HIP_TRY(components_select_count(mark, nn, mark_part.as<uint64_t>(), s));
+        HIP_TRY(launch_exclusive_scan(mark_part.as<uint64_t>(), comp_blocks(nn), s));
+    }
     HIP_TRY(hipMemcpyAsync(&count, part + comp_blocks(nn), sizeof count, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(&pieces, mark_part.as<uint64_t>() + comp_blocks(nn), sizeof pieces, hipMemcpyDeviceToHost, s));
+    if (n_pieces) HIP_TRY(hipMemcpyAsync(&pieces, mark_part.as<uint64_t>() + comp_blocks(nn), sizeof pieces, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     *n = size_t(count);
-    *n_pieces = size_t(pieces);
+    if (n_pieces) *n_pieces = size_t(pieces);
     if (count_only || count == 0) return VXRT_OK;
     if ((pos || piece) && cap < count) {
         set_error(std::string(who) + ": " + std::to_string(count) + " voxels, room for " + std::to_string(cap));
@@ -163,28 +175,34 @@ int vxrt_detached_pieces_device(vxrt_ctx* c, const int32_t anchor_min[3], const 
         set_error(std::string(who) + ": " + std::to_string(pieces) + " pieces, room for " + std::to_string(info_cap));
         return VXRT_E_INVALID;
     }
-    // pos and mrgb are written in place where the kernel's stores fit the arrays' alignment (2 bytes per coordinate, 4 per mrgb
-    // word); otherwise staged and copied
-    const bool direct = (reinterpret_cast<uintptr_t>(pos) & 1u) == 0u && (reinterpret_cast<uintptr_t>(mrgb) & 3u) == 0u;
-    ScratchBuffer dpos, dmrgb;
-    if (pos && !direct) {
-        if (int rc = alloc_scratch(&dpos, size_t(count) * 3 * sizeof(int16_t), who, "the positions")) return rc;
-        if (int rc = alloc_scratch(&dmrgb, size_t(count) * 4, who, "the mrgb words")) return rc;
-    }
-    HIP_TRY(pieces_number(mark, nn, mark_part.as<uint64_t>(), pick.as<uint32_t>(), part, pa, s));
-    if (pos) {
-        HIP_TRY(components_select_write(pick.as<uint32_t>(), nn, part, spos.as<int16_t>(), smrgb.as<uint32_t>(),
-                                        direct ? reinterpret_cast<int16_t*>(pos) : dpos.as<int16_t>(),
-                                        direct ? reinterpret_cast<uint32_t*>(mrgb) : dmrgb.as<uint32_t>(), s));
-        if (!direct) {
-            HIP_TRY(hipMemcpyAsync(pos, dpos.p, size_t(count) * 3 * sizeof(int16_t), hipMemcpyDeviceToDevice, s));
-            HIP_TRY(hipMemcpyAsync(mrgb, dmrgb.p, size_t(count) * 4, hipMemcpyDeviceToDevice, s));
-        }
-    }
-    if (piece) HIP_TRY(pieces_write(pick.as<uint32_t>(), nn, part, pa, piece, s));
+    if (n_pieces) HIP_TRY(pieces_number(mark, nn, mark_part.as<uint64_t>(), pick, part, pa, s));
+    ScratchBuffer stage[2];
+    if (pos)
+        if (int rc = write_voxels_staged(pos, mrgb, size_t(count), s, who, stage, [&](int16_t* dst_pos, uint32_t* dst_mrgb) {
+                return components_select_write(pick, nn, part, spos.as<int16_t>(), smrgb.as<uint32_t>(), dst_pos, dst_mrgb, s);
+            }))
+            return rc;
+    if (piece) HIP_TRY(pieces_write(pick, nn, part, pa, piece, s));
     if (info) HIP_TRY(pieces_emit(pa, uint32_t(l.components), 1u, info, s));
     HIP_TRY(hipStreamSynchronize(s));
     return VXRT_OK;
+}
+
+}  // namespace vxrt
+
+extern "C" {
+
+int vxrt_component_table_device(vxrt_ctx* c, const int16_t (*pos)[3], size_t n, uint32_t connectivity, uint32_t* label, uint32_t* id,
+                                vxrt_piece* info, size_t info_cap, size_t* n_components) try {
+    return vxrt::component_table("vxrt_component_table_device", c, pos, n, connectivity, label, id, info, info_cap, n_components);
+} VXRT_CATCH
+
+int vxrt_detached_pieces_device(vxrt_ctx* c, const int32_t anchor_min[3], const int32_t anchor_max[3], uint32_t connectivity, uint32_t min_voxels,
+                                uint32_t max_voxels, int16_t (*pos)[3], uint8_t (*mrgb)[4], uint32_t* piece, size_t cap, size_t* n, vxrt_piece* info,
+                                size_t info_cap, size_t* n_pieces) try {
+    if (!n_pieces) { vxrt::set_error("null argument"); return VXRT_E_INVALID; }
+    return vxrt::detached_pieces("vxrt_detached_pieces_device", c, anchor_min, anchor_max, connectivity, min_voxels, max_voxels, pos, mrgb, piece, cap,
+                                 n, info, info_cap, n_pieces);
 } VXRT_CATCH
 
 }  // extern "C"

@@ -82,15 +82,7 @@ int vxrt_pick_device(vxrt_ctx* c, const float (*origins)[3], const float (*dirs)
             if (int rc = check_device_array(c, v.p, v.bytes, who, v.what)) return rc;
     if (!c->has_scene) { set_error("no scene set"); return VXRT_E_NOSCENE; }
 
-    TraceArgs a{};   // as vxrt_pick builds it, 8-byte records only
-    a.svo = c->d_svo;
-    a.leaves = c->d_leaves;
-    a.root_rec = c->root_rec;
-    a.node_levels = int(c->depth) + 1;
-    memcpy(a.root_center, c->root_center, sizeof a.root_center);
-    a.root_size = c->root_size;
-    a.stack_levels = c->depth < 1 ? 1 : int(c->depth);
-    HIP_TRY(launch_query_pick(a, reinterpret_cast<const float*>(origins), reinterpret_cast<const float*>(dirs), max_time, out, unsigned(n), c->stream));
+    HIP_TRY(launch_query_pick(pick_args(c), reinterpret_cast<const float*>(origins), reinterpret_cast<const float*>(dirs), max_time, out, unsigned(n), c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return VXRT_OK;
 } VXRT_CATCH

@@ -81,20 +81,11 @@ int voxelize_output(const char* who, const uint64_t* keys, const int32_t* words,
         set_error(std::string(who) + ": " + std::to_string(m) + " voxels, room for " + std::to_string(cap));
         return VXRT_E_INVALID;
     }
-    // written in place where the kernel's stores fit the arrays' alignment (2 bytes per coordinate, 4 per mrgb word); otherwise
-    // staged and copied
-    const bool direct = (reinterpret_cast<uintptr_t>(pos) & 1u) == 0u && (reinterpret_cast<uintptr_t>(mrgb) & 3u) == 0u;
-    ScratchBuffer spos, smrgb;
-    if (!direct) {
-        if (int rc = alloc_scratch(&spos, m * 3 * sizeof(int16_t), who, "the positions")) return rc;
-        if (int rc = alloc_scratch(&smrgb, m * 4, who, "the mrgb words")) return rc;
-    }
-    HIP_TRY(voxelize_decode(keys, words, uint32_t(m), depth, direct ? static_cast<int16_t*>(pos) : spos.as<int16_t>(),
-                            direct ? static_cast<uint32_t*>(mrgb) : smrgb.as<uint32_t>(), s));
-    if (!direct) {
-        HIP_TRY(hipMemcpyAsync(pos, spos.p, m * 3 * sizeof(int16_t), hipMemcpyDeviceToDevice, s));
-        HIP_TRY(hipMemcpyAsync(mrgb, smrgb.p, m * 4, hipMemcpyDeviceToDevice, s));
-    }
+    ScratchBuffer stage[2];
+    if (int rc = write_voxels_staged(pos, mrgb, m, s, who, stage, [&](int16_t* dst_pos, uint32_t* dst_mrgb) {
+            return voxelize_decode(keys, words, uint32_t(m), depth, dst_pos, dst_mrgb, s);
+        }))
+        return rc;
     HIP_TRY(hipStreamSynchronize(s));
     *n = m;
     return VXRT_OK;

@@ -1,8 +1,10 @@
 // block_scan.h — wave and workgroup reductions and prefix sums (wave64) shared by the level-synchronous kernels (extract.hip,
-// device_build.hip).  Everything is in thread order and integer, so the results never depend on scheduling.
+// device_build.hip, edit.hip, device_edit.hip, voxelize.hip, components.hip, pieces.hip, query.hip).  Everything is in thread order
+// and integer, so the results never depend on scheduling.
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <climits>
 #include <cstdint>
 
 namespace vxrt {
@@ -10,6 +12,18 @@ namespace vxrt {
 template <typename T> __device__ __forceinline__ T wave_sum(T v) {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+
+__device__ __forceinline__ uint32_t wave_min(uint32_t v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = min(v, __shfl_xor(v, off, 64));
+    return v;
+}
+
+__device__ __forceinline__ uint32_t wave_max(uint32_t v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = max(v, __shfl_xor(v, off, 64));
     return v;
 }
 
@@ -38,6 +52,60 @@ template <typename T, uint32_t W> __device__ __forceinline__ T block_exclusive(T
     *total = all;
     __syncthreads();
     return before + incl - v;
+}
+
+// the sum of `mine` over the block of W waves -> *out (thread 0 writes; per-wave sums, added in wave order).  Once per kernel: its
+// LDS is not reused, and no barrier follows the read.
+template <uint32_t W, typename Out> __device__ __forceinline__ void block_sum_to(uint32_t mine, Out* out) {
+    __shared__ uint32_t lds[W];
+    mine = wave_sum(mine);
+    if ((threadIdx.x & 63u) == 0u) lds[threadIdx.x >> 6] = mine;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t all = 0;
+        for (uint32_t w = 0; w < W; w++) all += lds[w];
+        *out = all;
+    }
+}
+
+// A box and flag bits: what the passes over a voxel list (device_edit.hip) and over a mesh (voxelize.hip) reduce.
+struct BoxFlags {
+    int lo[3], hi[3];
+    uint32_t flags;
+};
+
+__device__ __forceinline__ BoxFlags empty_box() { return BoxFlags{{INT_MAX, INT_MAX, INT_MAX}, {INT_MIN, INT_MIN, INT_MIN}, 0u}; }
+
+__device__ __forceinline__ void merge(BoxFlags* a, const BoxFlags& b) {
+#pragma unroll
+    for (int ax = 0; ax < 3; ax++) {
+        a->lo[ax] = min(a->lo[ax], b.lo[ax]);
+        a->hi[ax] = max(a->hi[ax], b.hi[ax]);
+    }
+    a->flags |= b.flags;
+}
+
+// the block's box and flags (W waves) -> *out (thread 0 writes), a record of lo[3], hi[3], the flags and a pad word (edit.h:
+// ListBounds, voxelize.h: MeshSummary).  Once per kernel, as block_sum_to.
+template <uint32_t W, typename Rec> __device__ __forceinline__ void block_box_to(BoxFlags v, Rec* out) {
+    __shared__ BoxFlags lds[W];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        BoxFlags o;
+#pragma unroll
+        for (int ax = 0; ax < 3; ax++) {
+            o.lo[ax] = __shfl_xor(v.lo[ax], off, 64);
+            o.hi[ax] = __shfl_xor(v.hi[ax], off, 64);
+        }
+        o.flags = uint32_t(__shfl_xor(int(v.flags), off, 64));
+        merge(&v, o);
+    }
+    if ((threadIdx.x & 63u) == 0u) lds[threadIdx.x >> 6] = v;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (uint32_t w = 1; w < W; w++) merge(&v, lds[w]);
+        *out = Rec{{v.lo[0], v.lo[1], v.lo[2]}, {v.hi[0], v.hi[1], v.hi[2]}, v.flags, 0u};
+    }
 }
 
 }  // namespace vxrt

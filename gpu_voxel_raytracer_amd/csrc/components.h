@@ -22,6 +22,21 @@ constexpr uint32_t kCompNone = 0xffffffffu;
 
 inline uint32_t comp_blocks(uint64_t n) { return uint32_t((n + kCompSpan - 1) / kCompSpan); }
 
+// this block's round-j entry of this thread (< 2^32 + kCompSpan)
+__device__ __forceinline__ uint64_t entry_of(uint32_t j) { return uint64_t(blockIdx.x) * kCompSpan + j * kCompThreads + threadIdx.x; }
+
+// a depth-15 path key -> u = p + 2^15 per axis (the inverse of path_key_of)
+__device__ __forceinline__ void cell_of(uint64_t key, uint32_t u[3]) {
+    u[0] = u[1] = u[2] = 0;
+#pragma unroll
+    for (uint32_t k = 0; k <= kCompDepth; k++) {
+        const uint32_t t = uint32_t(key >> (3u * k)) & 7u;
+        u[0] |= (t >> 2) << k;
+        u[1] |= ((t >> 1) & 1u) << k;
+        u[2] |= (t & 1u) << k;
+    }
+}
+
 // The half-open anchor box of vxrt_detached_voxels_device; on == 0: there is none (vxrt_label_components_device).
 struct CompBox {
     int32_t lo[3], hi[3];

@@ -25,34 +25,6 @@ namespace {
 
 constexpr uint32_t kWaves = kCompThreads / 64;
 
-// this block's round-j entry of this thread (< 2^32 + kCompSpan)
-__device__ __forceinline__ uint64_t entry_of(uint32_t j) { return uint64_t(blockIdx.x) * kCompSpan + j * kCompThreads + threadIdx.x; }
-
-// the block's sum of `mine` -> part[block] (thread 0 writes)
-__device__ __forceinline__ void block_count(uint32_t mine, uint64_t* part) {
-    __shared__ uint32_t lds[kWaves];
-    mine = wave_sum(mine);
-    if ((threadIdx.x & 63u) == 0u) lds[threadIdx.x >> 6] = mine;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t all = 0;
-        for (uint32_t w = 0; w < kWaves; w++) all += lds[w];
-        part[blockIdx.x] = all;
-    }
-}
-
-// a depth-15 path key -> u = p + 2^15 per axis (the inverse of path_key_of)
-__device__ __forceinline__ void cell_of(uint64_t key, uint32_t u[3]) {
-    u[0] = u[1] = u[2] = 0;
-#pragma unroll
-    for (uint32_t k = 0; k <= kCompDepth; k++) {
-        const uint32_t t = uint32_t(key >> (3u * k)) & 7u;
-        u[0] |= (t >> 2) << k;
-        u[1] |= ((t >> 1) & 1u) << k;
-        u[2] |= (t & 1u) << k;
-    }
-}
-
 // Unique result: no atomic, one store per entry.  Bound: kCompItems rounds.
 __global__ __launch_bounds__(kCompThreads) void comp_keys_kernel(const int16_t* pos, uint32_t n, uint64_t* keys, uint32_t* vals) {
 #pragma unroll 1
@@ -76,7 +48,7 @@ __global__ __launch_bounds__(kCompThreads) void comp_heads_count_kernel(const ui
         const uint64_t i = entry_of(j);
         if (i < n && head_at(keys, i)) mine++;
     }
-    block_count(mine, part);
+    block_sum_to<kWaves>(mine, part + blockIdx.x);
 }
 
 // Unique result: every offset is the scanned part[block] plus a block prefix sum in entry order; no atomic.  Bound: kCompItems rounds.
@@ -205,7 +177,7 @@ __global__ __launch_bounds__(kCompThreads) void comp_flatten_kernel(const uint64
         }
         if (v != kCompNone) atomicMin(acc + r, v);
     }
-    block_count(roots, part);
+    block_sum_to<kWaves>(roots, part + blockIdx.x);
 }
 
 // A launch after the flatten, so comp[] and acc[] are final.  Unique result: vals is a permutation of the indices, so every word of
@@ -229,7 +201,7 @@ __global__ __launch_bounds__(kCompThreads) void comp_select_count_kernel(const u
         const uint64_t i = entry_of(j);
         if (i < n && flag[i] != 0u) mine++;
     }
-    block_count(mine, part);
+    block_sum_to<kWaves>(mine, part + blockIdx.x);
 }
 
 // Unique result: every offset is the scanned part[block] plus a block prefix sum in entry order; no atomic.  Bound: kCompItems rounds.

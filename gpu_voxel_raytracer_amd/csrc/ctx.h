@@ -74,6 +74,24 @@ inline int alloc_scratch(ScratchBuffer* b, size_t bytes, const char* who, const 
     return alloc_failed(e, who, what);
 }
 
+// `count` voxels into a caller's device arrays pos (3 int16 each) and mrgb (4 bytes each) by write(int16_t*, uint32_t*), which
+// enqueues the kernel on s: in place where the kernel's stores fit the arrays' alignment (2 bytes per coordinate, 4 per mrgb word);
+// otherwise staged (in `stage`, which must outlive the work on s) and copied.  Does not wait.
+template <typename Write>
+int write_voxels_staged(void* pos, void* mrgb, size_t count, hipStream_t s, const char* who, ScratchBuffer (&stage)[2], Write write) {
+    const bool direct = (reinterpret_cast<uintptr_t>(pos) & 1u) == 0u && (reinterpret_cast<uintptr_t>(mrgb) & 3u) == 0u;
+    if (direct) {
+        HIP_TRY(write(static_cast<int16_t*>(pos), static_cast<uint32_t*>(mrgb)));
+        return VXRT_OK;
+    }
+    if (int rc = alloc_scratch(&stage[0], count * 3 * sizeof(int16_t), who, "the positions")) return rc;
+    if (int rc = alloc_scratch(&stage[1], count * 4, who, "the mrgb words")) return rc;
+    HIP_TRY(write(stage[0].as<int16_t>(), stage[1].as<uint32_t>()));
+    HIP_TRY(hipMemcpyAsync(pos, stage[0].p, count * 3 * sizeof(int16_t), hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipMemcpyAsync(mrgb, stage[1].p, count * 4, hipMemcpyDeviceToDevice, s));
+    return VXRT_OK;
+}
+
 struct EventPair {
     hipEvent_t a = nullptr, b = nullptr;
     int stage = 0;  // 0 trace, 1 temporal, 2 denoise, 3 halo pack, 4 halo unpack

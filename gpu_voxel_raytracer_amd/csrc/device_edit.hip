@@ -3,12 +3,11 @@
 //
 //   keys     a thread per 8 consecutive entries: the path key at the scene's depth (device_build.h: path_key_of, the key
 //            vxrt_edit_voxels sorts by) and, for a set, the leaf word; the thread's least and greatest position per axis and whether
-//            one of its positions lies outside the root cube -> reduced per block (wave shuffles, then LDS) -> part[block]
+//            one of its positions lies outside the root cube -> reduced per block (block_scan.h: block_box_to) -> part[block]
 //   reduce   one workgroup over the blocks' partials -> 32 bytes read back
 // Where the arrays are 16-byte aligned a thread reads its 48 bytes of positions as three 16-byte loads and its 32 bytes of mrgb as two;
 // otherwise, and for the list's last entries when n is no multiple of 8, element by element.  Nothing is decided by an atomic.
-#include <climits>
-
+#include "block_scan.h"
 #include "ctx.h"
 #include "device_build.h"
 #include "edit.h"
@@ -21,54 +20,11 @@ constexpr uint32_t kWaves = kThreads / 64;
 constexpr uint32_t kGroup = 8;                      // entries per thread
 constexpr uint32_t kSpan = kThreads * kGroup;       // entries per block
 
-struct Bounds {
-    int lo[3], hi[3];
-    uint32_t outside;
-};
-
-__device__ __forceinline__ Bounds empty_bounds() { return Bounds{{INT_MAX, INT_MAX, INT_MAX}, {INT_MIN, INT_MIN, INT_MIN}, 0u}; }
-
-__device__ __forceinline__ void merge(Bounds* a, const Bounds& b) {
-#pragma unroll
-    for (int ax = 0; ax < 3; ax++) {
-        a->lo[ax] = min(a->lo[ax], b.lo[ax]);
-        a->hi[ax] = max(a->hi[ax], b.hi[ax]);
-    }
-    a->outside |= b.outside;
-}
-
-// the block's bounds -> *out (thread 0 writes)
-__device__ __forceinline__ void block_bounds(Bounds v, ListBounds* out) {
-    __shared__ Bounds lds[kWaves];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        Bounds o;
-#pragma unroll
-        for (int ax = 0; ax < 3; ax++) {
-            o.lo[ax] = __shfl_xor(v.lo[ax], off, 64);
-            o.hi[ax] = __shfl_xor(v.hi[ax], off, 64);
-        }
-        o.outside = uint32_t(__shfl_xor(int(v.outside), off, 64));
-        merge(&v, o);
-    }
-    if ((threadIdx.x & 63u) == 0u) lds[threadIdx.x >> 6] = v;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (uint32_t w = 1; w < kWaves; w++) merge(&v, lds[w]);
-        ListBounds r;
-#pragma unroll
-        for (int ax = 0; ax < 3; ax++) { r.lo[ax] = v.lo[ax]; r.hi[ax] = v.hi[ax]; }
-        r.outside = v.outside;
-        r.pad = 0u;
-        *out = r;
-    }
-}
-
 // vec_pos / vec_mrgb: the array is 16-byte aligned.  mrgb == nullptr (a clear): no leaf words, vals is not touched.
 __global__ __launch_bounds__(kThreads) void edit_keys_kernel(const int16_t* pos, const uint8_t* mrgb, size_t n, uint32_t depth, uint32_t vec_pos,
                                                               uint32_t vec_mrgb, uint64_t* keys, uint32_t* vals, ListBounds* part) {
     const size_t i0 = (size_t(blockIdx.x) * kThreads + threadIdx.x) * kGroup;
-    Bounds v = empty_bounds();
+    BoxFlags v = empty_box();
     if (i0 < n) {
         const bool full = n - i0 >= kGroup;
         const uint32_t count = full ? kGroup : uint32_t(n - i0);
@@ -114,7 +70,7 @@ __global__ __launch_bounds__(kThreads) void edit_keys_kernel(const int16_t* pos,
                     const int c = p[3 * k + ax];
                     v.lo[ax] = min(v.lo[ax], c);
                     v.hi[ax] = max(v.hi[ax], c);
-                    v.outside |= (c < -half || c >= half) ? 1u : 0u;
+                    v.flags |= (c < -half || c >= half) ? 1u : 0u;      // ListBounds::outside
                     u[ax] = uint32_t(c + half);
                 }
                 keys[i0 + k] = path_key_of(u[0], u[1], u[2], depth);   // of an outside position: never used, the call is refused
@@ -122,20 +78,16 @@ __global__ __launch_bounds__(kThreads) void edit_keys_kernel(const int16_t* pos,
             }
         }
     }
-    block_bounds(v, part + blockIdx.x);
+    block_box_to<kWaves>(v, part + blockIdx.x);
 }
 
 __global__ __launch_bounds__(kThreads) void edit_bounds_reduce_kernel(ListBounds* part, uint32_t blocks) {
-    Bounds v = empty_bounds();
+    BoxFlags v = empty_box();
     for (uint32_t k = threadIdx.x; k < blocks; k += kThreads) {
         const ListBounds b = part[k];
-        Bounds o;
-#pragma unroll
-        for (int ax = 0; ax < 3; ax++) { o.lo[ax] = b.lo[ax]; o.hi[ax] = b.hi[ax]; }
-        o.outside = b.outside;
-        merge(&v, o);
+        merge(&v, BoxFlags{{b.lo[0], b.lo[1], b.lo[2]}, {b.hi[0], b.hi[1], b.hi[2]}, b.outside});
     }
-    block_bounds(v, part + blocks);
+    block_box_to<kWaves>(v, part + blocks);
 }
 
 }  // namespace

@@ -86,7 +86,6 @@ int reserve_edit_storage(vxrt_ctx* c, size_t nodes, size_t parents);
 // The tail of an edit, shared by vxrt_edit_voxels, vxrt_edit_voxel_grid and vxrt_edit_voxels_device: storage growth, the `edited` bookkeeping, the launch, the
 // counters, the touch maps and the sky cull's box.  Drains the frames in flight first; waits for the edit.  All or nothing.
 int apply_edit_batch(vxrt_ctx* c, const EditBatch& b);
-hipError_t launch_pick(const TraceArgs& a, const float* origins, const float* dirs, vxrt_pick_hit* out, unsigned n, hipStream_t s);
 
 // vxrt_scene_depth.h (scene_depth.hip; api_scene_depth.hip): one wave each, lane o < 8 takes octant o of the root (record `root`,
 // d_svo[0], at depth `depth`, child mask non-zero).

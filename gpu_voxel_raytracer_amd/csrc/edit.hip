@@ -1,5 +1,5 @@
-// edit.hip — device side of vxrt_edit.h: the in-place scene edit (edit_kernel) and the pick query (pick_kernel) on the 8-byte
-// records (kernels.h: SvoRecord).  The host side, which sorts a batch into the segments this kernel walks, is api_edit.hip.
+// edit.hip — device side of vxrt_edit.h: the in-place scene edit (edit_kernel) on the 8-byte records (kernels.h: SvoRecord).  The
+// host side, which sorts a batch into the segments this kernel walks, is api_edit.hip; vxrt_pick's kernel is query.hip's.
 //
 // The walk (trace_common.h: walk_step) finds slot s of a node at  base + popc(mask & (bit(s) - 1))  — for child records and leaf
 // words alike.  A node's block of children only has to be contiguous; where it lies does not matter.  So an edit:
@@ -9,31 +9,15 @@
 //     so a node in one moves at most once, to an 8-entry block, and never again);
 //   * prunes every node whose masks drop to 0 from its parent, up to the root, so that every mask is what a fresh build has.
 // Allocation is by block-wide prefix sums in segment order: the same scene and the same batch give the same records, bit for bit.
-#include "trace_common.h"
+#include "block_scan.h"
 #include "edit.h"
 
 namespace vxrt {
 namespace {
 
 constexpr int kEditThreads = 1024;
+constexpr uint32_t kEditWaves = kEditThreads / 64;
 constexpr uint32_t kNone = 0xffffffffu;
-
-// exclusive prefix sum of `v` over the block; *total = the sum of all.  Ends with a barrier (LDS may be reused).
-__device__ __forceinline__ uint32_t block_scan(uint32_t v, uint32_t* lds, uint32_t* total) {
-    const int t = threadIdx.x;
-    lds[t] = v;
-    __syncthreads();
-    for (int off = 1; off < kEditThreads; off <<= 1) {   // Hillis-Steele: 10 steps for 1024 threads
-        const uint32_t add = t >= off ? lds[t - off] : 0u;
-        __syncthreads();
-        lds[t] += add;
-        __syncthreads();
-    }
-    const uint32_t incl = lds[t];
-    *total = lds[kEditThreads - 1];
-    __syncthreads();
-    return incl - v;
-}
 
 // stores of this thread reach the CU's memory before the barrier that follows (the next level reads them from other waves)
 __device__ __forceinline__ void level_barrier() {
@@ -54,8 +38,7 @@ __device__ __forceinline__ uint32_t slot_index(uint32_t base, uint32_t mask, uin
 // One workgroup: the levels of a batch depend on each other, and a batch is small next to the work of one workgroup (a few loads
 // per touched node); the levels are separated by barriers, so a batch is one launch.
 __global__ __launch_bounds__(kEditThreads) void edit_kernel(const EditArgs a) {
-    __shared__ uint32_t lds[kEditThreads];
-    __shared__ uint32_t wave_sum[kEditThreads / 64];
+    __shared__ uint32_t lds[kEditWaves];
     const uint32_t t = threadIdx.x;
     const uint32_t L = a.depth;   // node levels 0 (root) .. L (leaf parents); segments of level L + 1 are the batch's entries
     uint32_t added = 0, removed = 0;
@@ -82,7 +65,7 @@ __global__ __launch_bounds__(kEditThreads) void edit_kernel(const EditArgs a) {
                     alloc = nw != old && (old == 0u || !eight);
                 }
                 uint32_t total;
-                const uint32_t rank = block_scan(alloc ? 1u : 0u, lds, &total);
+                const uint32_t rank = block_exclusive<uint32_t, kEditWaves>(alloc ? 1u : 0u, lds, &total);
                 if (active) {
                     if (nw != old) {
                         const uint32_t base = alloc ? (leaf_level ? leaf_top : svo_top) + 8u * rank : rec.base;
@@ -170,85 +153,17 @@ __global__ __launch_bounds__(kEditThreads) void edit_kernel(const EditArgs a) {
         }
         if (t == 0) { a.out[0] = a.svo_end; a.out[1] = a.leaf_end; }
     }
-    // live-record counters: per-wave sums (in wave order), then one lane adds them in order
-    uint32_t mine = a.clear ? removed : added;
-    for (int off = 32; off > 0; off >>= 1) mine += __shfl_xor(mine, off);
-    if ((t & 63u) == 0u) wave_sum[t >> 6] = mine;
-    __syncthreads();
+    block_sum_to<kEditWaves>(a.clear ? removed : added, a.out + 2);   // the live-record counter
     if (t == 0) {
-        uint32_t sum = 0;
-        for (int w = 0; w < kEditThreads / 64; w++) sum += wave_sum[w];
-        a.out[2] = sum;
         a.out[3] = uint32_t(a.svo[0].masks);
         a.out[4] = a.svo[0].base;
     }
-}
-
-// vxrt_pick: cast_ray (trace_common.h) — the same two walks, chosen by the same test — and, for a hit, the voxel from the walk's
-// integer path coordinates: at the leaf parent (level lvl = depth) the voxel's index along x is  ix << 1 | octant bit x,  d + 1 bits,
-// and its vxrt_set_voxels coordinate is that minus 2^depth (scene_host.cpp: build_octree's slot rule).
-__global__ __launch_bounds__(kBlock) void pick_kernel(const TraceArgs a, const float* origins, const float* dirs, vxrt_pick_hit* out, unsigned n) {
-    extern __shared__ uint2 pick_stack[];
-    const unsigned i = blockIdx.x * kBlock + threadIdx.x;
-    if (i >= n) return;
-    const SceneView sc = make_scene(a);
-    const uint32_t depth = uint32_t(a.node_levels - 1);
-    uint2* stack = pick_stack + threadIdx.x;
-    const f3 o = ld3(origins + 3 * size_t(i)), d = ld3(dirs + 3 * size_t(i));
-    const f3 inv = mk3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
-    int status = kWalkMiss;
-    f3 center = splat3(0.0f);
-    float time = 0.0f;
-    uint32_t lvl = 0, octant = 0, leaf = 0, ix = 0, iy = 0, iz = 0;
-    bool entered;
-    if (ray_is_regular(inv)) {
-        WalkF w;
-        entered = walkf_begin(w, sc, o, d, inv);
-        if (entered) {
-            do { status = walkf_step(w, sc, stack); } while (status == kWalkOn);
-            const uint32_t bit = 1u << w.octant;
-            center = w.center; time = w.time; lvl = w.lvl; octant = w.octant;
-            ix = w.ix; iy = w.iy; iz = w.iz;
-            leaf = w.rec.base + __popc((w.rec.masks >> 8) & (bit - 1u));
-        }
-    } else {
-        Walk w;
-        entered = walk_begin(w, sc, o, d);
-        if (entered) {
-            do { status = walk_step(w, sc, kAlmostInfinity, stack); } while (status == kWalkOn);
-            center = w.center; time = w.time; lvl = w.lvl; octant = w.octant;
-            ix = w.ix; iy = w.iy; iz = w.iz;
-            leaf = walk_leaf_index(w);
-        }
-    }
-    RayHit hit;
-    hit.time = 0.0f; hit.node = 0; hit.normal = splat3(0.0f);
-    vxrt_pick_hit r{};
-    if (entered && finish_ray(sc, status, o, d, time, center, lvl, octant, leaf, hit)) {
-        r.status = status == kWalkCap ? 2u : 1u;
-        if (status == kWalkLeaf) {
-            const int32_t half = int32_t(1) << depth;
-            r.voxel[0] = int32_t(ix << 1 | ((octant >> 2) & 1u)) - half;
-            r.voxel[1] = int32_t(iy << 1 | ((octant >> 1) & 1u)) - half;
-            r.voxel[2] = int32_t(iz << 1 | (octant & 1u)) - half;
-        }
-    }
-    r.time = hit.time;
-    r.normal[0] = hit.normal.x; r.normal[1] = hit.normal.y; r.normal[2] = hit.normal.z;
-    r.leaf = hit.node;
-    out[i] = r;
 }
 
 }  // namespace
 
 hipError_t launch_edit(const EditArgs& a, hipStream_t s) {
     hipLaunchKernelGGL(edit_kernel, dim3(1), dim3(kEditThreads), 0, s, a);
-    return hipGetLastError();
-}
-
-hipError_t launch_pick(const TraceArgs& a, const float* origins, const float* dirs, vxrt_pick_hit* out, unsigned n, hipStream_t s) {
-    const size_t lds = size_t(a.stack_levels) * kBlock * sizeof(uint2);
-    hipLaunchKernelGGL(pick_kernel, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), lds, s, a, origins, dirs, out, n);
     return hipGetLastError();
 }
 

@@ -52,4 +52,16 @@ hipError_t pieces_scatter(const uint32_t* sorted, const uint32_t* rank, uint32_t
 // Over the n input indices: a picked entry's piece number goes to the offset of the picked entries before it.
 hipError_t pieces_write(const uint32_t* pick, uint32_t n, const uint64_t* pick_part, const PieceAcc* accs, uint32_t* piece, hipStream_t s);
 
+// ---- api_pieces.hip: the bodies behind the entry points of vxrt_pieces.h and vxrt_components.h -----------------------------------------
+// who: the entry point the caller used, which every error text names.
+// vxrt_component_table_device as declared; vxrt_label_components_device is this with id = info = nullptr, info_cap = 0.
+int component_table(const char* who, vxrt_ctx* c, const int16_t (*pos)[3], size_t n, uint32_t connectivity, uint32_t* label, uint32_t* id,
+                    vxrt_piece* info, size_t info_cap, size_t* n_components);
+
+// vxrt_detached_pieces_device as declared (n_pieces not null).  n_pieces == nullptr: vxrt_detached_voxels_device, every detached voxel
+// whatever its component's size, with piece = info = nullptr; no accumulators are kept.
+int detached_pieces(const char* who, vxrt_ctx* c, const int32_t anchor_min[3], const int32_t anchor_max[3], uint32_t connectivity,
+                    uint32_t min_voxels, uint32_t max_voxels, int16_t (*pos)[3], uint8_t (*mrgb)[4], uint32_t* piece, size_t cap, size_t* n,
+                    vxrt_piece* info, size_t info_cap, size_t* n_pieces);
+
 }  // namespace vxrt

@@ -24,33 +24,6 @@ namespace {
 
 constexpr uint32_t kWaves = kCompThreads / 64;
 
-// this block's round-j entry of this thread (< 2^32 + kCompSpan)
-__device__ __forceinline__ uint64_t entry_of(uint32_t j) { return uint64_t(blockIdx.x) * kCompSpan + j * kCompThreads + threadIdx.x; }
-
-// a depth-15 path key -> u = p + 2^15 per axis (the inverse of path_key_of)
-__device__ __forceinline__ void cell_of(uint64_t key, uint32_t u[3]) {
-    u[0] = u[1] = u[2] = 0;
-#pragma unroll
-    for (uint32_t k = 0; k <= kCompDepth; k++) {
-        const uint32_t t = uint32_t(key >> (3u * k)) & 7u;
-        u[0] |= (t >> 2) << k;
-        u[1] |= ((t >> 1) & 1u) << k;
-        u[2] |= (t & 1u) << k;
-    }
-}
-
-__device__ __forceinline__ uint32_t wave_min(uint32_t v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = min(v, __shfl_xor(v, off, 64));
-    return v;
-}
-
-__device__ __forceinline__ uint32_t wave_max(uint32_t v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = max(v, __shfl_xor(v, off, 64));
-    return v;
-}
-
 // Unique result: a root's slot is the scanned part[block] plus a block prefix sum in entry order; no atomic.  Bound: kCompItems rounds.
 __global__ __launch_bounds__(kCompThreads) void pieces_slots_kernel(const uint32_t* comp, const uint32_t* acc, uint32_t m, const uint64_t* part,
                                                                     uint32_t anchored, uint32_t* slot, PieceAcc* accs) {

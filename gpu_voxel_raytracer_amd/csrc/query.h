@@ -5,7 +5,7 @@
 #include <cstddef>
 #include <cstdint>
 
-#include "kernels.h"
+#include "ctx.h"
 #include "../../include/vxrt_edit.h"
 
 namespace vxrt {
@@ -34,7 +34,21 @@ struct LookupArgs {
 // leaf[i] = the leaf word at pos[i] + offset or 0 (vxrt_query.h's rule); part[b] = the nonzero answers among block b's entries.
 hipError_t launch_query_lookup(const LookupArgs& a, hipStream_t s);
 
-// vxrt_pick's kernel with a bound per ray (max_time; nullptr: every ray unbounded).  a: as vxrt_pick builds it.
+// The pick's view of the loaded scene: the 8-byte records only, whatever format the tracers walk.
+inline TraceArgs pick_args(const vxrt_ctx* c) {
+    TraceArgs a{};
+    a.svo = c->d_svo;
+    a.leaves = c->d_leaves;
+    a.root_rec = c->root_rec;
+    a.node_levels = int(c->depth) + 1;
+    memcpy(a.root_center, c->root_center, sizeof a.root_center);
+    a.root_size = c->root_size;
+    a.stack_levels = c->depth < 1 ? 1 : int(c->depth);
+    return a;
+}
+
+// The pick of vxrt_pick and vxrt_pick_device: cast_ray per ray, bounded by max_time[i] (nullptr: every ray unbounded), n > 0 rays in
+// blocks of kBlock.  a: pick_args.
 hipError_t launch_query_pick(const TraceArgs& a, const float* origins, const float* dirs, const float* max_time, vxrt_pick_hit* out,
                              unsigned n, hipStream_t s);
 

@@ -1,6 +1,6 @@
-// query.hip — device side of vxrt_query.h: the voxel lookup (query_lookup_kernel) and the bounded pick (query_pick_kernel) on the
-// 8-byte records (kernels.h: SvoRecord).  The host side is api_query.hip; the kernels' contract is in query.h and the argument in
-// DESIGN.md §22.
+// query.hip — device side of vxrt_query.h: the voxel lookup (query_lookup_kernel) and the pick (query_pick_kernel, vxrt_edit.h's
+// vxrt_pick included) on the 8-byte records (kernels.h: SvoRecord).  The host side is api_query.hip, and api_edit.hip for vxrt_pick;
+// the kernels' contract is in query.h and the argument in DESIGN.md §22.
 //
 // A node's slot s (s = x << 2 | y << 1 | z) holds, as in the walk (trace_common.h: walk_step) and the extract (extract.hip), child
 // record / leaf word  base + popc(mask & (bit(s) - 1)).  Following those pointers from the root reads the tree in any layout the
@@ -32,7 +32,6 @@ __device__ __forceinline__ uint32_t slot_at(uint32_t xy, uint32_t z, uint32_t k)
 // for an entry that is outside the root cube or has met a clear bit — and the value is dropped by a select.  Such an entry carries
 // masks == 0 from there on.  The host launches this only for a scene that has record 0 and leaf word 0, and for n > 0.
 __global__ __launch_bounds__(kQueryThreads) void query_lookup_kernel(const LookupArgs a) {
-    __shared__ uint32_t lds[kWaves];
     const uint64_t first = uint64_t(blockIdx.x) * kQuerySpan + threadIdx.x;
     const uint32_t d = a.depth;
     const int64_t half = int64_t(1) << d;
@@ -95,19 +94,14 @@ __global__ __launch_bounds__(kQueryThreads) void query_lookup_kernel(const Looku
         mine += word[j] != 0u ? 1u : 0u;
     }
     if (a.part == nullptr) return;   // uniform over the grid
-    mine = wave_sum(mine);
-    if ((threadIdx.x & 63u) == 0u) lds[threadIdx.x >> 6] = mine;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t all = 0;
-        for (uint32_t w = 0; w < kWaves; w++) all += lds[w];
-        a.part[blockIdx.x] = all;
-    }
+    block_sum_to<kWaves>(mine, a.part + blockIdx.x);
 }
 
-// vxrt_pick_device: pick_kernel (edit.hip) with cast_ray's max_distance per ray — the same two walks, chosen by cast_ray's own test
-// (trace_common.h: the walk with the plane times in registers for a regular, unbounded ray, the shader's text otherwise) — and the
-// voxel from the walk's integer path coordinates as pick_kernel takes it.
+// vxrt_pick (max_time == nullptr: every ray unbounded) and vxrt_pick_device: cast_ray (trace_common.h) with its max_distance per ray —
+// the same two walks, chosen by cast_ray's own test (the walk with the plane times in registers for a regular, unbounded ray, the
+// shader's text otherwise) — and, for a hit, the voxel from the walk's integer path coordinates: at the leaf parent (level lvl =
+// depth) the voxel's index along x is  ix << 1 | octant bit x,  d + 1 bits, and its vxrt_set_voxels coordinate is that minus 2^depth
+// (scene_host.cpp: build_octree's slot rule).
 __global__ __launch_bounds__(kBlock) void query_pick_kernel(const TraceArgs a, const float* origins, const float* dirs, const float* max_time,
                                                             vxrt_pick_hit* out, unsigned n) {
     extern __shared__ uint2 query_stack[];

@@ -28,10 +28,6 @@ namespace {
 constexpr uint32_t kWaves = kVoxThreads / 64;
 constexpr uint32_t kNone = 0xffffffffu;
 
-__device__ __forceinline__ int64_t wmul(int a, int b) { return int64_t(a) * int64_t(b); }
-__device__ __forceinline__ int min3(int a, int b, int c) { return min(a, min(b, c)); }
-__device__ __forceinline__ int max3(int a, int b, int c) { return max(a, max(b, c)); }
-
 struct Tri {
     int q[9];       // [3 * vertex + axis]
 };

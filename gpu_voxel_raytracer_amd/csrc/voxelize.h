@@ -36,6 +36,11 @@ struct MeshSummary {
 
 inline uint32_t vox_blocks(uint64_t n) { return uint32_t((n + kVoxThreads - 1) / kVoxThreads); }
 
+// the exact integer arithmetic of the rules on snapped coordinates (voxelize.hip, solid.hip)
+__device__ __forceinline__ int64_t wmul(int a, int b) { return int64_t(a) * int64_t(b); }
+__device__ __forceinline__ int min3(int a, int b, int c) { return min(a, min(b, c)); }
+__device__ __forceinline__ int max3(int a, int b, int c) { return max(a, max(b, c)); }
+
 // The setup pass over n_tris > 0 triangles (< 2^32): tq[t] = triangle t snapped, off[t] = the columns of the triangles before t,
 // off[n_tris] = *columns = all columns (W), *out = the summary.  part: vox_blocks(n_tris) + 1 words, bounds: vox_blocks(n_tris) + 1
 // summaries.  No index is followed before it is compared with n_verts.  Waits for the result; with a flag set, off is meaningless.

@@ -16,8 +16,6 @@
 //             writes, so a cell is tested once where the column is short, which it is along the dominant axis.
 //   decode    a thread per unique key: the position and the (m & 0x7f, r, g, b) bytes
 // 256 threads, no atomics: every position is a prefix sum in triangle order, then column order, then up the column.
-#include <climits>
-
 #include "block_scan.h"
 #include "ctx.h"
 #include "device_build.h"
@@ -28,53 +26,7 @@ namespace {
 
 constexpr uint32_t kWaves = kVoxThreads / 64;
 
-struct Summary {
-    int lo[3], hi[3];
-    uint32_t flags;
-};
-
-__device__ __forceinline__ Summary empty_summary() { return Summary{{INT_MAX, INT_MAX, INT_MAX}, {INT_MIN, INT_MIN, INT_MIN}, 0u}; }
-
-__device__ __forceinline__ void merge(Summary* a, const Summary& b) {
-#pragma unroll
-    for (int ax = 0; ax < 3; ax++) {
-        a->lo[ax] = min(a->lo[ax], b.lo[ax]);
-        a->hi[ax] = max(a->hi[ax], b.hi[ax]);
-    }
-    a->flags |= b.flags;
-}
-
-// the block's summary -> *out (thread 0 writes)
-__device__ __forceinline__ void block_summary(Summary v, MeshSummary* out) {
-    __shared__ Summary lds[kWaves];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        Summary o;
-#pragma unroll
-        for (int ax = 0; ax < 3; ax++) {
-            o.lo[ax] = __shfl_xor(v.lo[ax], off, 64);
-            o.hi[ax] = __shfl_xor(v.hi[ax], off, 64);
-        }
-        o.flags = uint32_t(__shfl_xor(int(v.flags), off, 64));
-        merge(&v, o);
-    }
-    if ((threadIdx.x & 63u) == 0u) lds[threadIdx.x >> 6] = v;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (uint32_t w = 1; w < kWaves; w++) merge(&v, lds[w]);
-        MeshSummary r;
-#pragma unroll
-        for (int ax = 0; ax < 3; ax++) { r.lo[ax] = v.lo[ax]; r.hi[ax] = v.hi[ax]; }
-        r.flags = v.flags;
-        r.pad = 0u;
-        *out = r;
-    }
-}
-
-__device__ __forceinline__ int64_t wmul(int a, int b) { return int64_t(a) * int64_t(b); }
 __device__ __forceinline__ int64_t abs64(int64_t v) { return v < 0 ? -v : v; }
-__device__ __forceinline__ int min3(int a, int b, int c) { return min(a, min(b, c)); }
-__device__ __forceinline__ int max3(int a, int b, int c) { return max(a, max(b, c)); }
 
 // rule 2: the candidate cells [*c0, *c1] of an axis whose snapped coordinates span [lo, hi]; a face on a cell boundary belongs to
 // the cell above it only
@@ -178,7 +130,7 @@ __global__ __launch_bounds__(kVoxThreads) void vox_setup_kernel(const float* ver
                                                                  uint64_t* off, uint64_t* part, MeshSummary* bounds) {
     __shared__ uint64_t lds[kWaves];
     const uint32_t t = blockIdx.x * kVoxThreads + threadIdx.x;
-    Summary v = empty_summary();
+    BoxFlags v = empty_box();
     uint64_t columns = 0;
     if (t < n_tris) {
         int q[9];
@@ -217,20 +169,16 @@ __global__ __launch_bounds__(kVoxThreads) void vox_setup_kernel(const float* ver
     const uint64_t before = block_exclusive<uint64_t, kWaves>(columns, lds, &total);
     if (t < n_tris) off[t] = before;
     if (threadIdx.x == 0) part[blockIdx.x] = total;
-    block_summary(v, bounds + blockIdx.x);
+    block_box_to<kWaves>(v, bounds + blockIdx.x);
 }
 
 __global__ __launch_bounds__(kVoxThreads) void vox_reduce_kernel(MeshSummary* bounds, uint32_t blocks) {
-    Summary v = empty_summary();
+    BoxFlags v = empty_box();
     for (uint32_t k = threadIdx.x; k < blocks; k += kVoxThreads) {
         const MeshSummary b = bounds[k];
-        Summary o;
-#pragma unroll
-        for (int ax = 0; ax < 3; ax++) { o.lo[ax] = b.lo[ax]; o.hi[ax] = b.hi[ax]; }
-        o.flags = b.flags;
-        merge(&v, o);
+        merge(&v, BoxFlags{{b.lo[0], b.lo[1], b.lo[2]}, {b.hi[0], b.hi[1], b.hi[2]}, b.flags});
     }
-    block_summary(v, bounds + blocks);
+    block_box_to<kWaves>(v, bounds + blocks);
 }
 
 // off[t]: within its block -> over the mesh; off[n_tris] = the total

@@ -13,6 +13,7 @@ this thin ctypes layer; it keeps the reference's names and argument meaning:
 There is NO CPU fallback: if libvxrt.so is missing or no HIP device is present, construction raises.
 Nothing here imports the test oracle.
 """
+import contextlib
 import ctypes as C
 import os
 
@@ -515,6 +516,50 @@ class Context:
         if status != 0:
             raise VxrtError(status, where, (self._L.vxrt_last_error() or b"").decode(errors="replace"))
 
+    @contextlib.contextmanager
+    def _ordered(self):
+        """A library call ordered on both sides against torch's current stream -> that stream: the context's stream first waits for
+        what torch has enqueued there, and after the body that stream waits for what the context has enqueued."""
+        import torch
+        stream = torch.cuda.current_stream(torch.device("cuda", self.device)).cuda_stream
+        self.context_wait_stream(stream)
+        yield stream
+        self.stream_wait_context(stream)
+
+    @staticmethod
+    def _cap(cap):
+        if cap is not None and (not isinstance(cap, (int, np.integer)) or isinstance(cap, bool) or cap < 0):
+            raise ValueError("cap must be a count of voxels")
+
+    def _voxel_list(self, call, where, cap, pieces=False):
+        """A library call that gives a voxel list by the cap rule -> (pos int16[n,3], mrgb uint8[n,4]) on the context's device.
+        call(pos, mrgb, cap, n) is the call with everything in front of its output arguments bound.  cap=None: called once to count
+        and once into tensors of exactly that size; cap=k: once, into tensors with room for k, cut to the count.  The filling call is
+        ordered on both sides against torch's current stream (the allocator may hand out memory that work there still uses).
+        pieces: call(pos, mrgb, piece, cap, n, info, info_cap, n_pieces), with room for as many pieces as voxels when cap is given ->
+        (pos, mrgb, piece uint32[n], table)."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        got, k = C.c_size_t(0), C.c_size_t(0)
+
+        def run(cap, info_cap, pos=None, mrgb=None, piece=None, raw=None):
+            out = [None if t is None else C.c_void_p(t.data_ptr()) for t in (pos, mrgb, piece, raw)]
+            tail = (out[2], C.c_size_t(cap), C.byref(got), out[3], C.c_size_t(info_cap), C.byref(k)) if pieces else (C.c_size_t(cap), C.byref(got))
+            self._chk(call(out[0], out[1], *tail), where)
+        info_cap = cap
+        if cap is None:
+            run(0, 0)
+            cap, info_cap = int(got.value), int(k.value)
+        cap, info_cap = int(cap), int(info_cap)
+        pos, mrgb = torch.empty((cap, 3), dtype=torch.int16, device=dev), torch.empty((cap, 4), dtype=torch.uint8, device=dev)
+        piece = torch.empty(cap, dtype=torch.uint32, device=dev) if pieces else None
+        raw = torch.empty(info_cap * self.PIECE_BYTES, dtype=torch.uint8, device=dev) if pieces else None
+        if cap:
+            with self._ordered():
+                run(cap, info_cap, pos, mrgb, piece, raw)
+        n = int(got.value)
+        return (pos[:n], mrgb[:n], piece[:n], self._piece_table(raw, int(k.value))) if pieces else (pos[:n], mrgb[:n])
+
     # -- lifetime ------------------------------------------------------------------------------------
     def close(self):
         if getattr(self, "_h", None) is not None and self._h:
@@ -646,11 +691,9 @@ class Context:
             out = torch.empty(shape, dtype=torch.int32, device=dev)
         elif out.dtype != torch.int32 or tuple(out.shape) != shape or out.device != dev or not out.is_contiguous():
             raise ValueError(f"out must be a contiguous int32 tensor of shape {shape} on {dev}")
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        self.context_wait_stream(stream)
-        self._chk(self._L.vxrt_get_voxel_grid(self._h, (C.c_int32 * 3)(*(int(v) for v in origin)), (C.c_uint32 * 3)(*shape),
-                                              C.c_void_p(out.data_ptr() if out.numel() else None)), "vxrt_get_voxel_grid")
-        self.stream_wait_context(stream)
+        with self._ordered():
+            self._chk(self._L.vxrt_get_voxel_grid(self._h, (C.c_int32 * 3)(*(int(v) for v in origin)), (C.c_uint32 * 3)(*shape),
+                                                  C.c_void_p(out.data_ptr() if out.numel() else None)), "vxrt_get_voxel_grid")
         return out
 
     def set_menger(self, level, clip=0, mrgb=(0, 0xb0, 0xd0, 0x60), emissive_period=0):
@@ -745,21 +788,8 @@ class Context:
     def get_voxels_device(self, box_min=None, box_max=None):
         """vxrt_get_voxels_device: get_voxels into torch tensors on the context's device -> (pos int16[n,3], mrgb uint8[n,4]), the same
         voxels in the same order; only the count crosses to the host.  Ordered on both sides against torch's current stream."""
-        import torch
-        dev = torch.device("cuda", self.device)
         lo, hi = self._box(box_min, box_max)
-        got = C.c_size_t(0)
-        self._chk(self._L.vxrt_get_voxels_device(self._h, _p(lo), _p(hi), None, None, C.c_size_t(0), C.byref(got)), "vxrt_get_voxels_device")
-        n = int(got.value)
-        pos, mrgb = torch.empty((n, 3), dtype=torch.int16, device=dev), torch.empty((n, 4), dtype=torch.uint8, device=dev)
-        if n:
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            self.context_wait_stream(stream)
-            self._chk(self._L.vxrt_get_voxels_device(self._h, _p(lo), _p(hi), C.c_void_p(pos.data_ptr()), C.c_void_p(mrgb.data_ptr()),
-                                                     C.c_size_t(n), C.byref(got)), "vxrt_get_voxels_device")
-            assert got.value == n
-            self.stream_wait_context(stream)
-        return pos, mrgb
+        return self._voxel_list(lambda *out: self._L.vxrt_get_voxels_device(self._h, _p(lo), _p(hi), *out), "vxrt_get_voxels_device", None)
 
     def _mesh(self, verts, tris, mrgb):
         """voxelize_mesh's arguments -> (verts float32 [v,3], tris uint32 [t,3], mrgb uint8 [t,4]) as contiguous tensors on the
@@ -818,26 +848,12 @@ class Context:
         run: DESIGN.md §17).  cap=k: one run into tensors with room for k voxels, cut to the count; more than k voxels is an error
         (VXRT_E_INVALID)."""
         import torch
-        dev = torch.device("cuda", self.device)
-        if cap is not None and (not isinstance(cap, (int, np.integer)) or isinstance(cap, bool) or cap < 0):
-            raise ValueError("cap must be a count of voxels")
+        self._cap(cap)
         verts, tris, mrgb = self._mesh(verts, tris, mrgb)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        self.context_wait_stream(stream)
+        self.context_wait_stream(torch.cuda.current_stream(verts.device).cuda_stream)      # the mesh may just have been written there
         args = (self._h, C.c_void_p(verts.data_ptr() if len(verts) else None), C.c_size_t(len(verts)),
                 C.c_void_p(tris.data_ptr() if len(tris) else None), C.c_void_p(mrgb.data_ptr() if len(tris) else None), C.c_size_t(len(tris)))
-        got = C.c_size_t(0)
-        if cap is None:
-            self._chk(self._L.vxrt_voxelize_mesh_device(*args, None, None, C.c_size_t(0), C.byref(got)), "vxrt_voxelize_mesh_device")
-            cap = int(got.value)
-        pos, out = torch.empty((cap, 3), dtype=torch.int16, device=dev), torch.empty((cap, 4), dtype=torch.uint8, device=dev)
-        if cap:
-            self.context_wait_stream(stream)      # the allocator may hand out memory that work on torch's stream still uses
-            self._chk(self._L.vxrt_voxelize_mesh_device(*args, C.c_void_p(pos.data_ptr()), C.c_void_p(out.data_ptr()), C.c_size_t(cap),
-                                                        C.byref(got)), "vxrt_voxelize_mesh_device")
-            self.stream_wait_context(stream)
-        n = int(got.value)
-        return pos[:n], out[:n]
+        return self._voxel_list(lambda *out: self._L.vxrt_voxelize_mesh_device(*args, *out), "vxrt_voxelize_mesh_device", cap)
 
     def set_mesh(self, verts, tris, mrgb, cap=None):
         """voxelize_mesh, then set_voxels_device of its list: the scene becomes the mesh's surface, built on the device end to end."""
@@ -859,9 +875,7 @@ class Context:
         overlapping shells XOR and a shell inside a shell is a cavity.  verts, tris, mrgb and cap: as voxelize_mesh takes them;
         fill: one (m, r, g, b) of bytes."""
         import torch
-        dev = torch.device("cuda", self.device)
-        if cap is not None and (not isinstance(cap, (int, np.integer)) or isinstance(cap, bool) or cap < 0):
-            raise ValueError("cap must be a count of voxels")
+        self._cap(cap)
         if isinstance(fill, np.ndarray):
             if fill.dtype != np.uint8 or fill.size != 4:
                 raise ValueError("fill must be one (m, r, g, b) of uint8")
@@ -873,23 +887,11 @@ class Context:
         without_colours = mrgb is None and interior_only
         verts, tris, mrgb = self._mesh(verts, tris, (0, 0, 0, 0) if without_colours else mrgb)
         fill4 = (C.c_uint8 * 4)(*[int(b) for b in fill])
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        self.context_wait_stream(stream)
+        self.context_wait_stream(torch.cuda.current_stream(verts.device).cuda_stream)      # the mesh may just have been written there
         args = (self._h, C.c_void_p(verts.data_ptr() if len(verts) else None), C.c_size_t(len(verts)),
                 C.c_void_p(tris.data_ptr() if len(tris) else None), C.c_void_p(mrgb.data_ptr() if len(tris) and not without_colours else None),
                 C.c_size_t(len(tris)), fill4, C.c_uint32(SOLID_INTERIOR if interior_only else SOLID_UNION))
-        got = C.c_size_t(0)
-        if cap is None:
-            self._chk(self._L.vxrt_voxelize_solid_device(*args, None, None, C.c_size_t(0), C.byref(got)), "vxrt_voxelize_solid_device")
-            cap = int(got.value)
-        pos, out = torch.empty((cap, 3), dtype=torch.int16, device=dev), torch.empty((cap, 4), dtype=torch.uint8, device=dev)
-        if cap:
-            self.context_wait_stream(stream)      # the allocator may hand out memory that work on torch's stream still uses
-            self._chk(self._L.vxrt_voxelize_solid_device(*args, C.c_void_p(pos.data_ptr()), C.c_void_p(out.data_ptr()), C.c_size_t(cap),
-                                                         C.byref(got)), "vxrt_voxelize_solid_device")
-            self.stream_wait_context(stream)
-        n = int(got.value)
-        return pos[:n], out[:n]
+        return self._voxel_list(lambda *out: self._L.vxrt_voxelize_solid_device(*args, *out), "vxrt_voxelize_solid_device", cap)
 
     def set_solid(self, verts, tris, mrgb, fill, cap=None):
         """voxelize_solid, then set_voxels_device of its list: the scene becomes the mesh as a solid, built on the device end to end."""
@@ -927,11 +929,9 @@ class Context:
         label = torch.empty(len(pos), dtype=torch.uint32, device=dev)
         got = C.c_size_t(0)
         if len(pos):
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            self.context_wait_stream(stream)
-            self._chk(self._L.vxrt_label_components_device(self._h, C.c_void_p(pos.data_ptr()), C.c_size_t(len(pos)), conn,
-                                                           C.c_void_p(label.data_ptr()), C.byref(got)), "vxrt_label_components_device")
-            self.stream_wait_context(stream)
+            with self._ordered():
+                self._chk(self._L.vxrt_label_components_device(self._h, C.c_void_p(pos.data_ptr()), C.c_size_t(len(pos)), conn,
+                                                               C.c_void_p(label.data_ptr()), C.byref(got)), "vxrt_label_components_device")
         return label, int(got.value)
 
     def detached_voxels(self, anchor_min, anchor_max, connectivity=6, cap=None):
@@ -940,28 +940,13 @@ class Context:
         int16[n,3], mrgb uint8[n,4]) as torch tensors on the context's device, in the order and with the bytes of get_voxels.
         cap=None: two calls, one to count and one into tensors of exactly that size.  cap=k: one call into tensors with room for k
         voxels, cut to the count; more than k voxels is an error (VXRT_E_INVALID)."""
-        import torch
-        dev = torch.device("cuda", self.device)
         conn = self._connectivity(connectivity)
-        if cap is not None and (not isinstance(cap, (int, np.integer)) or isinstance(cap, bool) or cap < 0):
-            raise ValueError("cap must be a count of voxels")
+        self._cap(cap)
         if anchor_min is None or anchor_max is None:
             raise ValueError("anchor_min and anchor_max: three integers each")
         lo, hi = self._box(anchor_min, anchor_max)
-        got = C.c_size_t(0)
-        if cap is None:
-            self._chk(self._L.vxrt_detached_voxels_device(self._h, _p(lo), _p(hi), conn, None, None, C.c_size_t(0), C.byref(got)),
-                      "vxrt_detached_voxels_device")
-            cap = int(got.value)
-        pos, mrgb = torch.empty((cap, 3), dtype=torch.int16, device=dev), torch.empty((cap, 4), dtype=torch.uint8, device=dev)
-        if cap:
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            self.context_wait_stream(stream)      # the allocator may hand out memory that work on torch's stream still uses
-            self._chk(self._L.vxrt_detached_voxels_device(self._h, _p(lo), _p(hi), conn, C.c_void_p(pos.data_ptr()), C.c_void_p(mrgb.data_ptr()),
-                                                          C.c_size_t(cap), C.byref(got)), "vxrt_detached_voxels_device")
-            self.stream_wait_context(stream)
-        n = int(got.value)
-        return pos[:n], mrgb[:n]
+        return self._voxel_list(lambda *out: self._L.vxrt_detached_voxels_device(self._h, _p(lo), _p(hi), conn, *out),
+                                "vxrt_detached_voxels_device", cap)
 
     def drop_detached(self, anchor_min, anchor_max, connectivity=6):
         """detached_voxels, then clear_voxels_device of its list: what no longer hangs on a voxel in the anchor box is removed from the
@@ -1002,16 +987,14 @@ class Context:
         k = 0
         raw = torch.empty(0, dtype=torch.uint8, device=dev)
         if n:
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            self.context_wait_stream(stream)
-            args = (self._h, C.c_void_p(pos.data_ptr()), C.c_size_t(n), conn)
-            self._chk(self._L.vxrt_component_table_device(*args, None, None, None, C.c_size_t(0), C.byref(got)), "vxrt_component_table_device")
-            k = int(got.value)
-            raw = torch.empty(k * self.PIECE_BYTES, dtype=torch.uint8, device=dev)
-            self.context_wait_stream(stream)      # the allocator may hand out memory that work on torch's stream still uses
-            self._chk(self._L.vxrt_component_table_device(*args, C.c_void_p(label.data_ptr()), C.c_void_p(ids.data_ptr()),
-                                                          C.c_void_p(raw.data_ptr()), C.c_size_t(k), C.byref(got)), "vxrt_component_table_device")
-            self.stream_wait_context(stream)
+            with self._ordered() as stream:
+                args = (self._h, C.c_void_p(pos.data_ptr()), C.c_size_t(n), conn)
+                self._chk(self._L.vxrt_component_table_device(*args, None, None, None, C.c_size_t(0), C.byref(got)), "vxrt_component_table_device")
+                k = int(got.value)
+                raw = torch.empty(k * self.PIECE_BYTES, dtype=torch.uint8, device=dev)
+                self.context_wait_stream(stream)      # the allocator may hand out memory that work on torch's stream still uses
+                self._chk(self._L.vxrt_component_table_device(*args, C.c_void_p(label.data_ptr()), C.c_void_p(ids.data_ptr()),
+                                                              C.c_void_p(raw.data_ptr()), C.c_size_t(k), C.byref(got)), "vxrt_component_table_device")
         return label, ids, self._piece_table(raw, k)
 
     def detached_pieces(self, anchor_min, anchor_max, connectivity=6, min_voxels=0, max_voxels=None, cap=None):
@@ -1023,11 +1006,8 @@ class Context:
         that order, and table as component_table gives it for pos, so table["first"][p] is the index in pos of piece p's first voxel.
         cap=None: two calls, one to count and one into tensors of exactly that size.  cap=k: one call into tensors with room for k
         voxels and k pieces, cut to the counts; more than k voxels is an error (VXRT_E_INVALID)."""
-        import torch
-        dev = torch.device("cuda", self.device)
         conn = self._connectivity(connectivity)
-        if cap is not None and (not isinstance(cap, (int, np.integer)) or isinstance(cap, bool) or cap < 0):
-            raise ValueError("cap must be a count of voxels")
+        self._cap(cap)
         if max_voxels is None:
             max_voxels = 0xFFFFFFFF
         for v in (min_voxels, max_voxels):
@@ -1037,25 +1017,7 @@ class Context:
             raise ValueError("anchor_min and anchor_max: three integers each")
         lo, hi = self._box(anchor_min, anchor_max)
         head = (self._h, _p(lo), _p(hi), conn, C.c_uint32(int(min_voxels)), C.c_uint32(int(max_voxels)))
-        got, pieces = C.c_size_t(0), C.c_size_t(0)
-        if cap is None:
-            self._chk(self._L.vxrt_detached_pieces_device(*head, None, None, None, C.c_size_t(0), C.byref(got), None, C.c_size_t(0),
-                                                          C.byref(pieces)), "vxrt_detached_pieces_device")
-            cap, info_cap = int(got.value), int(pieces.value)
-        else:
-            cap = info_cap = int(cap)
-        pos, mrgb = torch.empty((cap, 3), dtype=torch.int16, device=dev), torch.empty((cap, 4), dtype=torch.uint8, device=dev)
-        piece = torch.empty(cap, dtype=torch.uint32, device=dev)
-        raw = torch.empty(info_cap * self.PIECE_BYTES, dtype=torch.uint8, device=dev)
-        if cap:
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            self.context_wait_stream(stream)      # the allocator may hand out memory that work on torch's stream still uses
-            self._chk(self._L.vxrt_detached_pieces_device(*head, C.c_void_p(pos.data_ptr()), C.c_void_p(mrgb.data_ptr()), C.c_void_p(piece.data_ptr()),
-                                                          C.c_size_t(cap), C.byref(got), C.c_void_p(raw.data_ptr()), C.c_size_t(info_cap),
-                                                          C.byref(pieces)), "vxrt_detached_pieces_device")
-            self.stream_wait_context(stream)
-        n, k = int(got.value), int(pieces.value)
-        return pos[:n], mrgb[:n], piece[:n], self._piece_table(raw, k)
+        return self._voxel_list(lambda *out: self._L.vxrt_detached_pieces_device(*head, *out), "vxrt_detached_pieces_device", cap, pieces=True)
 
     def drop_detached_pieces(self, anchor_min, anchor_max, connectivity=6, min_voxels=0, max_voxels=None, cap=None):
         """detached_pieces, then clear_voxels_device of its list: the detached pieces within the size range are removed from the
@@ -1156,11 +1118,9 @@ class Context:
         leaf = torch.empty(len(pos), dtype=torch.int32, device=dev) if words else None
         got = C.c_size_t(0)
         if len(pos):
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            self.context_wait_stream(stream)
-            self._chk(self._L.vxrt_lookup_voxels_device(self._h, C.c_void_p(pos.data_ptr()), C.c_size_t(len(pos)), off,
-                                                        C.c_void_p(leaf.data_ptr()) if words else None, C.byref(got)), "vxrt_lookup_voxels_device")
-            self.stream_wait_context(stream)
+            with self._ordered():
+                self._chk(self._L.vxrt_lookup_voxels_device(self._h, C.c_void_p(pos.data_ptr()), C.c_size_t(len(pos)), off,
+                                                            C.c_void_p(leaf.data_ptr()) if words else None, C.byref(got)), "vxrt_lookup_voxels_device")
         return leaf, int(got.value)
 
     def lookup_voxels(self, pos, offset=None):
@@ -1201,12 +1161,10 @@ class Context:
             t = self._query_tensor(max_time)
         out = torch.empty((len(o), PICK_HIT_DTYPE.itemsize // 4), dtype=torch.int32, device=dev)   # every record is written
         if len(o):
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            self.context_wait_stream(stream)
-            self._chk(self._L.vxrt_pick_device(self._h, C.c_void_p(o.data_ptr()), C.c_void_p(d.data_ptr()),
-                                               C.c_void_p(t.data_ptr()) if t is not None else None, C.c_size_t(len(o)),
-                                               C.c_void_p(out.data_ptr())), "vxrt_pick_device")
-            self.stream_wait_context(stream)
+            with self._ordered():
+                self._chk(self._L.vxrt_pick_device(self._h, C.c_void_p(o.data_ptr()), C.c_void_p(d.data_ptr()),
+                                                   C.c_void_p(t.data_ptr()) if t is not None else None, C.c_size_t(len(o)),
+                                                   C.c_void_p(out.data_ptr())), "vxrt_pick_device")
         return {"status": out[:, 0].view(torch.uint32), "time": out[:, 1].view(torch.float32), "normal": out[:, 2:5].view(torch.float32),
                 "voxel": out[:, 5:8], "leaf": out[:, 8]}
 

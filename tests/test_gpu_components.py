@@ -320,7 +320,7 @@ def test_refusals_write_nothing(ctx, H):
     short = C.c_void_p()
     assert hip.hipMalloc(C.byref(short), C.c_size_t(4 * (n - 1))) == 0
     refused(d_pos, n, 6, short)
-    assert "label" in last_error(ctx)
+    assert "label" in last_error(ctx) and last_error(ctx).startswith("vxrt_label_components_device:")     # the entry point that was called
     assert raw_label(ctx, d_pos, n - 1, 6, short) == (0, 1)               # it holds n - 1
     small = C.c_void_p()
     assert hip.hipMalloc(C.byref(small), C.c_size_t(6 * (n - 1))) == 0    # ... and a list one position short
@@ -391,7 +391,8 @@ def test_detached_voxels_of_an_edited_sponge(H, sponge, conn):
         # room for one voxel less: the count, an error and nothing written; odd addresses; exactly enough
         k = len(want[0])
         gp, gm = guarded(k + 2)
-        assert raw_detached(c, *anchor, conn, gp, gm, k - 1) == (H.E_INVALID, k) and last_error(c)
+        assert raw_detached(c, *anchor, conn, gp, gm, k - 1) == (H.E_INVALID, k)
+        assert last_error(c) == f"vxrt_detached_voxels_device: {k} voxels, room for {k - 1}"      # the entry point that was called
         assert untouched(gp, gm)
         assert raw_detached(c, *anchor, conn, gp, None, k)[0] == H.E_INVALID and raw_detached(c, None, anchor[1], conn, gp, gm, k)[0] == H.E_INVALID
         for bad in (0, 7, 27):

@@ -125,6 +125,7 @@ def check(ctx, pos, want, what, connectivities=K.CONNECTIVITIES):
         assert again[3] == k and all(a.tobytes() == b.tobytes() for a, b in zip((label, ids, table), again[:3])), (what, conn, "a second call")
         mere, mere_count = ctx.label_components(d_pos, conn)
         assert mere_count == k and mere.cpu().numpy().tobytes() == label.tobytes(), (what, conn, "label_components' bytes")
+        assert np.array_equal(mere.cpu().numpy(), w_label), (what, conn, "label_components against the model")
         assert np.array_equal(d_pos.cpu().numpy(), pos), (what, conn, "pos was written")
 
 
@@ -367,7 +368,7 @@ def test_refusals_write_nothing(ctx, H):
     refused(d_pos, 1 << 32, 6, label.ptr, ids.ptr, info.ptr, k)                      # checked before any pointer is looked at
     refused(None, 1 << 32, 6, None, None, None, 0)
     refused(d_pos, n, 6, label.ptr, ids.ptr, info.ptr, k - 1, count=k)               # room for one record less: the count all the same
-    assert "components" in last_error(ctx)
+    assert last_error(ctx) == f"vxrt_component_table_device: {k} components, room for {k - 1}"     # the entry point that was called
     refused(d_pos, n, 6, None, None, info.ptr, 0, count=k)
     # arrays one entry short.  Each is an allocation of its own, because what the library can see is the allocation: a torch tensor
     # lies in a larger block of torch's allocator.  1024 words and 256 records are whole pages, so no rounding hides the missing entry
@@ -468,6 +469,7 @@ def test_an_untouched_scene_and_one_layer_cleared(H, sponge, conn):
         got = assert_pieces(c, anchor, conn, (0, EVERY), want, "a layer cleared", H)
         mere = c.detached_voxels(*anchor, connectivity=conn)
         assert torch.equal(got[0], mere[0]) and torch.equal(got[1], mere[1])
+        assert np.array_equal(mere[0].cpu().numpy(), want[0]) and np.array_equal(mere[1].cpu().numpy(), want[1]), "detached_voxels against the model"
         for a, b in zip(c.read_scene(), records):
             assert np.array_equal(a, b), "the call changed the scene"
 
@@ -505,7 +507,8 @@ def test_pieces_of_different_sizes_and_the_size_filter(H, sponge, conn):
         gp, gm = guarded(n + 2)
         piece, info = Words(n), Words(k * PIECE_WORDS)
         for cap, info_cap in ((n - 1, k), (n, k - 1), (0, 0)):
-            assert raw_pieces(c, *anchor, conn, 0, EVERY, gp, gm, piece.ptr, cap, info.ptr, info_cap) == (H.E_INVALID, n, k) and last_error(c)
+            assert raw_pieces(c, *anchor, conn, 0, EVERY, gp, gm, piece.ptr, cap, info.ptr, info_cap) == (H.E_INVALID, n, k)
+            assert last_error(c).startswith("vxrt_detached_pieces_device: ") and "room for" in last_error(c)     # the entry point that was called
             assert untouched(gp, gm) and piece.untouched() and info.untouched()
         assert raw_pieces(c, *anchor, conn, 0, EVERY, None, None, piece.ptr, n - 1, None, 0) == (H.E_INVALID, n, k) and piece.untouched()
         # refusals: one of pos and mrgb, a null anchor, the connectivity, misaligned piece and info

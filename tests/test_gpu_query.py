@@ -428,9 +428,11 @@ def check_rays(O, ctx, ref, what, only=None):
         free = ctx.pick_device(d_o, d_d)
         assert_views_of_one_buffer(free, n)
         free_rec = records(free)
-        assert free_rec.tobytes() == records(ctx.pick(o, d)).tobytes(), f"{what}: {family}: unbounded, against vxrt_pick's bytes"
-        picked = (free_rec["status"] != 0, free_rec["time"], free_rec["leaf"], free_rec["normal"])
-        R.assert_rays_equal(picked, oracle_free(O, ref, family), f"{what}: {family}: unbounded", o, d, zero_time_sign=True)
+        host_rec = records(ctx.pick(o, d))
+        assert free_rec.tobytes() == host_rec.tobytes(), f"{what}: {family}: unbounded, against vxrt_pick's bytes"
+        for name, r in (("unbounded", free_rec), ("vxrt_pick", host_rec)):      # each against the oracle, not through the other
+            picked = (r["status"] != 0, r["time"], r["leaf"], r["normal"])
+            R.assert_rays_equal(picked, oracle_free(O, ref, family), f"{what}: {family}: {name}", o, d, zero_time_sign=True)
         bounds, want = oracle_bounded(O, ref, family)
         got = ctx.pick_device(d_o, d_d, on_device(bounds))
         rec = records(got)
@@ -487,6 +489,14 @@ def test_ray_counts_guards_and_repeatability(O, cube32):
         free = Words(HIT_WORDS * n)
         assert raw_pick(ctx, d_o, d_d, None, n, free.ptr) == 0 and free.guards_hold()
         assert free.words().tobytes() == records(ctx.pick(o[:n], d[:n])).tobytes(), f"{n} rays, unbounded"
+    # vxrt_pick through its host entry launches the same kernel in blocks of 256 rays (trace_common.h: kBlock): one ray, one short
+    # of a block, a block, one past it and one past two, each against the oracle with the walk test's pinned difference
+    want = oracle_free(O, ref, "on_planes")
+    for n in (1, 255, 256, 257, 513):
+        rec = records(ctx.pick(o[:n], d[:n]))
+        assert len(rec) == n
+        R.assert_rays_equal((rec["status"] != 0, rec["time"], rec["leaf"], rec["normal"]), tuple(w[:n] for w in want), f"vxrt_pick, {n} rays",
+                            o[:n], d[:n], zero_time_sign=True)
     assert ctx._L.vxrt_pick_device(ctx._h, C.c_void_p(4), None, None, C.c_size_t(0), None) == 0        # n == 0 touches no pointer
     none = ctx.pick_device(d_o[:0], d_d[:0], 1.0)
     assert_views_of_one_buffer(none, 0)
