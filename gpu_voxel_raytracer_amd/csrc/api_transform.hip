@@ -1,0 +1,122 @@
+// api_transform.hip — host side of vxrt_transform.h: a voxel list in device memory resampled under a fixed-point affine map, by
+// pulling every cell of a destination box through the map into the list.  The source is keyed at depth 15 by the device editor's
+// pass (device_edit.hip) and sorted and deduplicated by the list builder's front (device_build.h: sort_unique_list); the pull and
+// the decode are transform.hip's; the blocks' counts are summed by the list builder's scan and the result is sorted by its radix
+// sort.  Nothing but two counts and the source's bounds crosses to the host.  DESIGN.md §23.
+#include <string>
+
+#include "ctx.h"
+#include "device_build.h"
+#include "edit.h"
+#include "scene_args.h"
+#include "transform.h"
+#include "../../include/vxrt_transform.h"
+
+extern "C" {
+
+int vxrt_transform_voxels_device(vxrt_ctx* c, const int16_t (*pos)[3], const uint8_t (*mrgb)[4], size_t n, const vxrt_affine* pull,
+                                 const int32_t box_min[3], const int32_t box_max[3], int16_t (*out_pos)[3], uint8_t (*out_mrgb)[4],
+                                 size_t cap, size_t* n_out) try {
+    using namespace vxrt;
+    const char* who = "vxrt_transform_voxels_device";
+    const std::string w = who;
+    if (!valid_ctx(c)) { set_error("null context"); return VXRT_E_INVALID; }
+    if (uint64_t(n) >= (uint64_t(1) << 32)) { set_error(w + ": 2^32 voxels or more"); return VXRT_E_INVALID; }
+    if (!pull || !n_out || !box_min || !box_max) { set_error(w + ": null argument"); return VXRT_E_INVALID; }
+    if (pull->reserved != 0) { set_error(w + ": pull->reserved must be 0"); return VXRT_E_INVALID; }
+    for (int i = 0; i < 3; i++) {
+        for (int j = 0; j < 3; j++)
+            if (pull->m[i][j] < -(int32_t(1) << 24) || pull->m[i][j] > (int32_t(1) << 24)) {
+                set_error(w + ": an entry of pull->m beyond 2^24 (256.0 in Q16)");
+                return VXRT_E_INVALID;
+            }
+        if (pull->t[i] < -(int64_t(1) << 40) || pull->t[i] > (int64_t(1) << 40)) {
+            set_error(w + ": an entry of pull->t beyond 2^40 (2^24 cells in Q16)");
+            return VXRT_E_INVALID;
+        }
+    }
+    uint64_t cells = 1;
+    bool empty_box = false;
+    for (int ax = 0; ax < 3; ax++) {
+        if (box_min[ax] < -32768 || box_min[ax] > 32768 || box_max[ax] < -32768 || box_max[ax] > 32768) {
+            set_error(w + ": a box corner outside [-32768, 32768]");
+            return VXRT_E_INVALID;
+        }
+        if (box_min[ax] >= box_max[ax]) empty_box = true;
+        else cells *= uint64_t(box_max[ax] - box_min[ax]);      // each at most 2^16
+    }
+    if (!empty_box && cells >= (uint64_t(1) << 32)) { set_error(w + ": a box of 2^32 cells or more"); return VXRT_E_INVALID; }
+    if (n != 0 && !pos) { set_error(w + ": null voxel positions"); return VXRT_E_INVALID; }
+    if (mrgb ? (out_pos != nullptr) != (out_mrgb != nullptr) : out_mrgb != nullptr) {
+        set_error(w + (mrgb ? ": out_pos and out_mrgb come both or neither" : ": out_mrgb without mrgb"));
+        return VXRT_E_INVALID;
+    }
+    if (empty_box || n == 0) { *n_out = 0; return VXRT_OK; }
+
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    if (int rc = check_device_array(c, pos, n * 3 * sizeof(int16_t), who, "pos")) return rc;
+    if (mrgb)
+        if (int rc = check_device_array(c, mrgb, n * 4, who, "mrgb")) return rc;
+    if (out_pos)
+        if (int rc = check_device_array(c, out_pos, cap * 3 * sizeof(int16_t), who, "out_pos")) return rc;
+    if (out_mrgb)
+        if (int rc = check_device_array(c, out_mrgb, cap * 4, who, "out_mrgb")) return rc;
+
+    // the source: keys at depth 15 (every int16 position is inside that cube), sorted, one per position, the last entry's bytes
+    hipStream_t s = c->stream;     // behind everything enqueued there, vxrt_context_wait_stream's events included
+    const bool with_vals = mrgb != nullptr;
+    const uint32_t blocks = pull_blocks(cells);
+    ListScratch ls;
+    ScratchBuffer words, part;
+    if (int rc = alloc_list_scratch(n, with_vals, who, &ls)) return rc;
+    if (int rc = alloc_scratch(&part, (size_t(blocks) + 1) * sizeof(uint64_t), who, "the block counts")) return rc;
+    ListBounds lb;
+    if (int rc = edit_keys_device(reinterpret_cast<const int16_t*>(pos), reinterpret_cast<const uint8_t*>(mrgb), n, 15u,
+                                  ls.keys[0].as<uint64_t>(), ls.vals[0].as<uint32_t>(), s, who, &lb))
+        return rc;
+    size_t m = 0;
+    int cur = 0;
+    if (int rc = sort_unique_list(&ls, uint32_t(n), 15u, &words, s, who, &m, &cur)) return rc;
+
+    PullArgs a{};
+    for (int i = 0; i < 3; i++) {
+        for (int j = 0; j < 3; j++) a.m[i][j] = pull->m[i][j];
+        a.t[i] = pull->t[i];
+        a.lo[i] = box_min[i];
+        a.ext[i] = uint32_t(box_max[i] - box_min[i]);
+        a.src_lo[i] = lb.lo[i];
+        a.src_hi[i] = lb.hi[i];
+    }
+    a.cells = uint32_t(cells);
+    a.keys = ls.keys[cur].as<uint64_t>();
+    a.words = with_vals ? words.as<int32_t>() : nullptr;
+    a.count = uint32_t(m);      // 0 < m <= n
+    a.part = part.as<uint64_t>();
+    HIP_TRY(launch_transform_pull(a, s));
+    HIP_TRY(launch_exclusive_scan(a.part, blocks, s));
+    uint64_t count = 0;
+    HIP_TRY(hipMemcpyAsync(&count, a.part + blocks, sizeof count, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    *n_out = size_t(count);
+    if (!out_pos || count == 0) return VXRT_OK;
+    if (count > cap) {
+        set_error(w + ": " + std::to_string(count) + " voxels, room for " + std::to_string(cap));
+        return VXRT_E_INVALID;
+    }
+
+    // the result: (key of d, leaf word of s) per voxel at the scanned offsets, sorted by key (unique by construction), decoded
+    ListScratch out;
+    if (int rc = alloc_list_scratch(size_t(count), with_vals, who, &out)) return rc;
+    uint64_t* kp[2] = {out.keys[0].as<uint64_t>(), out.keys[1].as<uint64_t>()};
+    uint32_t* vp[2] = {out.vals[0].as<uint32_t>(), out.vals[1].as<uint32_t>()};
+    a.out_keys = kp[0];
+    a.out_words = vp[0];
+    HIP_TRY(launch_transform_pull(a, s));
+    int at = 0;
+    HIP_TRY(radix_sort_pairs(kp, vp, uint32_t(count), 48u, out.hist.as<uint32_t>(), out.totals.as<uint32_t>(), s, &at));
+    HIP_TRY(launch_transform_decode(kp[at], vp[at], uint32_t(count), reinterpret_cast<uint8_t*>(out_pos), reinterpret_cast<uint8_t*>(out_mrgb), s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return VXRT_OK;
+} VXRT_CATCH
+
+}  // extern "C"

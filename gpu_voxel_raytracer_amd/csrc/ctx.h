@@ -13,6 +13,7 @@
 //   api_scene_depth.hip   the octree depth of a loaded scene changed in place (vxrt_scene_depth.h)
 //   api_compact.hip  an edited scene re-laid as a fresh build lies, and the storage counts (vxrt_compact.h)
 //   api_query.hip    voxel lookups and bounded ray casts against the scene from device memory (vxrt_query.h)
+//   api_transform.hip  a device voxel list resampled under a fixed-point affine map (vxrt_transform.h)
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -180,6 +180,55 @@ class SceneStorage(C.Structure):
                 ("leaves_used", C.c_uint64), ("leaves_capacity", C.c_uint64)]
 
 
+class Affine(C.Structure):
+    """vxrt_affine (include/vxrt_transform.h): a pull map in Q16, 64 bytes."""
+    _fields_ = [("m", (C.c_int32 * 3) * 3), ("reserved", C.c_int32), ("t", C.c_int64 * 3)]
+
+
+AFFINE_M_LIMIT, AFFINE_T_LIMIT = 1 << 24, 1 << 40
+
+
+def _rigid_args(rotation, pivot, translation):
+    r = np.asarray(rotation, np.float64)
+    p, u = np.asarray(pivot, np.float64).reshape(-1), np.asarray(translation, np.float64).reshape(-1)
+    if r.shape != (3, 3) or p.shape != (3,) or u.shape != (3,):
+        raise ValueError("rotation must be 3x3, pivot and translation three numbers each")
+    if not (np.isfinite(r).all() and np.isfinite(p).all() and np.isfinite(u).all()):
+        raise ValueError("rotation, pivot and translation must be finite")
+    return r, p, u
+
+
+def rigid_pull(rotation, pivot=(0, 0, 0), translation=(0, 0, 0)):
+    """The pull map (include/vxrt_transform.h) of the rigid motion x -> R (x - pivot) + pivot + translation, R = rotation (3x3
+    float64), in the coordinates in which cell c is [c, c + 1)^3 -> Affine: m = rint(R^T * 65536), t = rint((pivot - R^T (pivot +
+    translation)) * 65536), both in float64.  pivot may be a half-integer (a piece's centre of mass is sum / voxels + 1/2).  A value
+    beyond the header's limits (|m| <= 2^24, |t| <= 2^40) is refused."""
+    r, p, u = _rigid_args(rotation, pivot, translation)
+    m = np.rint(r.T * 65536.0)
+    t = np.rint((p - r.T @ (p + u)) * 65536.0)
+    if (np.abs(m) > AFFINE_M_LIMIT).any() or (np.abs(t) > AFFINE_T_LIMIT).any():
+        raise ValueError("the pull map is beyond vxrt_affine's limits (|m| <= 2^24, |t| <= 2^40)")
+    a = Affine()
+    for i in range(3):
+        for j in range(3):
+            a.m[i][j] = int(m[i, j])
+        a.t[i] = int(t[i])
+    return a
+
+
+def rigid_box(src_min, src_max, rotation, pivot=(0, 0, 0), translation=(0, 0, 0)):
+    """The destination box of a list whose positions span src_min .. src_max (inclusive) under rigid_pull's motion -> (box_min,
+    box_max), half-open, three ints each: the eight corners of the cell box [src_min, src_max + 1] mapped forward, floor / ceil,
+    grown by 2 cells per side (the rounding of m moves a pulled centre by less than half a cell) and clipped to [-32768, 32768]."""
+    r, p, u = _rigid_args(rotation, pivot, translation)
+    lo, hi = np.asarray(src_min, np.float64).reshape(3), np.asarray(src_max, np.float64).reshape(3) + 1.0
+    corners = np.array([[(lo, hi)[(k >> ax) & 1][ax] for ax in range(3)] for k in range(8)], np.float64)
+    moved = (corners - p) @ r.T + p + u
+    box_min = np.clip(np.floor(moved.min(axis=0)) - 2, -32768, 32768)
+    box_max = np.clip(np.ceil(moved.max(axis=0)) + 2, -32768, 32768)
+    return tuple(int(v) for v in box_min), tuple(int(v) for v in box_max)
+
+
 # vxrt_pick_hit (include/vxrt_edit.h)
 PICK_HIT_DTYPE = np.dtype([("status", np.uint32), ("time", np.float32), ("normal", np.float32, (3,)), ("voxel", np.int32, (3,)),
                            ("leaf", np.int32)])
@@ -1167,6 +1216,77 @@ class Context:
                                                    C.c_void_p(out.data_ptr())), "vxrt_pick_device")
         return {"status": out[:, 0].view(torch.uint32), "time": out[:, 1].view(torch.float32), "normal": out[:, 2:5].view(torch.float32),
                 "voxel": out[:, 5:8], "leaf": out[:, 8]}
+
+    @staticmethod
+    def _cell3(v, name, lo, hi):
+        try:
+            o = [int(x) for x in np.asarray(v).reshape(-1).tolist()]
+            exact = [float(x) for x in np.asarray(v, np.float64).reshape(-1).tolist()] == [float(x) for x in o]
+        except (TypeError, ValueError):
+            raise ValueError(f"{name} must be three integers") from None
+        if len(o) != 3 or not exact or not all(lo <= x <= hi for x in o):
+            raise ValueError(f"{name} must be three integers of [{lo}, {hi}]")
+        return (C.c_int32 * 3)(*o)
+
+    def transform_voxels(self, pos, mrgb, pull, box_min, box_max, cap=None):
+        """vxrt_transform_voxels_device (include/vxrt_transform.h): the list pos / mrgb resampled under the pull map (an Affine, e.g.
+        rigid_pull's) into the half-open box [box_min, box_max): every cell of the box takes the voxel its centre is pulled into ->
+        (pos int16 [k,3], mrgb uint8 [k,4]) as torch tensors on the context's device, in path order.  mrgb=None: positions only, and
+        the second value is None.  pos (int16 [n,3]) and mrgb (uint8 [n,4]) are contiguous torch tensors on the context's device, or
+        numpy arrays, which are uploaded with torch once every check has passed.  cap=None: two calls, one to count and one into
+        tensors of exactly that size; cap=k: one call into tensors with room for k voxels, cut to the count; more than k voxels is an
+        error (VXRT_E_INVALID).  Ordered on both sides against torch's current stream.  No scene is needed or touched."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        self._query_check(pos, "pos", torch.int16, 3)
+        if mrgb is not None:
+            self._query_check(mrgb, "mrgb", torch.uint8, 4)
+            if len(mrgb) != len(pos):
+                raise ValueError("one mrgb per position")
+        if not isinstance(pull, Affine):
+            raise TypeError("pull must be an Affine (rigid_pull makes one)")
+        lo, hi = self._cell3(box_min, "box_min", -32768, 32768), self._cell3(box_max, "box_max", -32768, 32768)
+        self._cap(cap)
+        pos = self._query_tensor(pos)
+        mrgb = None if mrgb is None else self._query_tensor(mrgb)
+        n = len(pos)
+        got = C.c_size_t(0)
+
+        def run(out_pos, out_mrgb, room):
+            self._chk(self._L.vxrt_transform_voxels_device(
+                self._h, C.c_void_p(pos.data_ptr()), None if mrgb is None else C.c_void_p(mrgb.data_ptr()),
+                C.c_size_t(n), C.byref(pull), lo, hi, None if out_pos is None else C.c_void_p(out_pos.data_ptr()),
+                None if out_mrgb is None else C.c_void_p(out_mrgb.data_ptr()), C.c_size_t(room), C.byref(got)), "vxrt_transform_voxels_device")
+        if n == 0:          # an empty tensor has no address to tell "no mrgb" from "no entries" by: the result is empty either way
+            cap = 0
+        if cap is None:
+            with self._ordered():
+                run(None, None, 0)
+            cap = int(got.value)
+        cap = int(cap)
+        out_pos = torch.empty((cap, 3), dtype=torch.int16, device=dev)
+        out_mrgb = None if mrgb is None else torch.empty((cap, 4), dtype=torch.uint8, device=dev)
+        if cap:
+            with self._ordered():
+                run(out_pos, out_mrgb, cap)
+        k = int(got.value) if cap else 0
+        return out_pos[:k], (None if out_mrgb is None else out_mrgb[:k])
+
+    def rotate_voxels(self, pos, mrgb, rotation, pivot=(0, 0, 0), translation=(0, 0, 0)):
+        """transform_voxels under rigid_pull(rotation, pivot, translation) into rigid_box of the list's bounds, which are taken with
+        torch on the device: the list moved by x -> R (x - pivot) + pivot + translation, resampled."""
+        import torch
+        self._query_check(pos, "pos", torch.int16, 3)
+        if mrgb is not None:
+            self._query_check(mrgb, "mrgb", torch.uint8, 4)
+            if len(mrgb) != len(pos):
+                raise ValueError("one mrgb per position")
+        pull = rigid_pull(rotation, pivot, translation)
+        pos = self._query_tensor(pos)          # every check has passed: rigid_pull was the last that can refuse
+        if len(pos) == 0:
+            return self.transform_voxels(pos, mrgb, pull, (0, 0, 0), (0, 0, 0))
+        lo, hi = pos.amin(dim=0).cpu().numpy(), pos.amax(dim=0).cpu().numpy()
+        return self.transform_voxels(pos, mrgb, pull, *rigid_box(lo, hi, rotation, pivot, translation))
 
     def _box(self, box_min, box_max):
         if (box_min is None) != (box_max is None):

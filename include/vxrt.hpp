@@ -29,6 +29,7 @@
 #include "vxrt_query.h"
 #include "vxrt_scene_depth.h"
 #include "vxrt_solid.h"
+#include "vxrt_transform.h"
 #include "vxrt_voxelize.h"
 
 namespace vxrt {
@@ -275,6 +276,16 @@ class Context {
     // ... and pick with rays and hits in device memory, each ray bounded by max_time[i] (nullptr: unbounded, the bytes of pick)
     void pick_device(const float (*origins)[3], const float (*dirs)[3], const float* max_time, size_t n, vxrt_pick_hit* out) {
         check(vxrt_pick_device(ctx_, origins, dirs, max_time, n, out), "vxrt_pick_device");
+    }
+    // vxrt_transform.h: the list pos / mrgb (device memory; mrgb == nullptr: positions only) resampled under the pull map into the
+    // half-open box, in path order.  out_pos == out_mrgb == nullptr counts only.  Returns the number of voxels of the result.
+    size_t transform_voxels_device(const int16_t (*pos)[3], const uint8_t (*mrgb)[4], size_t n, const vxrt_affine& pull,
+                                   const std::array<int32_t, 3>& box_min, const std::array<int32_t, 3>& box_max,
+                                   int16_t (*out_pos)[3] = nullptr, uint8_t (*out_mrgb)[4] = nullptr, size_t cap = 0) {
+        size_t count = 0;
+        check(vxrt_transform_voxels_device(ctx_, pos, mrgb, n, &pull, box_min.data(), box_max.data(), out_pos, out_mrgb, cap, &count),
+              "vxrt_transform_voxels_device");
+        return count;
     }
     // vxrt_set_voxel_grid (vxrt_grid.h): dims[0] x dims[1] x dims[2] cells in device memory of the context's device, C order
     // [x][y][z], cell (i, j, k) at origin + (i, j, k); palette: 256 entries for VXRT_GRID_PALETTE8, nullptr for VXRT_GRID_WORD32
