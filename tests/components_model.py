@@ -49,14 +49,15 @@ def classes_of(cells, connectivity):
     """cells: a list of distinct (x, y, z) -> (Classes over their indices, {cell: index})"""
     index = {c: i for i, c in enumerate(cells)}
     assert len(index) == len(cells)
+    # every cell is an int16 position, so a neighbour beyond int16 is in no list: there is no such voxel, and in Python integers
+    # nothing wraps around to one
+    assert all(LO <= v <= HI for c in cells for v in c)
     sets = Classes(len(cells))
-    offs = offsets(connectivity)
+    offs = [d for d in offsets(connectivity) if d > (0, 0, 0)]      # adjacency is symmetric: one of d and -d finds every pair
+    assert 2 * len(offs) == connectivity
     for c, i in index.items():
         for d in offs:
-            nb = (c[0] + d[0], c[1] + d[1], c[2] + d[2])
-            if min(nb) < LO or max(nb) > HI:
-                continue                          # beyond int16: there is no such voxel, and nothing wraps around to one
-            j = index.get(nb)
+            j = index.get((c[0] + d[0], c[1] + d[1], c[2] + d[2]))
             if j is not None:
                 sets.join(i, j)
     return sets, index

@@ -2,7 +2,7 @@
 ({(x, y, z): leaf word}, tests/edit_model.py).  Pure Python and numpy: the GPU test (test_gpu_mutator_sequences.py) replays a
 sequence on a context, the CPU test (test_mutator_sequences_cpu.py) checks the generator itself.
 
-sequence(seed, model, depth) yields Step(kind, args, apply_to_model).  The twelve kinds are KINDS; args names the call's arguments
+sequence(seed, model, depth) yields Step(kind, args, apply_to_model).  The fourteen kinds are KINDS; args names the call's arguments
 (args["call"] tells which entry point of the kind, see the GPU test's `run`), and
   args["twin"]   the same step through edit_voxels / clear_voxels / set_scene_depth / fit_scene_depth / compact_scene only, as a list
                  of ("set", pos, mrgb) / ("clear", pos) / ("depth", d) / ("fit",) / ("compact",),
@@ -11,10 +11,21 @@ sequence(seed, model, depth) yields Step(kind, args, apply_to_model).  The twelv
 apply_to_model(model) applies the step to a dict in place (through edit_model.apply) and returns it.  What a step does to the dict
 comes from the models the suite has: edit_model.apply for the lists, grid_edit_model.edit_lists for the grids, voxelize_model.voxelize
 and solid_model.solid for the meshes (computed once per shape at the origin and moved by whole voxels, which the rules commute with:
-the CPU test checks that against the models of the moved meshes); the depth from host.cube_depth / host.scene_depth_for.
+the CPU test checks that against the models of the moved meshes); components_model.detached and pieces_model.detached_pieces for
+the two drops; the depth from host.cube_depth / host.scene_depth_for.
 
-Order.  The kinds of one seed follow an Eulerian circuit of the complete directed graph on the twelve kinds with its self-loops: 144
-edges, so 145 steps, the first kind once more at the end, and every ordered pair (A directly followed by B) occurs exactly once
+Drops.  A drop_detached or drop_detached_pieces step draws a connectivity and an anchor: an axis, the median of the present voxels'
+coordinate on it as the cut, and which side of the cut is anchored; the anchor box is that half-space clipped to [-32768, 32768)^3,
+so about half of the scene is anchored and what does not hang on that half is removed.  drop_detached_pieces also draws min_voxels /
+max_voxels from the sizes of the model's detached pieces (with two distinct sizes or more the range selects some pieces and leaves
+one behind) and a cap: None, the exact count or a few more.  A draw that would leave fewer than KEEP voxels (of a scene that holds as many) is drawn again, eight
+times at the most; then the half that holds the most voxels is anchored, over every axis and side (and the whole range where even
+that leaves fewer, so that nothing is removed).  args holds the call's arguments and the values it returns: pos and mrgb in path
+order, for the pieces also piece and table (pieces_model.PIECE records).  A drop is a clear of its list: the twin is ("clear", pos),
+and the depth and the far bookkeeping stay.
+
+Order.  The kinds of one seed follow an Eulerian circuit of the complete directed graph on the fourteen kinds with its self-loops: 196
+edges, so 197 steps, the first kind once more at the end, and every ordered pair (A directly followed by B) occurs exactly once
 among them.  The circuit starts at set_host, so that the smallest start scene holds more than its one voxel before anything clears.
 
 Chunk boundary.  After the first compact, before a set_host or set_device step of the circuit the generator chooses, it inserts a set
@@ -30,24 +41,28 @@ import functools
 
 import numpy as np
 
+import components_model as K
 import edit_model as M
+import extract_model as X
 import grid_edit_model as GE
+import pieces_model as P
 import solid_model as S
 import voxelize_model as V
 from gpu_voxel_raytracer_amd import host as H
 from gpu_voxel_raytracer_amd import scenes
 
 KINDS = ("set_host", "clear_host", "set_device", "clear_device", "grid_replace", "grid_mask", "depth", "far_set", "fit", "compact",
-         "mesh", "carve")
+         "mesh", "carve", "drop_detached", "drop_detached_pieces")
 BOUNDARY_COUNTS = (1023, 1024, 1025, 2049)
 BOUNDARY_DEPTH = 5
 KEEP = 4            # voxels a clearing step always leaves, so that a later carve finds one to clear and one to leave
+ANCHOR_DRAWS = 8    # anchors a drop step draws before it takes the half that holds the most voxels
 
 Step = collections.namedtuple("Step", "kind args apply_to_model")
 
 
 def circuit(rng):
-    """-> the 145 kinds of an Eulerian circuit over KINDS x KINDS from set_host (Hierholzer, the edges of every kind shuffled)."""
+    """-> the 197 kinds of an Eulerian circuit over KINDS x KINDS from set_host (Hierholzer, the edges of every kind shuffled)."""
     out = {k: [KINDS[i] for i in rng.permutation(len(KINDS))] for k in KINDS}
     stack, order = [KINDS[0]], []
     while stack:
@@ -100,10 +115,11 @@ def holding_depth(model):
 
 
 # the start scenes of the GPU test with the seed of each (one seed per scene): the device-built level-3 sponge, castle.vox and the one
-# voxel (0, 0, 0), whose depth is 0
-CASES = (("menger_device", 1), ("castle", 2), ("one_voxel", 3))
+# voxel (0, 0, 0), whose depth is 0.  The sponge's seed is the lowest whose first case holds a far_set that has to grow, which the GPU
+# test first makes without grow; that it is also the one-voxel scene's seed gives the two the same circuit and nothing else
+CASES = (("menger_device", 3), ("castle", 2), ("one_voxel", 3))
 MENGER_MRGB = (0, 0xB0, 0xD0, 0x60)
-PARTS = 2           # the GPU test runs a sequence as this many consecutive cases (test_gpu_mutator_sequences.py says why)
+PARTS = 5           # the GPU test runs a sequence as this many consecutive cases (test_gpu_mutator_sequences.py says why)
 
 
 def part_range(n, part):
@@ -134,11 +150,32 @@ def start_model(host, scenes, name):
     return pos, mrgb, M.from_list(pos, mrgb), host.scene_depth_for(pos)
 
 
-@functools.lru_cache(maxsize=None)
-def steps_of(name, seed):
-    """-> (start model, start depth, the steps of the scene's sequence as a tuple), generated once per process"""
-    _, _, model, depth = start_model(H, scenes, name)
-    return model, depth, tuple(sequence(seed, model, depth))
+STEPS = len(KINDS) ** 2 + 1 + 2 * len(BOUNDARY_COUNTS)     # of every sequence, or one more: the depth step before boundary batches left over
+_SEQUENCES = {}
+
+
+def steps_of(name, seed, upto=None):
+    """-> (start model, start depth, the steps of the scene's sequence generated so far: the first `upto` at the least, all of them
+    for None).  A sequence is generated once per process and only as far as it is asked for, so that each case of the GPU test pays
+    for its own steps; the list grows in place and is not the caller's to change."""
+    if (name, seed) not in _SEQUENCES:
+        _, _, model, depth = start_model(H, scenes, name)
+        _SEQUENCES[name, seed] = (model, depth, sequence(seed, model, depth), [])
+    model, depth, rest, steps = _SEQUENCES[name, seed]
+    while upto is None or len(steps) < upto:
+        step = next(rest, None)
+        if step is None:
+            break
+        steps.append(step)
+    return model, depth, steps
+
+
+def part_of(name, seed, part):
+    """-> (start model, start depth, steps, first, last): case `part` of the GPU test makes steps[first:last] on the device.  The
+    parts divide STEPS (part_range); the last one runs to the sequence's end, and only it generates the whole sequence."""
+    first, last = part_range(STEPS, part)
+    model, depth, steps = steps_of(name, seed, None if part == PARTS - 1 else last)
+    return model, depth, steps, first, (len(steps) if part == PARTS - 1 else last)
 
 
 def core_depth(start_model):
@@ -288,6 +325,59 @@ def sequence(seed, model, depth):
         yield emit(kind[0], {"call": call, "pos": pos, "mrgb": mrgb, "boundary": count}, [("set", pos, mrgb)], [("set", pos, mrgb)])
         yield emit(kind[1], {"call": call, "pos": pos, "boundary": count}, [("clear", pos)], [("clear", pos)])
 
+    def half_space(axis, cut, upper):
+        lo, hi = [-32768] * 3, [32768] * 3
+        if upper:
+            lo[axis] = cut
+        else:
+            hi[axis] = cut
+        return tuple(lo), tuple(hi)
+
+    def drop(pieces):
+        """the arguments of a drop and what it returns, from the two models (the docstring's "Drops")"""
+        keys = np.array(sorted(m), np.int64).reshape(-1, 3)
+        medians = [int(np.sort(keys[:, ax])[len(keys) // 2]) for ax in range(3)]
+        pos, mrgb = M.to_list(m)
+        voxels = {tuple(p): tuple(c) for p, c in zip(pos.tolist(), mrgb.tolist())}
+        conn = int(rng.choice(K.CONNECTIVITIES))
+
+        def chosen(anchor):
+            """-> what the call returns with this anchor, and its remaining arguments"""
+            if not pieces:
+                return K.detached(voxels, *anchor, conn), {}
+            got = P.detached_pieces(voxels, *anchor, conn)
+            sizes = sorted(set(got[3]["voxels"].tolist()))
+            least, most = 0, None
+            if len(sizes) >= 2:          # sizes[i] .. sizes[j], never the whole range: a detached piece stays
+                i, j = sorted(int(v) for v in rng.integers(0, len(sizes), 2))
+                if (i, j) == (0, len(sizes) - 1):
+                    i, j = ((1, j) if rng.random() < 0.5 else (0, j - 1))
+                least = sizes[i] if i > 0 or rng.random() < 0.5 else 0
+                most = sizes[j] if j < len(sizes) - 1 or rng.random() < 0.5 else None
+                got = P.detached_pieces(voxels, *anchor, conn, least, P.EVERY if most is None else most)
+            cap = (None, len(got[0]), len(got[0]) + int(rng.integers(1, 6)))[int(rng.integers(3))]
+            return got, {"min_voxels": least, "max_voxels": most, "cap": cap}
+
+        floor = min(KEEP, len(m))
+        for _ in range(ANCHOR_DRAWS):
+            axis, upper = int(rng.integers(3)), bool(rng.integers(2))
+            anchor = half_space(axis, medians[axis], upper)
+            got, more = chosen(anchor)
+            if len(m) - len(got[0]) >= floor:
+                break
+        else:
+            held = lambda a: int(X.in_box(keys, a).sum())   # noqa: E731
+            anchor = max((half_space(ax, medians[ax], up) for ax in range(3) for up in (False, True)), key=held)
+            got, more = chosen(anchor)
+            if len(m) - len(got[0]) < floor:
+                anchor = ((-32768,) * 3, (32768,) * 3)
+                got, more = chosen(anchor)
+        args = dict(more, call="drop_detached_pieces" if pieces else "drop_detached", anchor_min=anchor[0], anchor_max=anchor[1],
+                    connectivity=conn, pos=got[0], mrgb=got[1])
+        if pieces:
+            args.update(piece=got[2], table=got[3])
+        return emit(args["call"], args, [("clear", got[0])], [("clear", got[0])])
+
     def step(kind):
         d = state["depth"]
         if kind in ("set_host", "set_device"):
@@ -372,6 +462,8 @@ def sequence(seed, model, depth):
             args = {"call": "carve", "verts": (v.astype(np.float64) + shift).astype(np.float32), "tris": t, "shape": (name, radius),
                     "shift": shift}
             return emit(kind, args, [("clear", pos)], [("clear", pos)])
+        if kind in ("drop_detached", "drop_detached_pieces"):
+            return drop(kind == "drop_detached_pieces")
         raise ValueError(kind)
 
     kinds = circuit(rng)

@@ -50,8 +50,9 @@ def listed(ctx):
     return M.from_list(*ctx.get_voxels())
 
 
-def check_rebuild(H, ctx, model, cam, cfg, frame, what):
-    """ctx holds `model` at the depth its rule gives: decoded list, read-back, node count and frames equal a fresh build's."""
+def check_rebuild(H, ctx, model, cam, cfg, frame, what, also=None):
+    """ctx holds `model` at the depth its rule gives: decoded list, read-back, node count and frames equal a fresh build's.
+    also(ref): what else the caller compares with the fresh build while it is loaded."""
     pos, mrgb = M.to_list(model)
     assert ctx.scene_depth == H.scene_depth_for(pos), what
     assert M.decode_records(*ctx.read_scene(), ctx.scene_depth) == model, what
@@ -60,6 +61,8 @@ def check_rebuild(H, ctx, model, cam, cfg, frame, what):
         assert ref.stats().octree_depth == ctx.scene_depth
         assert ctx.stats().octree_nodes == ref.stats().octree_nodes, what
         assert_same_frames(H, ctx, ref, cfg, frame, what)
+        if also is not None:
+            also(ref)
 
 
 @pytest.mark.parametrize("cfg", CONFIGS, ids=lambda c: "tracer%d-cull%d-fif%d-fpl%d" % c)

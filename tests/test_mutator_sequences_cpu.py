@@ -1,18 +1,20 @@
 """CPU: the generator of the mutator sequences (tests/mutator_sequences.py), for every start scene and seed the GPU test uses: the pair
-coverage, the legality of every step against the model alone, the chunk-boundary batches, and that no step passes for coverage while
-doing nothing."""
+coverage, the legality of every step against the model alone, the chunk-boundary batches, the two drops against components_model and
+pieces_model, and that no step passes for coverage while doing nothing."""
 import numpy as np
 import pytest
 
+import components_model as K
 import edit_model as M
 import mutator_sequences as MS
+import pieces_model as P
 import solid_model as S
 import voxelize_model as V
 
 
 @pytest.fixture(scope="module", params=MS.CASES, ids=lambda c: f"{c[0]}-seed{c[1]}")
 def replay(request):
-    """-> (name, start model, [(step, model before it, depth before it)], final model)"""
+    """-> (name, start model, [(step, model before it, depth before it)], final model, (name, seed))"""
     name, seed = request.param
     model, depth, steps = MS.steps_of(name, seed)
     m, rows = dict(model), []
@@ -20,24 +22,42 @@ def replay(request):
         rows.append((s, dict(m), depth))
         s.apply_to_model(m)
         depth = s.args["depth"]
-    return name, model, rows, m
+    return name, model, rows, m, (name, seed)
 
 
 def test_every_ordered_pair_occurs(replay):
-    _, _, rows, _ = replay
+    _, _, rows, _, _ = replay
     kinds = [s.kind for s, _, _ in rows]
     assert set(kinds) == set(MS.KINDS)
     pairs = set(zip(kinds, kinds[1:]))
     assert pairs == {(a, b) for a in MS.KINDS for b in MS.KINDS}
-    # the circuit itself, without the inserted boundary batches: 145 steps, every pair exactly once
-    own = [s.kind for s, _, _ in rows if "boundary" not in s.args][:145]
-    assert len(own) == 145 and len(set(zip(own, own[1:]))) == 144
+    # the circuit itself, without the inserted boundary batches: 197 steps, every pair exactly once
+    assert len(MS.KINDS) == 14
+    own = [s.kind for s, _, _ in rows if "boundary" not in s.args][:197]
+    assert len(own) == 197 and len(set(zip(own, own[1:]))) == 196
+
+
+def test_the_parts_cover_the_sequence(replay):
+    """the GPU test's cases: consecutive ranges with one step of overlap, the last to the sequence's end, each generated only as far
+    as its own last step"""
+    _, _, rows, _, (name, seed) = replay
+    assert len(rows) in (MS.STEPS, MS.STEPS + 1) and MS.STEPS == 205
+    ends = 0
+    for part in range(MS.PARTS):
+        _, _, steps, first, last = MS.part_of(name, seed, part)
+        assert first == max(ends - 1, 0) and first < last <= len(steps)
+        assert [s.kind for s in steps[:last]] == [s.kind for s, _, _ in rows[:last]]
+        ends = last
+    assert ends == len(rows)
+    fresh = MS.sequence(seed, rows[0][1], rows[0][2])               # generated step by step: the same steps as generated whole
+    for (s, _, _), again in zip(rows[:12], fresh):
+        assert s.kind == again.kind and s.args["depth"] == again.args["depth"] and len(s.args["twin"]) == len(again.args["twin"])
 
 
 def test_the_circuit_is_eulerian_for_any_seed():
     for seed in range(20):
         order = MS.circuit(np.random.default_rng(seed))
-        assert len(order) == 145 and sorted(zip(order, order[1:])) == sorted((a, b) for a in MS.KINDS for b in MS.KINDS)
+        assert len(order) == 197 and sorted(zip(order, order[1:])) == sorted((a, b) for a in MS.KINDS for b in MS.KINDS)
 
 
 def positions_of(step):
@@ -45,7 +65,7 @@ def positions_of(step):
 
 
 def test_every_step_is_legal_against_the_model(replay):
-    _, _, rows, _ = replay
+    _, _, rows, _, _ = replay
     shrinks = grows = 0
     for i, (s, before, depth) in enumerate(rows):
         what = (i, s.kind)
@@ -75,12 +95,13 @@ def test_every_step_is_legal_against_the_model(replay):
     assert any(s.kind == "far_set" and after > before for (s, _, before), after in zip(rows, depths[1:]))   # the refusal's step
     if replay[0] == "menger_device":          # the GPU test makes the refusal in every case whose steps hold one: the first does
         steps = [s for s, _, _ in rows]
-        at = MS.refusal_step(steps, rows[0][2], *MS.part_range(len(steps), 0))
+        assert MS.part_of(*replay[4], 0)[3:] == MS.part_range(MS.STEPS, 0)
+        at = MS.refusal_step(steps, rows[0][2], *MS.part_range(MS.STEPS, 0))
         assert at is not None and steps[at].kind == "far_set" and steps[at].args["depth"] > rows[at][2]
 
 
 def test_the_boundary_batches(replay):
-    _, _, rows, _ = replay
+    _, _, rows, _, _ = replay
     kinds = [s.kind for s, _, _ in rows]
     first_compact = kinds.index("compact")
     counts = []
@@ -101,8 +122,53 @@ def test_the_boundary_batches(replay):
     assert sorted(counts) == sorted(MS.BOUNDARY_COUNTS)
 
 
+def voxel_bytes(model):
+    """the edit model's dict as the components and pieces models take it: {pos: (m, r, g, b)}"""
+    pos, mrgb = M.to_list(model)
+    return {tuple(p): tuple(c) for p, c in zip(pos.tolist(), mrgb.tolist())}
+
+
+def test_the_drops_equal_the_models(replay):
+    """every drop step: its arguments are legal, what it says the call returns is the model's list for those arguments, and its
+    effect is the clear of that list; per sequence the drops do remove something, by both calls, and leave KEEP voxels"""
+    _, _, rows, _, _ = replay
+    removed = {"drop_detached": 0, "drop_detached_pieces": 0}
+    some_left_behind = 0
+    for i, (s, before, depth) in enumerate(rows):
+        if s.kind not in removed:
+            continue
+        what, a = (i, s.kind), s.args
+        assert a["call"] == s.kind and a["connectivity"] in (6, 18, 26) and a["depth"] == depth and not a["grows"], what
+        lo, hi = a["anchor_min"], a["anchor_max"]
+        assert all(-32768 <= l <= h <= 32768 for l, h in zip(lo, hi)), what
+        assert sum((l, h) != (-32768, 32768) for l, h in zip(lo, hi)) <= 1, what                    # a half-space
+        voxels = voxel_bytes(before)
+        if s.kind == "drop_detached":
+            want = K.detached(voxels, lo, hi, a["connectivity"])
+        else:
+            most = P.EVERY if a["max_voxels"] is None else a["max_voxels"]
+            want = P.detached_pieces(voxels, lo, hi, a["connectivity"], a["min_voxels"], most)
+            assert np.array_equal(a["piece"], want[2]) and a["piece"].dtype == np.uint32, what
+            assert a["table"].dtype == P.PIECE and a["table"].tobytes() == want[3].tobytes(), what
+            assert a["cap"] is None or len(want[0]) <= a["cap"] <= len(want[0]) + 5, what             # never below the count
+            every = P.detached_pieces(voxels, lo, hi, a["connectivity"])[3]["voxels"].tolist()
+            if len(set(every)) >= 2:
+                assert 0 < len(want[3]) < len(every), what
+            some_left_behind += 0 < len(want[3]) < len(every)
+        assert np.array_equal(a["pos"], want[0]) and a["pos"].dtype == np.int16, what
+        assert np.array_equal(a["mrgb"], want[1]) and a["mrgb"].dtype == np.uint8, what
+        gone = set(map(tuple, a["pos"].tolist()))
+        assert len(gone) == len(a["pos"]) and gone <= set(before), what
+        after = s.apply_to_model(dict(before))
+        assert after == {p: w for p, w in before.items() if p not in gone}, what
+        assert a["twin"] == ([("clear", a["pos"])] if len(gone) else []), what
+        assert len(after) >= MS.KEEP, what
+        removed[s.kind] += len(gone) > 0
+    assert removed["drop_detached"] >= 1 and removed["drop_detached_pieces"] >= 1 and some_left_behind >= 1, (removed, some_left_behind)
+
+
 def test_no_step_counts_without_doing_something(replay):
-    _, _, rows, final = replay
+    _, _, rows, final, _ = replay
     for i, (s, before, depth) in enumerate(rows):
         after = s.apply_to_model(dict(before))
         if s.kind in ("mesh", "carve", "set_host", "set_device", "far_set"):
