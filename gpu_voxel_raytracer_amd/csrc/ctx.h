@@ -14,6 +14,7 @@
 //   api_compact.hip  an edited scene re-laid as a fresh build lies, and the storage counts (vxrt_compact.h)
 //   api_query.hip    voxel lookups and bounded ray casts against the scene from device memory (vxrt_query.h)
 //   api_transform.hip  a device voxel list resampled under a fixed-point affine map (vxrt_transform.h)
+//   api_setops.hip   two device voxel lists combined: union, intersection, difference, delta (vxrt_setops.h)
 #pragma once
 #include <hip/hip_runtime.h>
 

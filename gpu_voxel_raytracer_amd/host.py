@@ -234,6 +234,9 @@ PICK_HIT_DTYPE = np.dtype([("status", np.uint32), ("time", np.float32), ("normal
                            ("leaf", np.int32)])
 PICK_MISS, PICK_HIT, PICK_CAP = 0, 1, 2
 
+# vxrt_list_op (include/vxrt_setops.h)
+LIST_UNION, LIST_INTERSECT, LIST_DIFFERENCE, LIST_XOR, LIST_CHANGED = 0, 1, 2, 3, 4
+
 
 class Camera:
     """Camera, src/camera.rs:5-9.  Default = the reference's start camera, src/context.rs:618-622."""
@@ -1287,6 +1290,86 @@ class Context:
             return self.transform_voxels(pos, mrgb, pull, (0, 0, 0), (0, 0, 0))
         lo, hi = pos.amin(dim=0).cpu().numpy(), pos.amax(dim=0).cpu().numpy()
         return self.transform_voxels(pos, mrgb, pull, *rigid_box(lo, hi, rotation, pivot, translation))
+
+    def combine_voxels(self, a_pos, a_mrgb, b_pos, b_mrgb, op, cap=None):
+        """vxrt_combine_voxels_device (include/vxrt_setops.h): the lists A and B combined under op (LIST_UNION: in either, B's bytes
+        where both have it; LIST_INTERSECT: in both, A's bytes; LIST_DIFFERENCE: in A and not in B; LIST_XOR: in exactly one;
+        LIST_CHANGED: in B and absent from A or with other bytes there) -> (pos int16 [k,3], mrgb uint8 [k,4]) as torch tensors on the
+        context's device, in path order, each position once.  a_mrgb=None: positions only (b_mrgb must be None too, LIST_CHANGED is
+        refused) and the second value is None.  With bytes, LIST_UNION, LIST_XOR and LIST_CHANGED need b_mrgb for a B with entries;
+        LIST_INTERSECT and LIST_DIFFERENCE take B as a mask and ignore b_mrgb.  The lists (int16 [n,3], uint8 [n,4]) are contiguous
+        torch tensors on the context's device, or numpy arrays, which are uploaded with torch once every check has passed.  cap as
+        transform_voxels'.  Ordered on both sides against torch's current stream.  No scene is needed or touched."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        for pos, mrgb, which in ((a_pos, a_mrgb, "a"), (b_pos, b_mrgb, "b")):
+            self._query_check(pos, which + "_pos", torch.int16, 3)
+            if mrgb is not None:
+                self._query_check(mrgb, which + "_mrgb", torch.uint8, 4)
+                if len(mrgb) != len(pos):
+                    raise ValueError(f"one {which}_mrgb per position of {which}_pos")
+        if isinstance(op, bool) or not isinstance(op, (int, np.integer)) or not LIST_UNION <= op <= LIST_CHANGED:
+            raise ValueError("op must be one of LIST_UNION .. LIST_CHANGED")
+        if a_mrgb is None:
+            if b_mrgb is not None:
+                raise ValueError("b_mrgb without a_mrgb")
+            if op == LIST_CHANGED:
+                raise ValueError("LIST_CHANGED compares bytes: a_mrgb and b_mrgb are needed")
+        elif b_mrgb is None and len(b_pos) and op in (LIST_UNION, LIST_XOR, LIST_CHANGED):
+            raise ValueError("this op takes bytes from B: b_mrgb is needed")
+        self._cap(cap)
+        a_pos, b_pos = self._query_tensor(a_pos), self._query_tensor(b_pos)
+        with_vals = a_mrgb is not None
+        a_mrgb = None if a_mrgb is None else self._query_tensor(a_mrgb)
+        b_mrgb = None if b_mrgb is None else self._query_tensor(b_mrgb)
+        na, nb = len(a_pos), len(b_pos)
+        # an empty tensor has no address: "bytes, and no entries" is said with an address that is never read
+        spare = torch.empty((1, 4), dtype=torch.uint8, device=dev) if with_vals and na == 0 else None
+        ptr = lambda t: None if t is None or t.numel() == 0 else C.c_void_p(t.data_ptr())   # noqa: E731
+        got = C.c_size_t(0)
+
+        def run(out_pos, out_mrgb, room):
+            self._chk(self._L.vxrt_combine_voxels_device(
+                self._h, ptr(a_pos), ptr(spare) if spare is not None else ptr(a_mrgb), C.c_size_t(na), ptr(b_pos), ptr(b_mrgb), C.c_size_t(nb),
+                C.c_uint32(int(op)), ptr(out_pos), ptr(out_mrgb), C.c_size_t(room), C.byref(got)), "vxrt_combine_voxels_device")
+        if na == 0 and nb == 0:
+            cap = 0
+        if cap is None:
+            with self._ordered():
+                run(None, None, 0)
+            cap = int(got.value)
+        cap = int(cap)
+        out_pos = torch.empty((cap, 3), dtype=torch.int16, device=dev)
+        out_mrgb = torch.empty((cap, 4), dtype=torch.uint8, device=dev) if with_vals else None
+        if cap:
+            with self._ordered():
+                run(out_pos, out_mrgb, cap)
+        k = int(got.value) if cap else 0
+        return out_pos[:k], (None if out_mrgb is None else out_mrgb[:k])
+
+    def count_common(self, a_pos, b_pos):
+        """combine_voxels, counting LIST_INTERSECT only (the collision test of two lists): how many distinct positions both hold."""
+        import torch
+        self._query_check(a_pos, "a_pos", torch.int16, 3)
+        self._query_check(b_pos, "b_pos", torch.int16, 3)
+        a_pos, b_pos = self._query_tensor(a_pos), self._query_tensor(b_pos)
+        got = C.c_size_t(0)
+        if len(a_pos) and len(b_pos):
+            with self._ordered():
+                self._chk(self._L.vxrt_combine_voxels_device(
+                    self._h, C.c_void_p(a_pos.data_ptr()), None, C.c_size_t(len(a_pos)), C.c_void_p(b_pos.data_ptr()), None, C.c_size_t(len(b_pos)),
+                    C.c_uint32(LIST_INTERSECT), None, None, C.c_size_t(0), C.byref(got)), "vxrt_combine_voxels_device")
+        return int(got.value)
+
+    def diff_voxels(self, before_pos, before_mrgb, after_pos, after_mrgb):
+        """The delta between two snapshots -> (set_pos, set_mrgb, clear_pos): LIST_CHANGED(before, after), the voxels that are new
+        or have other bytes, and the positions of LIST_DIFFERENCE(before, after), the voxels that are gone.  edit_voxels_device(set_pos,
+        set_mrgb) followed by clear_voxels_device(clear_pos) turns a scene holding `before` into one holding `after`."""
+        if before_mrgb is None or after_mrgb is None:
+            raise ValueError("diff_voxels compares bytes: before_mrgb and after_mrgb are needed")
+        set_pos, set_mrgb = self.combine_voxels(before_pos, before_mrgb, after_pos, after_mrgb, LIST_CHANGED)
+        clear_pos, _ = self.combine_voxels(before_pos, None, after_pos, None, LIST_DIFFERENCE)
+        return set_pos, set_mrgb, clear_pos
 
     def _box(self, box_min, box_max):
         if (box_min is None) != (box_max is None):

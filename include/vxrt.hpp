@@ -28,6 +28,7 @@
 #include "vxrt_pieces.h"
 #include "vxrt_query.h"
 #include "vxrt_scene_depth.h"
+#include "vxrt_setops.h"
 #include "vxrt_solid.h"
 #include "vxrt_transform.h"
 #include "vxrt_voxelize.h"
@@ -285,6 +286,16 @@ class Context {
         size_t count = 0;
         check(vxrt_transform_voxels_device(ctx_, pos, mrgb, n, &pull, box_min.data(), box_max.data(), out_pos, out_mrgb, cap, &count),
               "vxrt_transform_voxels_device");
+        return count;
+    }
+    // vxrt_setops.h: the lists A and B (device memory; a_mrgb == nullptr: positions only) combined under op, in path order.
+    // out_pos == out_mrgb == nullptr counts only.  Returns the number of voxels of the result.
+    size_t combine_voxels_device(const int16_t (*a_pos)[3], const uint8_t (*a_mrgb)[4], size_t na, const int16_t (*b_pos)[3],
+                                 const uint8_t (*b_mrgb)[4], size_t nb, vxrt_list_op op, int16_t (*out_pos)[3] = nullptr,
+                                 uint8_t (*out_mrgb)[4] = nullptr, size_t cap = 0) {
+        size_t count = 0;
+        check(vxrt_combine_voxels_device(ctx_, a_pos, a_mrgb, na, b_pos, b_mrgb, nb, uint32_t(op), out_pos, out_mrgb, cap, &count),
+              "vxrt_combine_voxels_device");
         return count;
     }
     // vxrt_set_voxel_grid (vxrt_grid.h): dims[0] x dims[1] x dims[2] cells in device memory of the context's device, C order
