@@ -219,7 +219,8 @@ def rigid_pull(rotation, pivot=(0, 0, 0), translation=(0, 0, 0)):
 def rigid_box(src_min, src_max, rotation, pivot=(0, 0, 0), translation=(0, 0, 0)):
     """The destination box of a list whose positions span src_min .. src_max (inclusive) under rigid_pull's motion -> (box_min,
     box_max), half-open, three ints each: the eight corners of the cell box [src_min, src_max + 1] mapped forward, floor / ceil,
-    grown by 2 cells per side (the rounding of m moves a pulled centre by less than half a cell) and clipped to [-32768, 32768]."""
+    grown by 2 cells per side (the rounding of m, at most 2^-17 per entry times a coordinate below 2^15, three terms, moves a pulled
+    centre by up to three quarters of a cell, and the rounding of t by 2^-17 more) and clipped to [-32768, 32768]."""
     r, p, u = _rigid_args(rotation, pivot, translation)
     lo, hi = np.asarray(src_min, np.float64).reshape(3), np.asarray(src_max, np.float64).reshape(3) + 1.0
     corners = np.array([[(lo, hi)[(k >> ax) & 1][ax] for ax in range(3)] for k in range(8)], np.float64)

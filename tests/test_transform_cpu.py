@@ -364,13 +364,37 @@ int main() {
 """
 
 
-def test_the_kernels_arithmetic_under_the_sanitizers(tmp_path):
+def build_rule_program(tmp_path):
+    """DRIVER around csrc/transform_rule.h under the undefined-behaviour and address sanitizers -> the program's path"""
     src = tmp_path / "rule.cpp"
     src.write_text(DRIVER)
     exe = tmp_path / "rule"
     build = subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=undefined,address", "-fno-sanitize-recover=all", "-static-libasan",
                             "-I", CSRC, str(src), "-o", str(exe)], capture_output=True, text=True)
     assert build.returncode == 0, build.stderr
+    return exe
+
+
+def rule_program_agrees_with_the_model(exe, cases):
+    """(m, t, d) triples through the program: its output equals the model's and the sanitizers report nothing -> how many are in range"""
+    text = "".join(" ".join(str(int(v)) for row in m for v in row) + " " + " ".join(str(int(v)) for v in t) + " " + " ".join(str(int(v)) for v in d) + "\n"
+                   for m, t, d in cases)
+    run = subprocess.run([str(exe)], input=text, capture_output=True, text=True)
+    assert run.returncode == 0 and not run.stderr.strip(), run.stderr[-2000:]
+    lines = run.stdout.split("\n")[:-1]
+    assert len(lines) == len(cases)
+    in_count = 0
+    for (m, t, d), line in zip(cases, lines):
+        s = T.pull_cell(m, t, d)
+        inside = T.in_range(s)
+        in_count += inside
+        want = f"{s[0]} {s[1]} {s[2]} {1 if inside else 0} {T.path_key(s) if inside else 0}"
+        assert line == want, (m, t, d, line, want)
+    return in_count
+
+
+def test_the_kernels_arithmetic_under_the_sanitizers(tmp_path):
+    exe = build_rule_program(tmp_path)
     rng = np.random.default_rng(17)
     big_m, big_t = T.M_LIMIT, T.T_LIMIT
     cases = []
@@ -390,17 +414,5 @@ def test_the_kernels_arithmetic_under_the_sanitizers(tmp_path):
         m = rng.integers(-big_m if wide else -2 * T.ONE, (big_m if wide else 2 * T.ONE) + 1, (3, 3)).tolist()
         t = rng.integers(-big_t if wide else -(T.ONE << 15), (big_t if wide else T.ONE << 15) + 1, 3).tolist()
         cases.append((m, t, rng.integers(-32768, 32768, 3).tolist()))
-    text = "".join(" ".join(str(int(v)) for row in m for v in row) + " " + " ".join(str(int(v)) for v in t) + " " + " ".join(str(int(v)) for v in d) + "\n"
-                   for m, t, d in cases)
-    run = subprocess.run([str(exe)], input=text, capture_output=True, text=True)
-    assert run.returncode == 0 and not run.stderr.strip(), run.stderr[-2000:]
-    lines = run.stdout.split("\n")[:-1]
-    assert len(lines) == len(cases)
-    in_count = 0
-    for (m, t, d), line in zip(cases, lines):
-        s = T.pull_cell(m, t, d)
-        inside = T.in_range(s)
-        in_count += inside
-        want = f"{s[0]} {s[1]} {s[2]} {1 if inside else 0} {T.path_key(s) if inside else 0}"
-        assert line == want, (m, t, d, line, want)
+    in_count = rule_program_agrees_with_the_model(exe, cases)
     assert 50 < in_count < len(cases) - 50                                  # both answers of the range test are exercised
