@@ -15,6 +15,7 @@
 //   api_query.hip    voxel lookups and bounded ray casts against the scene from device memory (vxrt_query.h)
 //   api_transform.hip  a device voxel list resampled under a fixed-point affine map (vxrt_transform.h)
 //   api_setops.hip   two device voxel lists combined: union, intersection, difference, delta (vxrt_setops.h)
+//   api_morph.hip    a device voxel list dilated, eroded, or cut to its surface layer or margin ring (vxrt_morph.h)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -298,6 +299,8 @@ struct vxrt_ctx {
     uint64_t split_launches = 0;        // trace launches that went out as two grids
     std::vector<hipStream_t> low_streams;
     std::vector<hipEvent_t> low_fork, low_join;
+
+    int morph_tile_lookup = 0;    // vxrt_debug_morph_tile_lookup: vxrt_morph_voxels_device asks the block's LDS tile before the whole array
 
     // touch map (vxrt_debug_touch_map; -DVXRT_VARIANTS=1 builds): one bit per 64-byte line of the node records / the leaf words
     uint32_t* d_touch_nodes = nullptr;

@@ -237,6 +237,8 @@ PICK_MISS, PICK_HIT, PICK_CAP = 0, 1, 2
 
 # vxrt_list_op (include/vxrt_setops.h)
 LIST_UNION, LIST_INTERSECT, LIST_DIFFERENCE, LIST_XOR, LIST_CHANGED = 0, 1, 2, 3, 4
+# vxrt_morph_op (include/vxrt_morph.h)
+MORPH_DILATE, MORPH_ERODE, MORPH_SURFACE, MORPH_MARGIN = 0, 1, 2, 3
 
 
 class Camera:
@@ -1371,6 +1373,69 @@ class Context:
         set_pos, set_mrgb = self.combine_voxels(before_pos, before_mrgb, after_pos, after_mrgb, LIST_CHANGED)
         clear_pos, _ = self.combine_voxels(before_pos, None, after_pos, None, LIST_DIFFERENCE)
         return set_pos, set_mrgb, clear_pos
+
+    def _morph_check(self, pos, mrgb, connectivity, steps):
+        import torch
+        self._query_check(pos, "pos", torch.int16, 3)
+        if mrgb is not None:
+            self._query_check(mrgb, "mrgb", torch.uint8, 4)
+            if len(mrgb) != len(pos):
+                raise ValueError("one mrgb per position")
+        if isinstance(connectivity, bool) or not isinstance(connectivity, (int, np.integer)) or connectivity not in (6, 18, 26):
+            raise ValueError("connectivity must be 6, 18 or 26")
+        if isinstance(steps, bool) or not isinstance(steps, (int, np.integer)) or not 1 <= steps <= 64:
+            raise ValueError("steps must be an integer of 1 .. 64")
+
+    def morph_voxels(self, pos, mrgb, op, connectivity=6, steps=1, cap=None):
+        """vxrt_morph_voxels_device (include/vxrt_morph.h): the list pos / mrgb under op (MORPH_DILATE: the set and every cell with a
+        neighbour in it, a new cell taking the bytes of its first source; MORPH_ERODE: the cells whose neighbours are all in the set;
+        MORPH_SURFACE: the set without its erosion; MORPH_MARGIN: the dilation without the set), with the 6, 18 or 26 neighbourhood,
+        `steps` (1 .. 64) cells deep -> (pos int16 [k,3], mrgb uint8 [k,4]) as torch tensors on the context's device, in path order,
+        each position once.  mrgb=None: positions only, and the second value is None.  pos (int16 [n,3]) and mrgb (uint8 [n,4]) are
+        contiguous torch tensors on the context's device, or numpy arrays, which are uploaded with torch once every check has
+        passed.  cap as transform_voxels'.  Ordered on both sides against torch's current stream.  No scene is needed or touched."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        self._morph_check(pos, mrgb, connectivity, steps)
+        if isinstance(op, bool) or not isinstance(op, (int, np.integer)) or not MORPH_DILATE <= op <= MORPH_MARGIN:
+            raise ValueError("op must be one of MORPH_DILATE .. MORPH_MARGIN")
+        self._cap(cap)
+        pos = self._query_tensor(pos)
+        mrgb = None if mrgb is None else self._query_tensor(mrgb)
+        n = len(pos)
+        got = C.c_size_t(0)
+
+        def run(out_pos, out_mrgb, room):
+            self._chk(self._L.vxrt_morph_voxels_device(
+                self._h, C.c_void_p(pos.data_ptr()), None if mrgb is None else C.c_void_p(mrgb.data_ptr()), C.c_size_t(n),
+                C.c_uint32(int(op)), C.c_uint32(int(connectivity)), C.c_uint32(int(steps)),
+                None if out_pos is None else C.c_void_p(out_pos.data_ptr()), None if out_mrgb is None else C.c_void_p(out_mrgb.data_ptr()),
+                C.c_size_t(room), C.byref(got)), "vxrt_morph_voxels_device")
+        if n == 0:          # an empty tensor has no address to tell "no mrgb" from "no entries" by: the result is empty either way
+            cap = 0
+        if cap is None:
+            with self._ordered():
+                run(None, None, 0)
+            cap = int(got.value)
+        cap = int(cap)
+        out_pos = torch.empty((cap, 3), dtype=torch.int16, device=dev)
+        out_mrgb = None if mrgb is None else torch.empty((cap, 4), dtype=torch.uint8, device=dev)
+        if cap:
+            with self._ordered():
+                run(out_pos, out_mrgb, cap)
+        k = int(got.value) if cap else 0
+        return out_pos[:k], (None if out_mrgb is None else out_mrgb[:k])
+
+    def close_voxels(self, pos, mrgb, connectivity=6, steps=1):
+        """morph_voxels MORPH_DILATE, then MORPH_ERODE of the result: pinholes and gaps up to 2 * steps cells wide are filled, with the
+        bytes dilation gave them."""
+        self._morph_check(pos, mrgb, connectivity, steps)
+        return self.morph_voxels(*self.morph_voxels(pos, mrgb, MORPH_DILATE, connectivity, steps), MORPH_ERODE, connectivity, steps)
+
+    def open_voxels(self, pos, mrgb, connectivity=6, steps=1):
+        """morph_voxels MORPH_ERODE, then MORPH_DILATE of the result: specks and spurs up to 2 * steps cells wide are removed."""
+        self._morph_check(pos, mrgb, connectivity, steps)
+        return self.morph_voxels(*self.morph_voxels(pos, mrgb, MORPH_ERODE, connectivity, steps), MORPH_DILATE, connectivity, steps)
 
     def _box(self, box_min, box_max):
         if (box_min is None) != (box_max is None):

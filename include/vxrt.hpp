@@ -29,6 +29,7 @@
 #include "vxrt_query.h"
 #include "vxrt_scene_depth.h"
 #include "vxrt_setops.h"
+#include "vxrt_morph.h"
 #include "vxrt_solid.h"
 #include "vxrt_transform.h"
 #include "vxrt_voxelize.h"
@@ -296,6 +297,16 @@ class Context {
         size_t count = 0;
         check(vxrt_combine_voxels_device(ctx_, a_pos, a_mrgb, na, b_pos, b_mrgb, nb, uint32_t(op), out_pos, out_mrgb, cap, &count),
               "vxrt_combine_voxels_device");
+        return count;
+    }
+    // vxrt_morph.h: the list (device memory; mrgb == nullptr: positions only) dilated, eroded, or its surface layer or margin ring,
+    // under the 6, 18 or 26 neighbourhood, `steps` cells deep, in path order.  out_pos == out_mrgb == nullptr counts only.  Returns
+    // the number of voxels of the result.
+    size_t morph_voxels_device(const int16_t (*pos)[3], const uint8_t (*mrgb)[4], size_t n, vxrt_morph_op op, uint32_t connectivity = 6,
+                               uint32_t steps = 1, int16_t (*out_pos)[3] = nullptr, uint8_t (*out_mrgb)[4] = nullptr, size_t cap = 0) {
+        size_t count = 0;
+        check(vxrt_morph_voxels_device(ctx_, pos, mrgb, n, uint32_t(op), connectivity, steps, out_pos, out_mrgb, cap, &count),
+              "vxrt_morph_voxels_device");
         return count;
     }
     // vxrt_set_voxel_grid (vxrt_grid.h): dims[0] x dims[1] x dims[2] cells in device memory of the context's device, C order

@@ -147,6 +147,11 @@ int vxrt_debug_fused_profile(vxrt_ctx* ctx, uint64_t out[8]);
 int vxrt_debug_touch_map(vxrt_ctx* ctx, uint32_t enable);
 int vxrt_debug_touch_count(vxrt_ctx* ctx, uint64_t out[6], uint32_t reset);
 
+/* Measurement hook of vxrt_morph.h (scripts/morph_latency.py): enable = 1 makes vxrt_morph_voxels_device look a neighbour up in the
+ * block's own 2 048 keys, staged in LDS, before it asks the whole key array (morph_mask_kernel<true>); the results are the same
+ * bytes.  enable = 0 (the default) is the product's lookup, which asks the whole array at once: it measured faster. */
+int vxrt_debug_morph_tile_lookup(vxrt_ctx* ctx, uint32_t enable);
+
 /* What this build of the library contains: VXRT_FEATURE_VARIANTS = it was compiled with -DVXRT_VARIANTS=1 and also holds the
  * schedules and the scene format that measured slower on MI355X and are kept for comparison (tracers 2, 3, 5; the wide scene
  * records).  The default build holds tracers 1 and 4 over the 8-byte records and refuses the others with VXRT_E_INVALID. */

@@ -1,0 +1,469 @@
+"""CPU: the morphology interface (include/vxrt_morph.h) — plain C, declared once, exported with C linkage by both libraries, refused
+without a context — the Python wrappers' signatures and argument checks, which run before any library call; the rule's model
+(morph_model.py) against a dense numpy grid, against counts known by hand and against the identities the ops must satisfy; and the
+kernels' own arithmetic (csrc/morph_rule.h: the offset table, the neighbour key, the two lookups, the ops' reading of a mask),
+compiled by g++ with the undefined-behaviour and address sanitizers into a program of its own that walks a key list block by block
+and thread by thread as the kernels do, against the model."""
+import ctypes as C
+import inspect
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import morph_model as M
+import transform_model as T
+from conftest import ROOT
+from test_components_cpu import bare_context, declared
+
+FUNCTIONS = ["vxrt_morph_voxels_device"]
+HEADER = "vxrt_morph.h"
+NEW_SOURCES = ("morph.hip", "api_morph.hip", "morph.h", "morph_rule.h")
+CSRC = os.path.join(ROOT, "gpu_voxel_raytracer_amd", "csrc")
+
+
+# ---- the header, the libraries, the wrappers ---------------------------------------------------------------------------------------
+def test_header_declares_exactly_the_one_entry_point():
+    assert declared(HEADER) == FUNCTIONS
+    for other in sorted(os.listdir(os.path.join(ROOT, "include"))):
+        if other.endswith(".h") and other != HEADER:
+            assert not set(FUNCTIONS) & set(declared(other)), other
+    text = open(os.path.join(ROOT, "include", HEADER)).read()
+    assert '#include "vxrt.h"' in text and "typedef enum vxrt_morph_op" in text
+    assert "last entry of a position wins" in text and "bit 7" in text and "path order" in text and "do not wrap" in text
+    assert f'#include "{HEADER}"' in open(os.path.join(ROOT, "include", "vxrt.hpp")).read()
+    for doc in ("README.md", "INTEGRATION.md", "DESIGN.md"):
+        assert HEADER in open(os.path.join(ROOT, doc)).read(), doc
+    assert "api_morph.hip" in open(os.path.join(CSRC, "ctx.h")).read()
+    assert len(declared("vxrt.h")) <= 40
+
+
+def test_header_is_plain_c(tmp_path):
+    hdr = os.path.join(ROOT, "include", HEADER)
+    chk = subprocess.run(["gcc", "-std=c11", "-Wall", "-Wextra", "-pedantic", "-fsyntax-only", "-x", "c", "-I", os.path.join(ROOT, "include"), hdr],
+                         capture_output=True, text=True)
+    assert chk.returncode == 0 and not chk.stderr.strip(), chk.stderr
+    src = tmp_path / "c.c"
+    src.write_text(f'#include "{HEADER}"\n'
+                   'typedef char ops_are_0_to_3[VXRT_MORPH_DILATE == 0 && VXRT_MORPH_ERODE == 1 && VXRT_MORPH_SURFACE == 2 && VXRT_MORPH_MARGIN == 3 ? 1 : -1];\n'
+                   'int main(void) {\n'
+                   '    size_t n = 7;\n'
+                   '    vxrt_morph_op op = VXRT_MORPH_SURFACE;\n'
+                   '    int rc = vxrt_morph_voxels_device(0, 0, 0, 0, (uint32_t)op, 26, 2, 0, 0, 0, &n);\n'
+                   '    return rc == VXRT_E_INVALID && n == 7 ? 0 : 1;\n'
+                   '}\n')
+    subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), "-c", str(src), "-o",
+                    str(tmp_path / "c.o")], check=True)
+    cpp = tmp_path / "c.cpp"
+    cpp.write_text('#include "vxrt.hpp"\n'
+                   'size_t f(vxrt::Context& c, const int16_t (*p)[3], const uint8_t (*m)[4], int16_t (*q)[3], uint8_t (*w)[4]) {\n'
+                   '    return c.morph_voxels_device(p, nullptr, 1, VXRT_MORPH_ERODE) + c.morph_voxels_device(p, m, 1, VXRT_MORPH_DILATE, 26, 3, q, w, 27); }\n')
+    subprocess.run(["g++", "-std=c++17", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), "-fsyntax-only", str(cpp)], check=True)
+
+
+def test_both_libraries_export_it_with_c_linkage(H):
+    from gpu_voxel_raytracer_amd import _build
+    for lib in (_build.LIB, H.variants_library()):
+        out = subprocess.run(["nm", "-D", "--defined-only", lib], capture_output=True, text=True).stdout
+        exported = [l.split()[-1] for l in out.splitlines() if " T " in l]
+        for f in FUNCTIONS:
+            assert f in exported, (lib, f)          # unmangled => extern "C"
+    assert H.lib().vxrt_abi_version() == 6
+
+
+def test_a_null_context_is_invalid(H):
+    L = H.lib()
+    pos = np.zeros((2, 3), np.int16)
+    mrgb = np.full((2, 4), 9, np.uint8)
+    out_pos = np.full((64, 3), 0x5A5A, np.uint16)
+    out_mrgb = np.full((64, 4), 0xA5, np.uint8)
+    p = lambda a: a.ctypes.data_as(C.c_void_p)   # noqa: E731
+    n = C.c_size_t(7)
+    for count in (2, 0, 1 << 32):
+        k = C.c_size_t(count)
+        for op, c, steps in ((0, 6, 1), (3, 26, 64), (4, 6, 1), (0, 7, 1), (1, 18, 0), (2, 18, 65)):
+            args = (C.c_uint32(op), C.c_uint32(c), C.c_uint32(steps))
+            assert L.vxrt_morph_voxels_device(None, p(pos), p(mrgb), k, *args, p(out_pos), p(out_mrgb), C.c_size_t(64), C.byref(n)) == H.E_INVALID
+            assert L.vxrt_morph_voxels_device(None, p(pos), None, k, *args, None, None, C.c_size_t(0), C.byref(n)) == H.E_INVALID
+            assert L.vxrt_morph_voxels_device(None, None, None, k, *args, None, None, C.c_size_t(0), None) == H.E_INVALID
+    assert b"null context" in L.vxrt_last_error()
+    assert n.value == 7 and (out_pos == 0x5A5A).all() and (out_mrgb == 0xA5).all() and not pos.any() and (mrgb == 9).all()
+
+
+def test_the_new_sources_are_built_into_both_libraries():
+    from gpu_voxel_raytracer_amd import _build
+    for f in NEW_SOURCES:
+        assert os.path.exists(os.path.join(CSRC, f)), f
+    assert "morph.hip" in _build.SOURCES and "api_morph.hip" in _build.SOURCES      # the variants build takes SOURCES too
+    assert "morph.h" in _build.HEADERS and "morph_rule.h" in _build.HEADERS and any(h.endswith(HEADER) for h in _build.HEADERS)
+    rule = open(os.path.join(CSRC, "morph_rule.h")).read()
+    assert "#include <hip" not in rule and '#include "' not in rule           # nothing from HIP, nothing of the project's
+
+
+def test_the_wrapper_signatures_and_constants(H):
+    params = inspect.signature(H.Context.morph_voxels).parameters
+    assert list(params) == ["self", "pos", "mrgb", "op", "connectivity", "steps", "cap"]
+    assert (params["connectivity"].default, params["steps"].default, params["cap"].default) == (6, 1, None)
+    for f in (H.Context.close_voxels, H.Context.open_voxels):
+        params = inspect.signature(f).parameters
+        assert list(params) == ["self", "pos", "mrgb", "connectivity", "steps"]
+        assert (params["connectivity"].default, params["steps"].default) == (6, 1)
+    assert (H.MORPH_DILATE, H.MORPH_ERODE, H.MORPH_SURFACE, H.MORPH_MARGIN) == (0, 1, 2, 3) == M.OPS
+
+
+def test_the_wrappers_check_their_arguments_before_any_library_call(H):
+    import torch
+    ctx = bare_context(H)
+    try:
+        pos, mrgb = np.zeros((5, 3), np.int16), np.zeros((5, 4), np.uint8)
+        calls = (lambda p, c, **kw: ctx.morph_voxels(p, c, H.MORPH_DILATE, **kw), ctx.close_voxels, ctx.open_voxels)
+        for call in calls:
+            for bad in (pos.astype(np.int32), pos.astype(np.uint16), pos.astype(np.float32), torch.zeros((5, 3), dtype=torch.int32), np.zeros(15, np.int16),
+                        np.zeros((5, 4), np.int16), torch.zeros((5, 3), dtype=torch.int16), torch.zeros((3, 5), dtype=torch.int16).t()):
+                with pytest.raises(ValueError):
+                    call(bad, None)
+            for bad in (mrgb.astype(np.int8), mrgb.astype(np.uint32), np.zeros((5, 3), np.uint8), np.zeros(20, np.uint8), np.zeros((4, 4), np.uint8),
+                        torch.zeros((5, 4), dtype=torch.uint8), torch.zeros((4, 5), dtype=torch.uint8).t()):
+                with pytest.raises(ValueError):
+                    call(pos, bad)                                         # ... before anything is uploaded
+            for bad in (pos.tolist(), None, "pos"):
+                with pytest.raises(TypeError):
+                    call(bad, None)
+            with pytest.raises(TypeError):
+                call(pos, mrgb.tolist())
+            for bad in (0, 4, 8, 27, -6, 6.0, "6", None, True):
+                with pytest.raises(ValueError):
+                    call(pos, mrgb, connectivity=bad)
+            for bad in (0, 65, -1, 1.0, "1", None, True):
+                with pytest.raises(ValueError):
+                    call(pos, mrgb, steps=bad)
+        for bad in (-1, 4, 1.0, "0", None, True):
+            with pytest.raises(ValueError):
+                ctx.morph_voxels(pos, mrgb, bad)
+        for bad in (-1, 1.5, "3", True):
+            with pytest.raises(ValueError):
+                ctx.morph_voxels(pos, mrgb, H.MORPH_ERODE, cap=bad)
+    finally:
+        ctx._h = None                                                     # __del__ / close() have nothing to destroy
+
+
+# ---- the model -------------------------------------------------------------------------------------------------------------------
+def as_dict(pos, mrgb):
+    return {tuple(p): tuple(b) for p, b in zip(pos.tolist(), mrgb.tolist())}
+
+
+def cells_of(pos):
+    return {tuple(p) for p in np.asarray(pos).tolist()}
+
+
+def test_the_offset_table():
+    assert len(set(M.OFFSETS)) == 26 and (0, 0, 0) not in M.OFFSETS
+    assert [sum(1 for d in o if d) for o in M.OFFSETS] == [1] * 6 + [2] * 12 + [3] * 8
+    code = lambda o: 9 * (o[0] + 1) + 3 * (o[1] + 1) + (o[2] + 1)        # noqa: E731
+    for lo, hi in ((0, 6), (6, 18), (18, 26)):
+        assert [code(o) for o in M.OFFSETS[lo:hi]] == sorted(code(o) for o in M.OFFSETS[lo:hi])
+    assert M.OFFSETS[6] == (-1, -1, 0) and M.OFFSETS[17] == (1, 1, 0) and M.OFFSETS[18] == (-1, -1, -1) and M.OFFSETS[25] == (1, 1, 1)
+
+
+def dense(grid, colour, op, c, steps):
+    """The ops on a dense occupancy grid by shifted copies (numpy; the grid is padded so that nothing reaches its border): a
+    second, independent statement of rules 2 to 4."""
+    pad = steps + 1
+    occ = np.pad(grid, pad)
+    col = np.pad(colour, [(pad, pad)] * 3 + [(0, 0)])
+    start_occ, start_col = occ.copy(), col.copy()
+
+    def shifted(a, o):     # a'[x] = a[x + o]
+        return np.roll(a, (-o[0], -o[1], -o[2]), axis=(0, 1, 2))
+
+    for _ in range(steps):
+        if op in (M.DILATE, M.MARGIN):
+            new_col = col.copy()
+            grown = occ.copy()
+            for o in reversed(M.OFFSETS[:c]):                     # the least row is written last
+                src = shifted(occ, o) & ~occ
+                new_col[src] = shifted(col, o)[src]
+                grown |= src
+            occ, col = grown, new_col
+        else:
+            keep = occ.copy()
+            for o in M.OFFSETS[:c]:
+                keep &= shifted(occ, o)
+            occ = keep
+    if op == M.SURFACE:
+        occ, col = start_occ & ~occ, start_col
+    if op == M.MARGIN:
+        occ = occ & ~start_occ
+    at = np.argwhere(occ)
+    return {tuple((p - pad).tolist()): tuple(col[tuple(p)].tolist()) for p in at}
+
+
+@pytest.mark.parametrize("c", M.CONNECTIVITIES)
+def test_the_model_against_a_dense_grid(c):
+    rng = np.random.default_rng(40 + c)
+    for side, density in ((6, 0.5), (10, 0.2), (12, 0.85)):                  # 12 + 2 (3 + 1) = 20 cells a side at the most
+        grid = rng.random((side, side, side)) < density
+        colour = rng.integers(0, 128, (side, side, side, 4)).astype(np.uint8)
+        pos = np.argwhere(grid).astype(np.int16)
+        mrgb = colour[grid]
+        for op in M.OPS:
+            for steps in (1, 2, 3):
+                got = as_dict(*M.morph(pos, mrgb, op, c, steps))
+                assert got == dense(grid, colour, op, c, steps), (side, M.NAMES[op], c, steps)
+
+
+def test_counts_known_by_hand():
+    one, red = np.array([[3, -4, 5]], np.int16), np.array([[0x85, 200, 0, 0]], np.uint8)
+    count = lambda pos, op, c, steps=1: len(M.morph(pos, None, op, c, steps)[0])        # noqa: E731
+    assert [count(one, M.DILATE, c) for c in M.CONNECTIVITIES] == [7, 19, 27]
+    assert count(one, M.DILATE, 6, 2) == 25
+    assert [count(one, M.MARGIN, c) for c in M.CONNECTIVITIES] == [6, 18, 26]
+    assert [count(one, M.ERODE, c) for c in M.CONNECTIVITIES] == [0, 0, 0] and [count(one, M.SURFACE, c) for c in M.CONNECTIVITIES] == [1, 1, 1]
+    cube = M.cube16()[0]
+    assert len(cells_of(cube)) == 4096
+    assert [count(cube, M.DILATE, c) for c in M.CONNECTIVITIES] == [5632, 5824, 5832]
+    assert [count(cube, M.ERODE, c) for c in M.CONNECTIVITIES] == [2744] * 3 and [count(cube, M.SURFACE, c) for c in M.CONNECTIVITIES] == [1352] * 3
+    assert count(cube, M.ERODE, 6, 7) == 8 and count(cube, M.ERODE, 6, 8) == 0 and count(cube, M.ERODE, 26, 64) == 0
+    assert count(cube, M.SURFACE, 6, 8) == 4096
+    corner = np.array([[32767, 32767, 32767]], np.int16)
+    assert [count(corner, M.DILATE, c) for c in M.CONNECTIVITIES] == [4, 7, 8]
+    assert [count(corner, M.ERODE, c) for c in M.CONNECTIVITIES] == [0, 0, 0]
+    block = np.array([[x, y, z] for x in (32765, 32766, 32767) for y in (-1, 0, 1) for z in (-1, 0, 1)], np.int16)
+    assert M.morph(block, None, M.ERODE, 26)[0].tolist() == [[32766, 0, 0]]
+    assert count(block[block[:, 0] >= 32766], M.ERODE, 6) == 0                 # (32767, 0, 0) has no neighbour at + x: it goes
+    # a new cell between a red face neighbour and a blue edge neighbour
+    pair = np.array([[1, 0, 0], [-1, -1, 0]], np.int16)
+    bytes_ = np.array([[1, 255, 0, 0], [2, 0, 0, 255]], np.uint8)
+    for order in ([0, 1], [1, 0]):
+        assert as_dict(*M.morph(pair[order], bytes_[order], M.DILATE, 6))[(0, 0, 0)] == (1, 255, 0, 0)
+        for c in (18, 26):
+            assert as_dict(*M.morph(pair[order], bytes_[order], M.DILATE, c))[(0, 0, 0)] == (1, 255, 0, 0), c
+            assert as_dict(*M.morph(pair[order], bytes_[order], M.MARGIN, c))[(0, 0, 0)] == (1, 255, 0, 0), c
+    # ... and between two face neighbours the lower row wins: (-1, 0, 0) is row 0
+    both = np.array([[1, 0, 0], [-1, 0, 0]], np.int16)
+    assert as_dict(*M.morph(both, bytes_, M.DILATE, 6))[(0, 0, 0)] == (2, 0, 0, 255)
+    assert as_dict(*M.morph(one, red, M.DILATE, 6))[(4, -4, 5)] == (5, 200, 0, 0)
+
+
+@pytest.fixture(scope="module")
+def lists():
+    rng = np.random.default_rng(3)
+    pts = rng.integers(-4, 8, (1200, 3)).astype(np.int16)            # 1 200 random points of a cube of 12^3: duplicates are certain
+    return {"cube16": M.cube16(), "shell": T.shell(4), "random": (pts, rng.integers(0, 256, (1200, 4)).astype(np.uint8))}
+
+
+def test_the_identities(lists):
+    for name, (pos, mrgb) in lists.items():
+        s = T.source_of(pos, mrgb)
+        for c in M.CONNECTIVITIES:
+            for steps in ((1, 2) if c == 18 else (1,)):
+                surface, eroded, dilated, margin = (as_dict(*M.morph(pos, mrgb, op, c, steps)) for op in (M.SURFACE, M.ERODE, M.DILATE, M.MARGIN))
+                assert not surface.keys() & eroded.keys() and {**surface, **eroded} == s, (name, c, steps)       # SURFACE and ERODE partition S
+                assert not margin.keys() & s.keys() and {**margin, **s} == dilated, (name, c, steps)            # MARGIN and S partition DILATE
+                d_pos, d_mrgb = M.morph(pos, mrgb, M.DILATE, c, steps)
+                closed = as_dict(*M.morph(d_pos, d_mrgb, M.ERODE, c, steps))
+                assert all(closed.get(p) == b for p, b in s.items()), (name, c, steps)                           # ERODE(DILATE(S)) contains S
+        flipped = mrgb.copy()
+        flipped[:, 0] ^= 0x80                                              # bit 7 of the material byte never matters
+        for op in M.OPS:
+            assert all(np.array_equal(x, y) for x, y in zip(M.morph(pos, mrgb, op, 18, 2), M.morph(pos, flipped, op, 18, 2))), name
+            only, none = M.morph(pos, None, op, 18, 2)
+            assert none is None and np.array_equal(only, M.morph(pos, mrgb, op, 18, 2)[0])
+    assert len(T.source_of(*lists["random"])) < 1200                  # it has duplicates, and the last entry's bytes win
+
+
+def test_the_key_helpers_invert_each_other():
+    rng = np.random.default_rng(8)
+    for p in [(0, 0, 0), (-32768, 32767, -1), (32767, 32767, 32767)] + [tuple(int(v) for v in rng.integers(-32768, 32768, 3)) for _ in range(200)]:
+        assert M.key_cell(T.path_key(p)) == p
+    assert M.word_bytes(M.leaf_word((0x85, 1, 2, 3))) == (5, 1, 2, 3)
+
+
+# ---- the kernels' arithmetic as a host compiler reads it --------------------------------------------------------------------------
+# The program takes cases "op c steps m" + m lines "key word" and runs each as api_morph.hip and morph.hip do.  Per step the mask
+# kernel's walk: per block of kMorphSpan keys the tile copied into an array of exactly kMorphSpan entries (the sanitizer sees a
+# read past it), the whole list in an array of exactly its size, per thread and item and row the neighbour key, the tile's answer
+# where the tile decides and the whole array's where it does not (the two must agree wherever both can be asked); then ERODE's
+# compaction, or DILATE's offers, their sort, the first of each cell (which must be the cell's first_source by a gather of its own)
+# and the merge; then the difference of SURFACE and MARGIN.  It starts by printing the table and the opposite rows.
+DRIVER = r"""
+#include <algorithm>
+#include <cstdio>
+#include <iterator>
+#include <utility>
+#include <vector>
+#include "morph_rule.h"
+using namespace vxrt;
+typedef std::vector<std::pair<uint64_t, uint32_t>> Set;
+
+static int masks_of(const Set& s, uint32_t c, std::vector<uint32_t>* masks) {
+    const uint32_t m = uint32_t(s.size()), steps = list_steps(m);
+    std::vector<uint64_t> keys(m ? m : 2);          // an empty list's allocation is readable at [0]
+    for (uint32_t i = 0; i < m; i++) keys[i] = s[i].first;
+    masks->assign(m, 0u);
+    for (uint32_t base = 0; base < m; base += kMorphSpan) {
+        const uint32_t count = m - base > kMorphSpan ? kMorphSpan : m - base;
+        std::vector<uint64_t> tile(kMorphSpan);
+        for (uint32_t e = 0; e < kMorphSpan; e++) {
+            const uint64_t k = keys[morph_safe_index(base + e, m)];
+            tile[e] = e < count ? k : kMorphNoKey;
+        }
+        const uint64_t first = tile[0], last = tile[count - 1u];
+        for (uint32_t t = 0; t < kMorphThreads; t++) {
+            for (uint32_t k = 0; k < kMorphItems; k++) {
+                const uint32_t e = k * kMorphThreads + t;
+                const uint64_t key = keys[morph_safe_index(base + e, m)];
+                uint32_t mask = 0;
+                for (uint32_t r = 0; r < c; r++) {
+                    bool ok;
+                    const uint64_t q = neighbour_key(key, r, &ok);
+                    const bool inside = tile_decides(q, first, last);
+                    const bool in_tile = tile_has(tile.data(), q);
+                    const bool in_list = list_has(keys.data(), m, steps, q, true);
+                    if (list_has(keys.data(), m, steps, q, false)) return 10;
+                    if (inside && in_tile != in_list) return 11;
+                    if (in_tile && !in_list) return 12;
+                    const bool found = inside ? in_tile : list_has(keys.data(), m, steps, q, ok && !inside);
+                    mask |= (found && ok ? 1u : 0u) << r;
+                }
+                if (e < count) (*masks)[base + e] = mask;
+            }
+        }
+    }
+    return 0;
+}
+
+static int erode(const Set& s, uint32_t c, Set* out) {
+    std::vector<uint32_t> masks;
+    if (int rc = masks_of(s, c, &masks)) return rc;
+    out->clear();
+    for (size_t i = 0; i < s.size(); i++)
+        if (keep_eroded(masks[i], c)) out->push_back(s[i]);
+    return 0;
+}
+
+static int dilate(const Set& s, uint32_t c, Set* out) {
+    std::vector<uint32_t> masks;
+    if (int rc = masks_of(s, c, &masks)) return rc;
+    Set offers;
+    for (size_t i = 0; i < s.size(); i++) {
+        const uint32_t rows = offer_rows(s[i].first, masks[i], c);
+        for (uint32_t r = 0; r < c; r++) {
+            if (rows >> r & 1u) {
+                bool ok;
+                const uint64_t q = neighbour_key(s[i].first, r, &ok);
+                if (!ok) return 20;
+                offers.push_back({offer_key(q, r), s[i].second});
+            }
+        }
+    }
+    std::sort(offers.begin(), offers.end());
+    std::vector<uint64_t> keys(s.size() ? s.size() : 2);
+    for (size_t i = 0; i < s.size(); i++) keys[i] = s[i].first;
+    const uint32_t m = uint32_t(s.size()), steps = list_steps(m);
+    Set cells;
+    for (size_t i = 0; i < offers.size(); i++) {
+        if (i != 0 && offers[i].first == offers[i - 1].first) return 21;          // a cell has one source per row
+        if (i != 0 && offer_cell(offers[i].first) == offer_cell(offers[i - 1].first)) continue;
+        const uint64_t cell = offer_cell(offers[i].first);
+        uint32_t mask = 0;                                                        // the gather: the new cell's own neighbours
+        for (uint32_t r = 0; r < c; r++) {
+            bool ok;
+            const uint64_t q = neighbour_key(cell, r, &ok);
+            mask |= (ok && list_has(keys.data(), m, steps, q, true) ? 1u : 0u) << r;
+        }
+        if (first_source(mask, c) != uint32_t(offers[i].first & 31u)) return 22;
+        if (list_has(keys.data(), m, steps, cell, true)) return 23;               // a new cell is not in the set
+        cells.push_back({cell, offers[i].second});
+    }
+    out->resize(s.size() + cells.size());
+    std::merge(s.begin(), s.end(), cells.begin(), cells.end(), out->begin());
+    return 0;
+}
+
+int main() {
+    for (uint32_t r = 0; r < kMorphRows; r++)
+        std::printf("row %u %d %d %d %u\n", r, kMorphOffsets[r].d[0], kMorphOffsets[r].d[1], kMorphOffsets[r].d[2], opposite_row(r));
+    unsigned op, c, steps, m;
+    while (std::scanf("%u %u %u %u", &op, &c, &steps, &m) == 4) {
+        Set s(m);
+        for (unsigned i = 0; i < m; i++) {
+            unsigned long long k;
+            unsigned w;
+            if (std::scanf("%llu %u", &k, &w) != 2) return 2;
+            s[i] = {k, w};
+        }
+        Set cur = s, next;
+        for (unsigned step = 0; step < steps && !cur.empty(); step++) {
+            if (int rc = (op == kMorphDilate || op == kMorphMargin) ? dilate(cur, c, &next) : erode(cur, c, &next)) return rc;
+            cur.swap(next);
+        }
+        Set out;
+        auto by_key = [](const std::pair<uint64_t, uint32_t>& x, const std::pair<uint64_t, uint32_t>& y) { return x.first < y.first; };
+        if (op == kMorphSurface) std::set_difference(s.begin(), s.end(), cur.begin(), cur.end(), std::back_inserter(out), by_key);
+        else if (op == kMorphMargin) std::set_difference(cur.begin(), cur.end(), s.begin(), s.end(), std::back_inserter(out), by_key);
+        else out = cur;
+        for (const auto& e : out) std::printf("%llu %u\n", (unsigned long long)e.first, e.second);
+        std::printf("end %zu\n", out.size());
+    }
+    return 0;
+}
+"""
+
+
+def key_cases():
+    """[(pos, mrgb, [(op, c, steps)])]"""
+    rng = np.random.default_rng(29)
+    colours = lambda n: rng.integers(0, 256, (n, 4)).astype(np.uint8)       # noqa: E731
+    every = [(op, c, 1) for op in M.OPS for c in M.CONNECTIVITIES]
+    cases = [(np.zeros((0, 3), np.int16), colours(0), every), (np.array([[3, -4, 5]], np.int16), colours(1), every + [(M.DILATE, 6, 2), (M.MARGIN, 26, 3)])]
+    corners = np.array([[x, y, z] for x in (-32768, 32767) for y in (-32768, 32767) for z in (-32768, 32767)], np.int16)
+    cases.append((corners, colours(8), every + [(M.DILATE, 26, 2), (M.MARGIN, 18, 2)]))
+    box = np.stack(np.meshgrid(np.arange(-8, 9), np.arange(-8, 9), np.arange(-8, 9), indexing="ij"), -1).reshape(-1, 3)      # 17^3 = 4 913 cells
+    for n in (2047, 2048, 2049, 4097):
+        cells = box[rng.choice(len(box), n, replace=False)].astype(np.int16)
+        some = every if n == 4097 else [(op, 26, 1) for op in M.OPS] + [(M.ERODE, 6, 1), (M.DILATE, 18, 1)]
+        cases.append((cells, colours(n), some + [(M.ERODE, 6, 2), (M.DILATE, 18, 2)]))
+    g = np.arange(-32, 32)
+    plate = np.stack(np.meshgrid(g, g, [0], indexing="ij"), -1).reshape(-1, 3).astype(np.int16)                                  # 64 x 64 x 1: two tiles
+    cases.append((plate, colours(len(plate)), every + [(M.SURFACE, 18, 2)]))
+    for _ in range(100):
+        side = int(rng.choice([3, 5, 9]))
+        origin = np.array([int(rng.choice([-32768, -side // 2, 32768 - side])) for _ in range(3)])
+        n = int(rng.integers(1, 300))
+        cells = (rng.integers(0, side, (n, 3)) + origin).astype(np.int16)
+        cases.append((cells, colours(n), [(int(rng.choice(M.OPS)), int(rng.choice(M.CONNECTIVITIES)), int(rng.integers(1, 4)))]))
+    return cases
+
+
+def test_the_kernels_arithmetic_under_the_sanitizers(tmp_path):
+    src = tmp_path / "rule.cpp"
+    src.write_text(DRIVER)
+    exe = tmp_path / "rule"
+    build = subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=undefined,address", "-fno-sanitize-recover=all", "-static-libasan",
+                            "-I", CSRC, str(src), "-o", str(exe)], capture_output=True, text=True)
+    assert build.returncode == 0, build.stderr
+    runs = []
+    for pos, mrgb, params in key_cases():
+        keys, words = M.sorted_keys_words(pos, mrgb)
+        for op, c, steps in params:
+            runs.append((keys, words, op, c, steps))
+    text = "".join(f"{op} {c} {steps} {len(keys)}\n" + "".join(f"{k} {w}\n" for k, w in zip(keys, words)) for keys, words, op, c, steps in runs)
+    run = subprocess.run([str(exe)], input=text, capture_output=True, text=True)
+    assert run.returncode == 0 and not run.stderr.strip(), (run.returncode, run.stderr[-2000:])
+    lines = iter(run.stdout.split("\n"))
+    for r, o in enumerate(M.OFFSETS):
+        assert next(lines) == f"row {r} {o[0]} {o[1]} {o[2]} {M.OFFSETS.index((-o[0], -o[1], -o[2]))}"
+    kept_any = {op: 0 for op in M.OPS}
+    for n, (keys, words, op, c, steps) in enumerate(runs):
+        want = M.morph_keys(keys, words, op, c, steps)
+        got = []
+        for line in lines:
+            if line.startswith("end"):
+                assert line == f"end {len(want)}", (n, M.NAMES[op], c, steps, line, len(want))
+                break
+            got.append(tuple(int(v) for v in line.split()))
+        assert got == want, (n, M.NAMES[op], c, steps, len(keys))
+        kept_any[op] += len(want)
+    assert all(kept_any.values()) and next(lines) == ""
