@@ -7,6 +7,7 @@
 #include "compact.h"
 #include "ctx.h"
 #include "device_build.h"
+#include "list_ops.h"
 #include "scene_args.h"
 
 namespace vxrt {
@@ -55,10 +56,8 @@ int relayout(vxrt_ctx* c, ScratchBuffer* svo, ScratchBuffer* leaves, size_t* lea
         a.leaf = l == L ? 1u : 0u;
         const uint32_t blocks = compact_blocks(a.start, a.n);
         HIP_TRY(launch_compact_count(a, c->stream));
-        HIP_TRY(launch_exclusive_scan(a.part, blocks, c->stream));
         uint64_t total = 0;
-        HIP_TRY(hipMemcpyAsync(&total, a.part + blocks, sizeof total, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
+        if (int rc = scan_total(a.part, blocks, c->stream, &total)) return rc;
         if (a.leaf) {
             if (start + n != live) return miscounted(start + n, live);
             if (total == 0 || total > c->leaf_count) { set_error(std::string(kWho) + ": the leaf parents hold " + std::to_string(total) + " leaf words"); return VXRT_E_SCENE; }

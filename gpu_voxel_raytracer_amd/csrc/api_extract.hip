@@ -8,6 +8,7 @@
 #include "ctx.h"
 #include "device_build.h"
 #include "extract.h"
+#include "list_ops.h"
 #include "scene_args.h"
 #include "../../include/vxrt_device_edit.h"
 #include "../../include/vxrt_extract.h"
@@ -95,10 +96,8 @@ static int get_voxels(vxrt_ctx* c, const int32_t box_min[3], const int32_t box_m
             return alloc_failed(e, who, "the scan partials");
         a.part = static_cast<uint64_t*>(x.part);
         HIP_TRY(launch_extract_count(a, c->stream));
-        HIP_TRY(launch_exclusive_scan(a.part, blocks, c->stream));
         uint64_t total = 0;
-        HIP_TRY(hipMemcpyAsync(&total, a.part + blocks, sizeof total, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
+        if (int rc = scan_total(a.part, blocks, c->stream, &total)) return rc;
         if (total == 0) break;
         if (a.leaf) { count = total; break; }
         if (total >= (uint64_t(1) << 32)) { set_error(std::string(who) + ": a tree level of 2^32 nodes or more"); return VXRT_E_INVALID; }

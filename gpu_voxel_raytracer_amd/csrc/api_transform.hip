@@ -1,13 +1,11 @@
 // api_transform.hip — host side of vxrt_transform.h: a voxel list in device memory resampled under a fixed-point affine map, by
-// pulling every cell of a destination box through the map into the list.  The source is keyed at depth 15 by the device editor's
-// pass (device_edit.hip) and sorted and deduplicated by the list builder's front (device_build.h: sort_unique_list); the pull and
-// the decode are transform.hip's; the blocks' counts are summed by the list builder's scan and the result is sorted by its radix
-// sort.  Nothing but two counts and the source's bounds crosses to the host.  DESIGN.md §23.
+// pulling every cell of a destination box through the map into the list.  The source is keyed, sorted and deduplicated by
+// list_ops.h's key_list, which also gives its bounds; the pull is transform.hip's; the blocks' counts are summed by scan_total and
+// the result is sorted by the list builder's radix sort (device_build.h); the output checks and the decode are list_ops.h's.
+// Nothing but two counts and the source's bounds crosses to the host.  DESIGN.md §23.
 #include <string>
 
-#include "ctx.h"
-#include "device_build.h"
-#include "edit.h"
+#include "list_ops.h"
 #include "scene_args.h"
 #include "transform.h"
 #include "../../include/vxrt_transform.h"
@@ -47,36 +45,23 @@ int vxrt_transform_voxels_device(vxrt_ctx* c, const int16_t (*pos)[3], const uin
     }
     if (!empty_box && cells >= (uint64_t(1) << 32)) { set_error(w + ": a box of 2^32 cells or more"); return VXRT_E_INVALID; }
     if (n != 0 && !pos) { set_error(w + ": null voxel positions"); return VXRT_E_INVALID; }
-    if (mrgb ? (out_pos != nullptr) != (out_mrgb != nullptr) : out_mrgb != nullptr) {
-        set_error(w + (mrgb ? ": out_pos and out_mrgb come both or neither" : ": out_mrgb without mrgb"));
-        return VXRT_E_INVALID;
-    }
+    if (int rc = check_output_pair(mrgb != nullptr, out_pos, out_mrgb, who, "mrgb")) return rc;
     if (empty_box || n == 0) { *n_out = 0; return VXRT_OK; }
 
     HIP_TRY(hipSetDevice(c->cfg.device));
-    if (int rc = check_device_array(c, pos, n * 3 * sizeof(int16_t), who, "pos")) return rc;
-    if (mrgb)
-        if (int rc = check_device_array(c, mrgb, n * 4, who, "mrgb")) return rc;
-    if (out_pos)
-        if (int rc = check_device_array(c, out_pos, cap * 3 * sizeof(int16_t), who, "out_pos")) return rc;
-    if (out_mrgb)
-        if (int rc = check_device_array(c, out_mrgb, cap * 4, who, "out_mrgb")) return rc;
+    if (int rc = check_input_list(c, pos, mrgb, n, who, "pos", "mrgb")) return rc;
+    if (int rc = check_output_arrays(c, out_pos, out_mrgb, cap, who)) return rc;
 
-    // the source: keys at depth 15 (every int16 position is inside that cube), sorted, one per position, the last entry's bytes
+    // the source: sorted, one key per position, the last entry's bytes (carried on a counting call too)
     hipStream_t s = c->stream;     // behind everything enqueued there, vxrt_context_wait_stream's events included
     const bool with_vals = mrgb != nullptr;
     const uint32_t blocks = pull_blocks(cells);
-    ListScratch ls;
-    ScratchBuffer words, part;
-    if (int rc = alloc_list_scratch(n, with_vals, who, &ls)) return rc;
-    if (int rc = alloc_scratch(&part, (size_t(blocks) + 1) * sizeof(uint64_t), who, "the block counts")) return rc;
+    KeyedList src;
+    ScratchBuffer part;
     ListBounds lb;
-    if (int rc = edit_keys_device(reinterpret_cast<const int16_t*>(pos), reinterpret_cast<const uint8_t*>(mrgb), n, 15u,
-                                  ls.keys[0].as<uint64_t>(), ls.vals[0].as<uint32_t>(), s, who, &lb))
-        return rc;
-    size_t m = 0;
-    int cur = 0;
-    if (int rc = sort_unique_list(&ls, uint32_t(n), 15u, &words, s, who, &m, &cur)) return rc;
+    // allocated ahead of the front, whose last kernel is still running when it returns: the pull is enqueued right behind it
+    if (int rc = alloc_scratch(&part, (size_t(blocks) + 1) * sizeof(uint64_t), who, "the block counts")) return rc;
+    if (int rc = key_list(pos, mrgb, n, with_vals, s, who, &src, &lb)) return rc;
 
     PullArgs a{};
     for (int i = 0; i < 3; i++) {
@@ -88,21 +73,15 @@ int vxrt_transform_voxels_device(vxrt_ctx* c, const int16_t (*pos)[3], const uin
         a.src_hi[i] = lb.hi[i];
     }
     a.cells = uint32_t(cells);
-    a.keys = ls.keys[cur].as<uint64_t>();
-    a.words = with_vals ? words.as<int32_t>() : nullptr;
-    a.count = uint32_t(m);      // 0 < m <= n
+    a.keys = src.view.keys;
+    a.words = reinterpret_cast<const int32_t*>(src.view.words);
+    a.count = src.view.m;      // 0 < m <= n
     a.part = part.as<uint64_t>();
     HIP_TRY(launch_transform_pull(a, s));
-    HIP_TRY(launch_exclusive_scan(a.part, blocks, s));
     uint64_t count = 0;
-    HIP_TRY(hipMemcpyAsync(&count, a.part + blocks, sizeof count, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    *n_out = size_t(count);
+    if (int rc = scan_total(a.part, blocks, s, &count)) return rc;
+    if (int rc = list_room(count, out_pos, cap, who, n_out)) return rc;
     if (!out_pos || count == 0) return VXRT_OK;
-    if (count > cap) {
-        set_error(w + ": " + std::to_string(count) + " voxels, room for " + std::to_string(cap));
-        return VXRT_E_INVALID;
-    }
 
     // the result: (key of d, leaf word of s) per voxel at the scanned offsets, sorted by key (unique by construction), decoded
     ListScratch out;
@@ -114,9 +93,7 @@ int vxrt_transform_voxels_device(vxrt_ctx* c, const int16_t (*pos)[3], const uin
     HIP_TRY(launch_transform_pull(a, s));
     int at = 0;
     HIP_TRY(radix_sort_pairs(kp, vp, uint32_t(count), 48u, out.hist.as<uint32_t>(), out.totals.as<uint32_t>(), s, &at));
-    HIP_TRY(launch_transform_decode(kp[at], vp[at], uint32_t(count), reinterpret_cast<uint8_t*>(out_pos), reinterpret_cast<uint8_t*>(out_mrgb), s));
-    HIP_TRY(hipStreamSynchronize(s));
-    return VXRT_OK;
+    return decode_list(kp[at], vp[at], count, out_pos, out_mrgb, s);
 } VXRT_CATCH
 
 }  // extern "C"

@@ -16,6 +16,7 @@
 //   api_transform.hip  a device voxel list resampled under a fixed-point affine map (vxrt_transform.h)
 //   api_setops.hip   two device voxel lists combined: union, intersection, difference, delta (vxrt_setops.h)
 //   api_morph.hip    a device voxel list dilated, eroded, or cut to its surface layer or margin ring (vxrt_morph.h)
+//   list_ops.hip     no entry point: the host pipeline those three share (list_ops.h)
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -1,7 +1,9 @@
 // device_build.h — what api_device_scene.hip (host side of vxrt_device_scene.h), device_build.hip (the list builder), grid_build.hip
 // (the dense-grid builder), grid_edit.hip (the grid editor), api_grid.hip (host side of vxrt_grid.h) and api_device_edit.hip /
 // device_edit.hip (vxrt_device_edit.h) share, and the device primitives they and api_extract.hip use: the path key and leaf word,
-// lanes_below, the exclusive scan, the radix sort and the sort-and-dedupe front of a list (device_build.hip).
+// lanes_below, the exclusive scan, the radix sort and the sort-and-dedupe front of a list (device_build.hip).  The front at depth
+// 15 behind vxrt_transform.h, vxrt_setops.h and vxrt_morph.h, and the scan with its total read back, are list_ops.h's key_list and
+// scan_total over these; api_device_edit.hip, api_voxelize.hip and api_solid.hip run the front at a depth of their own.
 #pragma once
 #include <hip/hip_runtime.h>
 

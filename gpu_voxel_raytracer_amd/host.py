@@ -321,6 +321,11 @@ def _p(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None else None
 
 
+def _dptr(t):
+    """A device tensor's address for ctypes; None, and an empty tensor (which has no address), are a null pointer."""
+    return None if t is None or t.numel() == 0 else C.c_void_p(t.data_ptr())
+
+
 def _check(status, where):
     if status != 0:
         raise VxrtError(status, where, (lib().vxrt_last_error() or b"").decode(errors="replace"))
@@ -614,6 +619,26 @@ class Context:
                 run(cap, info_cap, pos, mrgb, piece, raw)
         n = int(got.value)
         return (pos[:n], mrgb[:n], piece[:n], self._piece_table(raw, int(k.value))) if pieces else (pos[:n], mrgb[:n])
+
+    def _list_result(self, run, with_vals, empty, cap):
+        """_voxel_list's cap rule for the operators on lists, whose mrgb is optional and whose counting call reads device lists, so
+        that both calls are ordered against torch's current stream -> (pos int16 [k,3], mrgb uint8 [k,4] or None).  run(out_pos,
+        out_mrgb, room) is the call with its inputs bound -> the count it gave.  empty: no input has an entry, and nothing is called."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        if empty:
+            cap = 0
+        if cap is None:
+            with self._ordered():
+                cap = run(None, None, 0)
+        cap = int(cap)
+        out_pos = torch.empty((cap, 3), dtype=torch.int16, device=dev)
+        out_mrgb = torch.empty((cap, 4), dtype=torch.uint8, device=dev) if with_vals else None
+        k = 0
+        if cap:
+            with self._ordered():
+                k = run(out_pos, out_mrgb, cap)
+        return out_pos[:k], (None if out_mrgb is None else out_mrgb[:k])
 
     # -- lifetime ------------------------------------------------------------------------------------
     def close(self):
@@ -966,9 +991,14 @@ class Context:
         self.clear_voxels_device(pos)
 
     @staticmethod
+    def _int_of(v, allowed, message):
+        """v is an integer (no bool) of `allowed`, or ValueError(message)."""
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or int(v) not in allowed:
+            raise ValueError(message)
+
+    @staticmethod
     def _connectivity(connectivity):
-        if isinstance(connectivity, bool) or not isinstance(connectivity, (int, np.integer)) or int(connectivity) not in (6, 18, 26):
-            raise ValueError("connectivity must be 6, 18 or 26")
+        Context._int_of(connectivity, (6, 18, 26), "connectivity must be 6, 18 or 26")
         return C.c_uint32(int(connectivity))
 
     def label_components(self, pos, connectivity=6):
@@ -1146,6 +1176,15 @@ class Context:
             if a.device != dev:
                 raise ValueError(f"{name} must be on {dev}")
 
+    def _list_check(self, pos, mrgb, names=("pos", "mrgb"), mismatch="one mrgb per position"):
+        """_query_check of a list's positions and, where given, its bytes, one per position."""
+        import torch
+        self._query_check(pos, names[0], torch.int16, 3)
+        if mrgb is not None:
+            self._query_check(mrgb, names[1], torch.uint8, 4)
+            if len(mrgb) != len(pos):
+                raise ValueError(mismatch)
+
     def _query_tensor(self, a):
         """A checked argument on the context's device: a numpy array goes there with torch."""
         import torch
@@ -1242,51 +1281,27 @@ class Context:
         numpy arrays, which are uploaded with torch once every check has passed.  cap=None: two calls, one to count and one into
         tensors of exactly that size; cap=k: one call into tensors with room for k voxels, cut to the count; more than k voxels is an
         error (VXRT_E_INVALID).  Ordered on both sides against torch's current stream.  No scene is needed or touched."""
-        import torch
-        dev = torch.device("cuda", self.device)
-        self._query_check(pos, "pos", torch.int16, 3)
-        if mrgb is not None:
-            self._query_check(mrgb, "mrgb", torch.uint8, 4)
-            if len(mrgb) != len(pos):
-                raise ValueError("one mrgb per position")
+        self._list_check(pos, mrgb)
         if not isinstance(pull, Affine):
             raise TypeError("pull must be an Affine (rigid_pull makes one)")
         lo, hi = self._cell3(box_min, "box_min", -32768, 32768), self._cell3(box_max, "box_max", -32768, 32768)
         self._cap(cap)
         pos = self._query_tensor(pos)
         mrgb = None if mrgb is None else self._query_tensor(mrgb)
-        n = len(pos)
         got = C.c_size_t(0)
 
         def run(out_pos, out_mrgb, room):
             self._chk(self._L.vxrt_transform_voxels_device(
-                self._h, C.c_void_p(pos.data_ptr()), None if mrgb is None else C.c_void_p(mrgb.data_ptr()),
-                C.c_size_t(n), C.byref(pull), lo, hi, None if out_pos is None else C.c_void_p(out_pos.data_ptr()),
-                None if out_mrgb is None else C.c_void_p(out_mrgb.data_ptr()), C.c_size_t(room), C.byref(got)), "vxrt_transform_voxels_device")
-        if n == 0:          # an empty tensor has no address to tell "no mrgb" from "no entries" by: the result is empty either way
-            cap = 0
-        if cap is None:
-            with self._ordered():
-                run(None, None, 0)
-            cap = int(got.value)
-        cap = int(cap)
-        out_pos = torch.empty((cap, 3), dtype=torch.int16, device=dev)
-        out_mrgb = None if mrgb is None else torch.empty((cap, 4), dtype=torch.uint8, device=dev)
-        if cap:
-            with self._ordered():
-                run(out_pos, out_mrgb, cap)
-        k = int(got.value) if cap else 0
-        return out_pos[:k], (None if out_mrgb is None else out_mrgb[:k])
+                self._h, _dptr(pos), _dptr(mrgb), C.c_size_t(len(pos)), C.byref(pull), lo, hi, _dptr(out_pos), _dptr(out_mrgb),
+                C.c_size_t(room), C.byref(got)), "vxrt_transform_voxels_device")
+            return int(got.value)
+        # an empty tensor has no address to tell "no mrgb" from "no entries" by: the result is empty either way
+        return self._list_result(run, mrgb is not None, len(pos) == 0, cap)
 
     def rotate_voxels(self, pos, mrgb, rotation, pivot=(0, 0, 0), translation=(0, 0, 0)):
         """transform_voxels under rigid_pull(rotation, pivot, translation) into rigid_box of the list's bounds, which are taken with
         torch on the device: the list moved by x -> R (x - pivot) + pivot + translation, resampled."""
-        import torch
-        self._query_check(pos, "pos", torch.int16, 3)
-        if mrgb is not None:
-            self._query_check(mrgb, "mrgb", torch.uint8, 4)
-            if len(mrgb) != len(pos):
-                raise ValueError("one mrgb per position")
+        self._list_check(pos, mrgb)
         pull = rigid_pull(rotation, pivot, translation)
         pos = self._query_tensor(pos)          # every check has passed: rigid_pull was the last that can refuse
         if len(pos) == 0:
@@ -1306,13 +1321,8 @@ class Context:
         import torch
         dev = torch.device("cuda", self.device)
         for pos, mrgb, which in ((a_pos, a_mrgb, "a"), (b_pos, b_mrgb, "b")):
-            self._query_check(pos, which + "_pos", torch.int16, 3)
-            if mrgb is not None:
-                self._query_check(mrgb, which + "_mrgb", torch.uint8, 4)
-                if len(mrgb) != len(pos):
-                    raise ValueError(f"one {which}_mrgb per position of {which}_pos")
-        if isinstance(op, bool) or not isinstance(op, (int, np.integer)) or not LIST_UNION <= op <= LIST_CHANGED:
-            raise ValueError("op must be one of LIST_UNION .. LIST_CHANGED")
+            self._list_check(pos, mrgb, (which + "_pos", which + "_mrgb"), f"one {which}_mrgb per position of {which}_pos")
+        self._int_of(op, range(LIST_UNION, LIST_CHANGED + 1), "op must be one of LIST_UNION .. LIST_CHANGED")
         if a_mrgb is None:
             if b_mrgb is not None:
                 raise ValueError("b_mrgb without a_mrgb")
@@ -1328,39 +1338,25 @@ class Context:
         na, nb = len(a_pos), len(b_pos)
         # an empty tensor has no address: "bytes, and no entries" is said with an address that is never read
         spare = torch.empty((1, 4), dtype=torch.uint8, device=dev) if with_vals and na == 0 else None
-        ptr = lambda t: None if t is None or t.numel() == 0 else C.c_void_p(t.data_ptr())   # noqa: E731
         got = C.c_size_t(0)
 
         def run(out_pos, out_mrgb, room):
             self._chk(self._L.vxrt_combine_voxels_device(
-                self._h, ptr(a_pos), ptr(spare) if spare is not None else ptr(a_mrgb), C.c_size_t(na), ptr(b_pos), ptr(b_mrgb), C.c_size_t(nb),
-                C.c_uint32(int(op)), ptr(out_pos), ptr(out_mrgb), C.c_size_t(room), C.byref(got)), "vxrt_combine_voxels_device")
-        if na == 0 and nb == 0:
-            cap = 0
-        if cap is None:
-            with self._ordered():
-                run(None, None, 0)
-            cap = int(got.value)
-        cap = int(cap)
-        out_pos = torch.empty((cap, 3), dtype=torch.int16, device=dev)
-        out_mrgb = torch.empty((cap, 4), dtype=torch.uint8, device=dev) if with_vals else None
-        if cap:
-            with self._ordered():
-                run(out_pos, out_mrgb, cap)
-        k = int(got.value) if cap else 0
-        return out_pos[:k], (None if out_mrgb is None else out_mrgb[:k])
+                self._h, _dptr(a_pos), _dptr(spare) if spare is not None else _dptr(a_mrgb), C.c_size_t(na), _dptr(b_pos), _dptr(b_mrgb),
+                C.c_size_t(nb), C.c_uint32(int(op)), _dptr(out_pos), _dptr(out_mrgb), C.c_size_t(room), C.byref(got)), "vxrt_combine_voxels_device")
+            return int(got.value)
+        return self._list_result(run, with_vals, na == 0 and nb == 0, cap)
 
     def count_common(self, a_pos, b_pos):
         """combine_voxels, counting LIST_INTERSECT only (the collision test of two lists): how many distinct positions both hold."""
-        import torch
-        self._query_check(a_pos, "a_pos", torch.int16, 3)
-        self._query_check(b_pos, "b_pos", torch.int16, 3)
+        self._list_check(a_pos, None, ("a_pos", None))
+        self._list_check(b_pos, None, ("b_pos", None))
         a_pos, b_pos = self._query_tensor(a_pos), self._query_tensor(b_pos)
         got = C.c_size_t(0)
         if len(a_pos) and len(b_pos):
             with self._ordered():
                 self._chk(self._L.vxrt_combine_voxels_device(
-                    self._h, C.c_void_p(a_pos.data_ptr()), None, C.c_size_t(len(a_pos)), C.c_void_p(b_pos.data_ptr()), None, C.c_size_t(len(b_pos)),
+                    self._h, _dptr(a_pos), None, C.c_size_t(len(a_pos)), _dptr(b_pos), None, C.c_size_t(len(b_pos)),
                     C.c_uint32(LIST_INTERSECT), None, None, C.c_size_t(0), C.byref(got)), "vxrt_combine_voxels_device")
         return int(got.value)
 
@@ -1375,16 +1371,9 @@ class Context:
         return set_pos, set_mrgb, clear_pos
 
     def _morph_check(self, pos, mrgb, connectivity, steps):
-        import torch
-        self._query_check(pos, "pos", torch.int16, 3)
-        if mrgb is not None:
-            self._query_check(mrgb, "mrgb", torch.uint8, 4)
-            if len(mrgb) != len(pos):
-                raise ValueError("one mrgb per position")
-        if isinstance(connectivity, bool) or not isinstance(connectivity, (int, np.integer)) or connectivity not in (6, 18, 26):
-            raise ValueError("connectivity must be 6, 18 or 26")
-        if isinstance(steps, bool) or not isinstance(steps, (int, np.integer)) or not 1 <= steps <= 64:
-            raise ValueError("steps must be an integer of 1 .. 64")
+        self._list_check(pos, mrgb)
+        self._connectivity(connectivity)
+        self._int_of(steps, range(1, 65), "steps must be an integer of 1 .. 64")
 
     def morph_voxels(self, pos, mrgb, op, connectivity=6, steps=1, cap=None):
         """vxrt_morph_voxels_device (include/vxrt_morph.h): the list pos / mrgb under op (MORPH_DILATE: the set and every cell with a
@@ -1394,37 +1383,20 @@ class Context:
         each position once.  mrgb=None: positions only, and the second value is None.  pos (int16 [n,3]) and mrgb (uint8 [n,4]) are
         contiguous torch tensors on the context's device, or numpy arrays, which are uploaded with torch once every check has
         passed.  cap as transform_voxels'.  Ordered on both sides against torch's current stream.  No scene is needed or touched."""
-        import torch
-        dev = torch.device("cuda", self.device)
         self._morph_check(pos, mrgb, connectivity, steps)
-        if isinstance(op, bool) or not isinstance(op, (int, np.integer)) or not MORPH_DILATE <= op <= MORPH_MARGIN:
-            raise ValueError("op must be one of MORPH_DILATE .. MORPH_MARGIN")
+        self._int_of(op, range(MORPH_DILATE, MORPH_MARGIN + 1), "op must be one of MORPH_DILATE .. MORPH_MARGIN")
         self._cap(cap)
         pos = self._query_tensor(pos)
         mrgb = None if mrgb is None else self._query_tensor(mrgb)
-        n = len(pos)
         got = C.c_size_t(0)
 
         def run(out_pos, out_mrgb, room):
             self._chk(self._L.vxrt_morph_voxels_device(
-                self._h, C.c_void_p(pos.data_ptr()), None if mrgb is None else C.c_void_p(mrgb.data_ptr()), C.c_size_t(n),
-                C.c_uint32(int(op)), C.c_uint32(int(connectivity)), C.c_uint32(int(steps)),
-                None if out_pos is None else C.c_void_p(out_pos.data_ptr()), None if out_mrgb is None else C.c_void_p(out_mrgb.data_ptr()),
-                C.c_size_t(room), C.byref(got)), "vxrt_morph_voxels_device")
-        if n == 0:          # an empty tensor has no address to tell "no mrgb" from "no entries" by: the result is empty either way
-            cap = 0
-        if cap is None:
-            with self._ordered():
-                run(None, None, 0)
-            cap = int(got.value)
-        cap = int(cap)
-        out_pos = torch.empty((cap, 3), dtype=torch.int16, device=dev)
-        out_mrgb = None if mrgb is None else torch.empty((cap, 4), dtype=torch.uint8, device=dev)
-        if cap:
-            with self._ordered():
-                run(out_pos, out_mrgb, cap)
-        k = int(got.value) if cap else 0
-        return out_pos[:k], (None if out_mrgb is None else out_mrgb[:k])
+                self._h, _dptr(pos), _dptr(mrgb), C.c_size_t(len(pos)), C.c_uint32(int(op)), C.c_uint32(int(connectivity)),
+                C.c_uint32(int(steps)), _dptr(out_pos), _dptr(out_mrgb), C.c_size_t(room), C.byref(got)), "vxrt_morph_voxels_device")
+            return int(got.value)
+        # an empty tensor has no address to tell "no mrgb" from "no entries" by: the result is empty either way
+        return self._list_result(run, mrgb is not None, len(pos) == 0, cap)
 
     def close_voxels(self, pos, mrgb, connectivity=6, steps=1):
         """morph_voxels MORPH_DILATE, then MORPH_ERODE of the result: pinholes and gaps up to 2 * steps cells wide are filled, with the

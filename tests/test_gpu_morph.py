@@ -12,49 +12,14 @@ import torch
 
 import morph_model as M
 import transform_model as T
+from list_op_harness import Bytes, check_call, colours, last_error, on_device
 
 pytestmark = pytest.mark.gpu
 
-DEV = torch.device("cuda", 0)
-GUARD = 0xA5
-GUARD_BYTES = 64
 MENGER_MRGB = (0, 0xB0, 0xD0, 0x60)
 
 
 # ---- helpers -----------------------------------------------------------------------------------------------------------------------
-def on_device(a):
-    return torch.as_tensor(np.ascontiguousarray(a), device=DEV)
-
-
-def last_error(ctx):
-    return (ctx._L.vxrt_last_error() or b"").decode()
-
-
-class Bytes:
-    """n bytes of device memory between guard bytes, starting `shift` bytes past a 16-byte boundary"""
-    def __init__(self, n, shift=0, fill=None):
-        self.n, self.lead = n, GUARD_BYTES + shift
-        self.buf = torch.full((n + 2 * GUARD_BYTES + 16,), GUARD, dtype=torch.uint8, device=DEV)
-        assert self.buf.data_ptr() % 16 == 0
-        if fill is not None and n:
-            self.buf[self.lead:self.lead + n] = on_device(np.ascontiguousarray(fill).view(np.uint8).reshape(-1))
-        torch.cuda.synchronize()
-        self.ptr = C.c_void_p(self.buf.data_ptr() + self.lead)
-
-    def all(self):
-        return self.buf.cpu().numpy()
-
-    def guards_hold(self):
-        b = self.all()
-        return bool((b[:self.lead] == GUARD).all()) and bool((b[self.lead + self.n:] == GUARD).all())
-
-    def untouched(self):
-        return bool((self.all() == GUARD).all())
-
-    def data(self):
-        return self.all()[self.lead:self.lead + self.n].copy()
-
-
 def raw(ctx, pos, mrgb, n, op, c, steps, out_pos, out_mrgb, cap, count=True):
     """The C call over raw addresses -> (status, *n_out)."""
     torch.cuda.synchronize()
@@ -69,49 +34,15 @@ def check(ctx, pos, mrgb, op, c, steps, what, shift=0):
     what = f"{what}: {M.NAMES[op]} at {c}, {steps} step(s)"
     pos = np.ascontiguousarray(pos, np.int16).reshape(-1, 3)
     mrgb = None if mrgb is None else np.ascontiguousarray(mrgb, np.uint8).reshape(-1, 4)
-    n = len(pos)
     want_pos, want_mrgb = M.morph(pos, mrgb, op, c, steps)
-    k = len(want_pos)
-    ins = [Bytes(6 * n, shift, pos), None if mrgb is None else Bytes(4 * n, shift, mrgb)]
-    ptr = [None if b is None else b.ptr for b in ins]
-    args = (ctx, ptr[0], ptr[1], n, op, c, steps)
-    assert raw(*args, None, None, 0) == (0, k), (what, "count only", last_error(ctx))
-    assert raw(*args, None, None, 12345) == (0, k), (what, "count only ignores cap")
-    outs = []
-    for turn in range(2):
-        out_pos, out_mrgb = Bytes(6 * k, shift), (None if mrgb is None else Bytes(4 * k, shift))
-        assert raw(*args, out_pos.ptr, None if out_mrgb is None else out_mrgb.ptr, k) == (0, k), (what, f"call {turn}", last_error(ctx))
-        assert out_pos.guards_hold() and (out_mrgb is None or out_mrgb.guards_hold()), f"{what}: guard bytes"
-        outs.append((out_pos, out_mrgb))
-    got_pos = outs[0][0].data().view(np.int16).reshape(-1, 3)
-    assert np.array_equal(got_pos, want_pos), f"{what}: {int((got_pos != want_pos).any(axis=1).sum())} of {k} positions differ"
-    got_mrgb = None
-    if mrgb is not None:
-        got_mrgb = outs[0][1].data().reshape(-1, 4)
-        assert np.array_equal(got_mrgb, want_mrgb), f"{what}: {int((got_mrgb != want_mrgb).any(axis=1).sum())} of {k} voxels' bytes differ"
-    assert outs[1][0].all().tobytes() == outs[0][0].all().tobytes(), f"{what}: a second call"
-    assert mrgb is None or outs[1][1].all().tobytes() == outs[0][1].all().tobytes(), f"{what}: a second call"
-    for b, v, name in zip(ins, (pos, mrgb), ("pos", "mrgb")):
-        assert b is None or (b.guards_hold() and b.data().tobytes() == v.tobytes()), f"{what}: {name} was written"
-    # the wrapper, counting first and with room to spare
-    dev = [on_device(pos), None if mrgb is None else on_device(mrgb)]
-    for cap in (None, k + 3):
-        w_pos, w_mrgb = ctx.morph_voxels(*dev, op, c, steps, cap=cap)
-        assert w_pos.dtype == torch.int16 and w_pos.device == DEV and tuple(w_pos.shape) == (k, 3), what
-        assert np.array_equal(w_pos.cpu().numpy(), want_pos), f"{what}: the wrapper"
-        assert (w_mrgb is None) == (mrgb is None)
-        if mrgb is not None:
-            assert w_mrgb.dtype == torch.uint8 and tuple(w_mrgb.shape) == (k, 4) and np.array_equal(w_mrgb.cpu().numpy(), want_mrgb), f"{what}: the wrapper"
-    return got_pos, got_mrgb
+    return check_call(ctx, lambda ptr, *out: raw(ctx, *ptr, len(pos), op, c, steps, *out),
+                      lambda dev, cap: ctx.morph_voxels(*dev, op, c, steps, cap=cap),
+                      [("pos", pos), ("mrgb", mrgb)], want_pos, want_mrgb, what, shift)
 
 
 def check_ops(ctx, pos, mrgb, c, what, steps=1, shift=0):
     """All four ops -> the results' sizes."""
     return [len(check(ctx, pos, mrgb, op, c, steps, what, shift)[0]) for op in M.OPS]
-
-
-def colours(n, seed):
-    return np.random.default_rng(seed).integers(0, 256, (n, 4)).astype(np.uint8)
 
 
 def cells(*p):

@@ -13,50 +13,15 @@ import torch
 import ray_families as R
 import setops_model as S
 import transform_model as T
+from list_op_harness import Bytes, by_path, check_call, colours, last_error, on_device
 
 pytestmark = pytest.mark.gpu
 
-DEV = torch.device("cuda", 0)
-GUARD = 0xA5
-GUARD_BYTES = 64
 MENGER_MRGB = (0, 0xB0, 0xD0, 0x60)
 WITH_B_BYTES = (S.UNION, S.XOR, S.CHANGED)
 
 
 # ---- helpers -----------------------------------------------------------------------------------------------------------------------
-def on_device(a):
-    return torch.as_tensor(np.ascontiguousarray(a), device=DEV)
-
-
-def last_error(ctx):
-    return (ctx._L.vxrt_last_error() or b"").decode()
-
-
-class Bytes:
-    """n bytes of device memory between guard bytes, starting `shift` bytes past a 16-byte boundary"""
-    def __init__(self, n, shift=0, fill=None):
-        self.n, self.lead = n, GUARD_BYTES + shift
-        self.buf = torch.full((n + 2 * GUARD_BYTES + 16,), GUARD, dtype=torch.uint8, device=DEV)
-        assert self.buf.data_ptr() % 16 == 0
-        if fill is not None and n:
-            self.buf[self.lead:self.lead + n] = on_device(np.ascontiguousarray(fill).view(np.uint8).reshape(-1))
-        torch.cuda.synchronize()
-        self.ptr = C.c_void_p(self.buf.data_ptr() + self.lead)
-
-    def all(self):
-        return self.buf.cpu().numpy()
-
-    def guards_hold(self):
-        b = self.all()
-        return bool((b[:self.lead] == GUARD).all()) and bool((b[self.lead + self.n:] == GUARD).all())
-
-    def untouched(self):
-        return bool((self.all() == GUARD).all())
-
-    def data(self):
-        return self.all()[self.lead:self.lead + self.n].copy()
-
-
 def raw(ctx, a_pos, a_mrgb, na, b_pos, b_mrgb, nb, op, out_pos, out_mrgb, cap, count=True):
     """The C call over raw addresses -> (status, *n_out)."""
     torch.cuda.synchronize()
@@ -71,56 +36,15 @@ def check(ctx, a_pos, a_mrgb, b_pos, b_mrgb, op, what, shift=0):
     what = f"{what}: {S.NAMES[op]}"
     a_pos, b_pos = (np.ascontiguousarray(p, np.int16).reshape(-1, 3) for p in (a_pos, b_pos))
     a_mrgb, b_mrgb = (None if c is None else np.ascontiguousarray(c, np.uint8).reshape(-1, 4) for c in (a_mrgb, b_mrgb))
-    na, nb = len(a_pos), len(b_pos)
     want_pos, want_mrgb = S.combine(a_pos, a_mrgb, b_pos, b_mrgb, op)
-    k = len(want_pos)
-    ins = [Bytes(6 * na, shift, a_pos), None if a_mrgb is None else Bytes(4 * na, shift, a_mrgb),
-           Bytes(6 * nb, shift, b_pos), None if b_mrgb is None else Bytes(4 * nb, shift, b_mrgb)]
-    given = [a_pos, a_mrgb, b_pos, b_mrgb]
-    ptr = [None if b is None else b.ptr for b in ins]
-    args = (ctx, ptr[0], ptr[1], na, ptr[2], ptr[3], nb, op)
-    assert raw(*args, None, None, 0) == (0, k), (what, "count only", last_error(ctx))
-    assert raw(*args, None, None, 12345) == (0, k), (what, "count only ignores cap")
-    outs = []
-    for turn in range(2):
-        out_pos, out_mrgb = Bytes(6 * k, shift), (None if a_mrgb is None else Bytes(4 * k, shift))
-        assert raw(*args, out_pos.ptr, None if out_mrgb is None else out_mrgb.ptr, k) == (0, k), (what, f"call {turn}", last_error(ctx))
-        assert out_pos.guards_hold() and (out_mrgb is None or out_mrgb.guards_hold()), f"{what}: guard bytes"
-        outs.append((out_pos, out_mrgb))
-    got_pos = outs[0][0].data().view(np.int16).reshape(-1, 3)
-    assert np.array_equal(got_pos, want_pos), f"{what}: {int((got_pos != want_pos).any(axis=1).sum())} of {k} positions differ"
-    got_mrgb = None
-    if a_mrgb is not None:
-        got_mrgb = outs[0][1].data().reshape(-1, 4)
-        assert np.array_equal(got_mrgb, want_mrgb), f"{what}: {int((got_mrgb != want_mrgb).any(axis=1).sum())} of {k} voxels' bytes differ"
-    assert outs[1][0].all().tobytes() == outs[0][0].all().tobytes(), f"{what}: a second call"
-    assert a_mrgb is None or outs[1][1].all().tobytes() == outs[0][1].all().tobytes(), f"{what}: a second call"
-    for b, v, name in zip(ins, given, ("a_pos", "a_mrgb", "b_pos", "b_mrgb")):
-        assert b is None or (b.guards_hold() and b.data().tobytes() == v.tobytes()), f"{what}: {name} was written"
-    # the wrapper, counting first and with room to spare
-    dev = [None if v is None else on_device(v) for v in given]
-    for cap in (None, k + 3):
-        w_pos, w_mrgb = ctx.combine_voxels(*dev, op, cap=cap)
-        assert w_pos.dtype == torch.int16 and w_pos.device == DEV and tuple(w_pos.shape) == (k, 3), what
-        assert np.array_equal(w_pos.cpu().numpy(), want_pos), f"{what}: the wrapper"
-        assert (w_mrgb is None) == (a_mrgb is None)
-        if a_mrgb is not None:
-            assert w_mrgb.dtype == torch.uint8 and tuple(w_mrgb.shape) == (k, 4) and np.array_equal(w_mrgb.cpu().numpy(), want_mrgb), f"{what}: the wrapper"
-    return got_pos, got_mrgb
+    return check_call(ctx, lambda ptr, *out: raw(ctx, ptr[0], ptr[1], len(a_pos), ptr[2], ptr[3], len(b_pos), op, *out),
+                      lambda dev, cap: ctx.combine_voxels(*dev, op, cap=cap),
+                      [("a_pos", a_pos), ("a_mrgb", a_mrgb), ("b_pos", b_pos), ("b_mrgb", b_mrgb)], want_pos, want_mrgb, what, shift)
 
 
 def check_ops(ctx, a, b, what, shift=0):
     """All five ops with bytes -> the results' sizes."""
     return [len(check(ctx, *a, *b, op, what, shift)[0]) for op in S.OPS]
-
-
-def colours(n, seed):
-    return np.random.default_rng(seed).integers(0, 256, (n, 4)).astype(np.uint8)
-
-
-def by_path(pos):
-    """Distinct positions, in path order."""
-    return np.array(sorted({tuple(p) for p in np.asarray(pos).tolist()}, key=T.path_key), np.int16).reshape(-1, 3)
 
 
 @pytest.fixture(scope="module")

@@ -13,50 +13,15 @@ import torch
 
 import ray_families as R
 import transform_model as T
+from list_op_harness import Bytes, check_call, last_error, on_device
 
 pytestmark = pytest.mark.gpu
 
-DEV = torch.device("cuda", 0)
-GUARD = 0xA5
-GUARD_BYTES = 64
 MENGER_MRGB = (0, 0xB0, 0xD0, 0x60)
 LOOP_CELLS = 30000        # boxes up to this many cells are walked by the model's Python loop
 
 
 # ---- helpers -----------------------------------------------------------------------------------------------------------------------
-def on_device(a):
-    return torch.as_tensor(np.ascontiguousarray(a), device=DEV)
-
-
-def last_error(ctx):
-    return (ctx._L.vxrt_last_error() or b"").decode()
-
-
-class Bytes:
-    """n bytes of device memory between guard bytes, starting `shift` bytes past a 16-byte boundary"""
-    def __init__(self, n, shift=0, fill=None):
-        self.n, self.lead = n, GUARD_BYTES + shift
-        self.buf = torch.full((n + 2 * GUARD_BYTES + 16,), GUARD, dtype=torch.uint8, device=DEV)
-        assert self.buf.data_ptr() % 16 == 0
-        if fill is not None:
-            self.buf[self.lead:self.lead + n] = on_device(np.ascontiguousarray(fill).view(np.uint8).reshape(-1))
-        torch.cuda.synchronize()
-        self.ptr = C.c_void_p(self.buf.data_ptr() + self.lead)
-
-    def all(self):
-        return self.buf.cpu().numpy()
-
-    def guards_hold(self):
-        b = self.all()
-        return bool((b[:self.lead] == GUARD).all()) and bool((b[self.lead + self.n:] == GUARD).all())
-
-    def untouched(self):
-        return bool((self.all() == GUARD).all())
-
-    def data(self):
-        return self.all()[self.lead:self.lead + self.n].copy()
-
-
 def affine(H, m, t, reserved=0):
     a = H.Affine()
     for i in range(3):
@@ -86,42 +51,12 @@ def model(pos, mrgb, m, t, box_min, box_max):
 def check(H, ctx, pos, mrgb, m, t, box_min, box_max, what, want=None, shift=0):
     """One list, map and box through every form of the call against the model -> (pos, mrgb) of the result."""
     pos = np.ascontiguousarray(pos, np.int16).reshape(-1, 3)
-    n = len(pos)
+    mrgb = None if mrgb is None else np.ascontiguousarray(mrgb, np.uint8).reshape(-1, 4)
     want_pos, want_mrgb = model(pos, mrgb, m, t, box_min, box_max) if want is None else want
-    k = len(want_pos)
     pull = affine(H, m, t)
-    src_pos = Bytes(6 * n, shift, pos)
-    src_mrgb = None if mrgb is None else Bytes(4 * n, shift, np.ascontiguousarray(mrgb, np.uint8))
-    p_ptr, m_ptr = src_pos.ptr, (None if src_mrgb is None else src_mrgb.ptr)
-    args = (ctx, p_ptr, m_ptr, n, pull, box_min, box_max)
-    assert raw(*args, None, None, 0) == (0, k), (what, "count only", last_error(ctx))
-    assert raw(*args, None, None, 12345) == (0, k), (what, "count only ignores cap")
-    outs = []
-    for turn in range(2):
-        out_pos, out_mrgb = Bytes(6 * k, shift), (None if mrgb is None else Bytes(4 * k, shift))
-        assert raw(*args, out_pos.ptr, None if out_mrgb is None else out_mrgb.ptr, k) == (0, k), (what, f"call {turn}", last_error(ctx))
-        assert out_pos.guards_hold() and (out_mrgb is None or out_mrgb.guards_hold()), f"{what}: guard bytes"
-        outs.append((out_pos, out_mrgb))
-    got_pos = outs[0][0].data().view(np.int16).reshape(-1, 3)
-    assert np.array_equal(got_pos, want_pos), f"{what}: {int((got_pos != want_pos).any(axis=1).sum())} of {k} positions differ"
-    got_mrgb = None
-    if mrgb is not None:
-        got_mrgb = outs[0][1].data().reshape(-1, 4)
-        assert np.array_equal(got_mrgb, want_mrgb), f"{what}: {int((got_mrgb != want_mrgb).any(axis=1).sum())} of {k} voxels' bytes differ"
-    assert outs[1][0].all().tobytes() == outs[0][0].all().tobytes(), f"{what}: a second call"
-    assert mrgb is None or outs[1][1].all().tobytes() == outs[0][1].all().tobytes(), f"{what}: a second call"
-    assert src_pos.guards_hold() and np.array_equal(src_pos.data().view(np.int16).reshape(-1, 3), pos), f"{what}: pos was written"
-    assert mrgb is None or (src_mrgb.guards_hold() and np.array_equal(src_mrgb.data().reshape(-1, 4), mrgb)), f"{what}: mrgb was written"
-    # the wrapper, counting first and with room to spare
-    d_pos, d_mrgb = on_device(pos), (None if mrgb is None else on_device(np.ascontiguousarray(mrgb, np.uint8)))
-    for cap in (None, k + 3):
-        w_pos, w_mrgb = ctx.transform_voxels(d_pos, d_mrgb, pull, box_min, box_max, cap=cap)
-        assert w_pos.dtype == torch.int16 and w_pos.device == DEV and tuple(w_pos.shape) == (k, 3), what
-        assert np.array_equal(w_pos.cpu().numpy(), want_pos), f"{what}: the wrapper"
-        assert (w_mrgb is None) == (mrgb is None)
-        if mrgb is not None:
-            assert w_mrgb.dtype == torch.uint8 and tuple(w_mrgb.shape) == (k, 4) and np.array_equal(w_mrgb.cpu().numpy(), want_mrgb), f"{what}: the wrapper"
-    return got_pos, got_mrgb
+    return check_call(ctx, lambda ptr, *out: raw(ctx, *ptr, len(pos), pull, box_min, box_max, *out),
+                      lambda dev, cap: ctx.transform_voxels(*dev, pull, box_min, box_max, cap=cap),
+                      [("pos", pos), ("mrgb", mrgb)], want_pos, want_mrgb, what, shift)
 
 
 def box_of(pos, grow=0):
