@@ -16,7 +16,8 @@
 //   api_transform.hip  a device voxel list resampled under a fixed-point affine map (vxrt_transform.h)
 //   api_setops.hip   two device voxel lists combined: union, intersection, difference, delta (vxrt_setops.h)
 //   api_morph.hip    a device voxel list dilated, eroded, or cut to its surface layer or margin ring (vxrt_morph.h)
-//   list_ops.hip     no entry point: the host pipeline those three share (list_ops.h)
+//   api_mesh.hip     a device voxel list's exposed faces as an indexed triangle mesh (vxrt_mesh.h)
+//   list_ops.hip     no entry point: the host pipeline those four share (list_ops.h)
 #pragma once
 #include <hip/hip_runtime.h>
 

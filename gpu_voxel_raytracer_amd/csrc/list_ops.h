@@ -1,7 +1,8 @@
 // list_ops.h — the host pipeline behind the operators that take voxel lists in device memory and give one back (api_transform.hip,
 // api_setops.hip, api_morph.hip): a list keyed at depth 15, sorted and deduplicated; a scan's total read back; two sorted unique
-// sets merged under a set operation; the checks of the two output arrays and the decode into them.  Host code only: the kernels
-// are device_edit.hip's, device_build.hip's, setops.hip's and transform.hip's.  DESIGN.md §26.
+// sets merged under a set operation; the checks of the two output arrays and the decode into them.  api_mesh.hip, which gives a
+// mesh back, takes the front, the total and the input's checks from here.  Host code only: the kernels are device_edit.hip's,
+// device_build.hip's, setops.hip's and transform.hip's.  DESIGN.md §26.
 #pragma once
 #include <utility>
 

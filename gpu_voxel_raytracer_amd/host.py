@@ -239,6 +239,8 @@ PICK_MISS, PICK_HIT, PICK_CAP = 0, 1, 2
 LIST_UNION, LIST_INTERSECT, LIST_DIFFERENCE, LIST_XOR, LIST_CHANGED = 0, 1, 2, 3, 4
 # vxrt_morph_op (include/vxrt_morph.h)
 MORPH_DILATE, MORPH_ERODE, MORPH_SURFACE, MORPH_MARGIN = 0, 1, 2, 3
+# vxrt_mesh_mode (include/vxrt_mesh.h)
+MESH_FACES, MESH_RUNS = 0, 1
 
 
 class Camera:
@@ -1397,6 +1399,55 @@ class Context:
             return int(got.value)
         # an empty tensor has no address to tell "no mrgb" from "no entries" by: the result is empty either way
         return self._list_result(run, mrgb is not None, len(pos) == 0, cap)
+
+    def mesh_voxels(self, pos, mrgb, mode=MESH_RUNS, cap=None):
+        """vxrt_mesh_voxels_device (include/vxrt_mesh.h): the exposed faces of the list pos / mrgb as an indexed triangle mesh ->
+        (verts float32 [V,3], tris int32 [T,3], tri_mrgb uint8 [T,4]) as torch tensors on the context's device: what voxelize_mesh
+        and voxelize_solid take (tris holds the library's uint32 bits).  MESH_FACES: one quad (two triangles) per face; MESH_RUNS:
+        one per run of consecutive faces of one row and one colour.  Vertices ascend by (x, y, z), each once; quads are in face-key
+        order (direction, plane, row, cell).  mrgb=None: positions only, runs merge across colours and the third value is None.
+        pos (int16 [n,3]) and mrgb (uint8 [n,4]) are contiguous torch tensors on the context's device, or numpy arrays, which are
+        uploaded with torch once every check has passed.  cap=None: the list is meshed twice, once to count and once into tensors
+        of exactly that size; cap=(v, t): one call into tensors with room for v vertices and t triangles, cut to the counts; more
+        of either is an error (VXRT_E_INVALID).  8 vertices and 12 triangles per entry always suffice.  Ordered on both sides
+        against torch's current stream.  No scene is needed or touched."""
+        import torch
+        self._list_check(pos, mrgb)
+        self._int_of(mode, (MESH_FACES, MESH_RUNS), "mode must be MESH_FACES or MESH_RUNS")
+        if cap is not None:
+            if not isinstance(cap, (tuple, list)) or len(cap) != 2:
+                raise ValueError("cap must be (vertices, triangles)")
+            for k in cap:
+                self._cap(k)
+                if k is None:
+                    raise ValueError("cap must be (vertices, triangles)")
+        dev = torch.device("cuda", self.device)
+        pos = self._query_tensor(pos)
+        mrgb = None if mrgb is None else self._query_tensor(mrgb)
+        n_verts, n_tris = C.c_size_t(0), C.c_size_t(0)
+
+        def run(verts, tris, tri_mrgb, vert_cap, tri_cap):
+            self._chk(self._L.vxrt_mesh_voxels_device(
+                self._h, _dptr(pos), _dptr(mrgb), C.c_size_t(len(pos)), C.c_uint32(int(mode)), _dptr(verts), C.c_size_t(vert_cap), _dptr(tris),
+                _dptr(tri_mrgb), C.c_size_t(tri_cap), C.byref(n_verts), C.byref(n_tris)), "vxrt_mesh_voxels_device")
+            return int(n_verts.value), int(n_tris.value)
+        # an empty tensor has no address to tell "no mrgb" from "no entries" by: the result is empty either way
+        if len(pos) == 0:
+            cap = (0, 0)
+        if cap is None:
+            with self._ordered():
+                cap = run(None, None, None, 0, 0)
+        vert_cap, tri_cap = int(cap[0]), int(cap[1])
+        verts = torch.empty((vert_cap, 3), dtype=torch.float32, device=dev)
+        tris = torch.empty((tri_cap, 3), dtype=torch.int32, device=dev)
+        tri_mrgb = torch.empty((tri_cap, 4), dtype=torch.uint8, device=dev) if mrgb is not None else None
+        v = t = 0
+        if len(pos):
+            if vert_cap == 0 or tri_cap == 0:      # an empty tensor has no address: a list with an entry has a face, so this cannot fit
+                raise VxrtError(E_INVALID, "vxrt_mesh_voxels_device", "cap has no room for a vertex or a triangle")
+            with self._ordered():
+                v, t = run(verts, tris, tri_mrgb, vert_cap, tri_cap)
+        return verts[:v], tris[:t], (None if tri_mrgb is None else tri_mrgb[:t])
 
     def close_voxels(self, pos, mrgb, connectivity=6, steps=1):
         """morph_voxels MORPH_DILATE, then MORPH_ERODE of the result: pinholes and gaps up to 2 * steps cells wide are filled, with the

@@ -29,6 +29,7 @@
 #include "vxrt_query.h"
 #include "vxrt_scene_depth.h"
 #include "vxrt_setops.h"
+#include "vxrt_mesh.h"
 #include "vxrt_morph.h"
 #include "vxrt_solid.h"
 #include "vxrt_transform.h"
@@ -308,6 +309,17 @@ class Context {
         check(vxrt_morph_voxels_device(ctx_, pos, mrgb, n, uint32_t(op), connectivity, steps, out_pos, out_mrgb, cap, &count),
               "vxrt_morph_voxels_device");
         return count;
+    }
+    // vxrt_mesh.h: the list's exposed faces (device memory; mrgb == nullptr: positions only) as an indexed triangle mesh, one quad
+    // per face (VXRT_MESH_FACES) or per run of faces of one row and colour (VXRT_MESH_RUNS).  out_verts == out_tris == nullptr
+    // counts only.  Returns {vertices, triangles}.
+    std::pair<size_t, size_t> mesh_voxels_device(const int16_t (*pos)[3], const uint8_t (*mrgb)[4], size_t n, vxrt_mesh_mode mode = VXRT_MESH_RUNS,
+                                                 float (*out_verts)[3] = nullptr, size_t vert_cap = 0, uint32_t (*out_tris)[3] = nullptr,
+                                                 uint8_t (*out_tri_mrgb)[4] = nullptr, size_t tri_cap = 0) {
+        size_t verts = 0, tris = 0;
+        check(vxrt_mesh_voxels_device(ctx_, pos, mrgb, n, uint32_t(mode), out_verts, vert_cap, out_tris, out_tri_mrgb, tri_cap, &verts, &tris),
+              "vxrt_mesh_voxels_device");
+        return {verts, tris};
     }
     // vxrt_set_voxel_grid (vxrt_grid.h): dims[0] x dims[1] x dims[2] cells in device memory of the context's device, C order
     // [x][y][z], cell (i, j, k) at origin + (i, j, k); palette: 256 entries for VXRT_GRID_PALETTE8, nullptr for VXRT_GRID_WORD32
