@@ -29,13 +29,14 @@ def raw(ctx, pos, mrgb, n, mode, verts, vert_cap, tris, tri_mrgb, tri_cap, given
     return rc, v.value, t.value
 
 
-def check(ctx, pos, mrgb, mode, what, shift=0, round_trip=None):
+def check(ctx, pos, mrgb, mode, what, shift=0, round_trip=None, want=None):
     """A list and a mode through every form of the call against the model -> (verts, tris, tri_mrgb) of the result.  The inputs and
-    out_tri_mrgb start `shift` bytes past a 16-byte boundary, out_verts and out_tris 4 * shift (mod 16) bytes past one."""
+    out_tri_mrgb start `shift` bytes past a 16-byte boundary, out_verts and out_tris 4 * shift (mod 16) bytes past one.  want: the
+    model's result, where the caller has it already."""
     what = f"{what}: {MM.NAMES[mode]}"
     pos = np.ascontiguousarray(pos, np.int16).reshape(-1, 3)
     mrgb = None if mrgb is None else np.ascontiguousarray(mrgb, np.uint8).reshape(-1, 4)
-    want_verts, want_tris, want_mrgb = MM.mesh(pos, mrgb, mode)
+    want_verts, want_tris, want_mrgb = MM.mesh(pos, mrgb, mode) if want is None else want
     nv, nt, n = len(want_verts), len(want_tris), len(pos)
     assert nv <= 8 * n and nt <= 12 * n
     aligned = 4 * shift % 16

@@ -29,12 +29,13 @@ def raw(ctx, pos, mrgb, n, op, c, steps, out_pos, out_mrgb, cap, count=True):
     return rc, got.value
 
 
-def check(ctx, pos, mrgb, op, c, steps, what, shift=0):
-    """A list, an op, a connectivity and a depth through every form of the call against the model -> (pos, mrgb) of the result."""
+def check(ctx, pos, mrgb, op, c, steps, what, shift=0, want=None):
+    """A list, an op, a connectivity and a depth through every form of the call against the model -> (pos, mrgb) of the result.
+    want: the model's result, where the caller has it already."""
     what = f"{what}: {M.NAMES[op]} at {c}, {steps} step(s)"
     pos = np.ascontiguousarray(pos, np.int16).reshape(-1, 3)
     mrgb = None if mrgb is None else np.ascontiguousarray(mrgb, np.uint8).reshape(-1, 4)
-    want_pos, want_mrgb = M.morph(pos, mrgb, op, c, steps)
+    want_pos, want_mrgb = M.morph(pos, mrgb, op, c, steps) if want is None else want
     return check_call(ctx, lambda ptr, *out: raw(ctx, *ptr, len(pos), op, c, steps, *out),
                       lambda dev, cap: ctx.morph_voxels(*dev, op, c, steps, cap=cap),
                       [("pos", pos), ("mrgb", mrgb)], want_pos, want_mrgb, what, shift)

@@ -31,12 +31,13 @@ def raw(ctx, a_pos, a_mrgb, na, b_pos, b_mrgb, nb, op, out_pos, out_mrgb, cap, c
     return rc, got.value
 
 
-def check(ctx, a_pos, a_mrgb, b_pos, b_mrgb, op, what, shift=0):
-    """Two lists and an op through every form of the call against the model -> (pos, mrgb) of the result."""
+def check(ctx, a_pos, a_mrgb, b_pos, b_mrgb, op, what, shift=0, want=None):
+    """Two lists and an op through every form of the call against the model -> (pos, mrgb) of the result.  want: the model's result,
+    where the caller has it already."""
     what = f"{what}: {S.NAMES[op]}"
     a_pos, b_pos = (np.ascontiguousarray(p, np.int16).reshape(-1, 3) for p in (a_pos, b_pos))
     a_mrgb, b_mrgb = (None if c is None else np.ascontiguousarray(c, np.uint8).reshape(-1, 4) for c in (a_mrgb, b_mrgb))
-    want_pos, want_mrgb = S.combine(a_pos, a_mrgb, b_pos, b_mrgb, op)
+    want_pos, want_mrgb = S.combine(a_pos, a_mrgb, b_pos, b_mrgb, op) if want is None else want
     return check_call(ctx, lambda ptr, *out: raw(ctx, ptr[0], ptr[1], len(a_pos), ptr[2], ptr[3], len(b_pos), op, *out),
                       lambda dev, cap: ctx.combine_voxels(*dev, op, cap=cap),
                       [("a_pos", a_pos), ("a_mrgb", a_mrgb), ("b_pos", b_pos), ("b_mrgb", b_mrgb)], want_pos, want_mrgb, what, shift)

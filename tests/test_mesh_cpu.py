@@ -346,35 +346,49 @@ def key_cases():
         n = int(rng.integers(1, 200))
         pos = (rng.integers(0, side, (n, 3)) + origin).astype(np.int16)
         cases.append(("random", pos, None if rng.random() < 0.3 else MM.three_colours(n, int(rng.integers(100)))))
+    # keys whose coordinates differ in bits 6 to 14, and patches on every face, edge and corner of the range (list_families.py)
+    import list_families as LF
+    for case in (LF.seams()[0], LF.range_faces()[0]):
+        cases.append((case.name, case.pos, case.mrgb))
     return cases
 
 
+def run_rule_program(exe, runs):
+    """runs: [(mode, with words, keys, words)] through the program (test_morph_cpu.build_rule_program of DRIVER) ->
+    [(verts float32 [V,3], rows int64 [T,4]: a triangle's three indices and its quad's leaf word)] per run, each held to the counts
+    the program prints in front of it."""
+    text = "".join(f"{mode} {1 if with_words else 0} {len(keys)}\n" + "".join(f"{k} {w}\n" for k, w in zip(keys, words)) for mode, with_words, keys, words in runs)
+    run = subprocess.run([exe], input=text, capture_output=True, text=True)
+    assert run.returncode == 0 and not run.stderr.strip(), (run.returncode, run.stderr[-2000:])
+    lines = iter(run.stdout.split("\n"))
+    results = []
+    for n in range(len(runs)):
+        head = next(lines).split()
+        assert len(head) == 3 and head[0] == "mesh", (n, head)
+        n_verts, n_tris = int(head[1]), int(head[2])
+        verts = np.array([next(lines).split() for _ in range(n_verts)], np.float64).reshape(-1, 3).astype(np.float32)
+        rows = np.array([next(lines).split() for _ in range(n_tris)], np.int64).reshape(-1, 4)
+        results.append((verts, rows))
+    assert next(lines) == ""
+    return results
+
+
 def test_the_kernels_arithmetic_under_the_sanitizers(tmp_path):
-    src = tmp_path / "rule.cpp"
-    src.write_text(DRIVER)
-    exe = tmp_path / "rule"
-    build = subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=undefined,address", "-fno-sanitize-recover=all", "-static-libasan",
-                            "-I", CSRC, str(src), "-o", str(exe)], capture_output=True, text=True)
-    assert build.returncode == 0, build.stderr
+    from test_morph_cpu import build_rule_program
+    exe = build_rule_program(tmp_path, DRIVER)
     runs = []
     for name, pos, mrgb in key_cases():
         keys, words = M.sorted_keys_words(pos, mrgb)
         for mode in MM.MODES:
             runs.append((name, pos, mrgb, mode, keys, words))
-    text = "".join(f"{mode} {0 if mrgb is None else 1} {len(keys)}\n" + "".join(f"{k} {w}\n" for k, w in zip(keys, words))
-                   for _, _, mrgb, mode, keys, words in runs)
-    run = subprocess.run([str(exe)], input=text, capture_output=True, text=True)
-    assert run.returncode == 0 and not run.stderr.strip(), (run.returncode, run.stderr[-2000:])
-    lines = iter(run.stdout.split("\n"))
     merged = 0
-    for name, pos, mrgb, mode, _, _ in runs:
+    results = run_rule_program(exe, [(mode, mrgb is not None, keys, words) for _, _, mrgb, mode, keys, words in runs])
+    for (name, pos, mrgb, mode, _, _), (got, rows) in zip(runs, results):
         verts, tris, out = MM.mesh(pos, mrgb, mode)
-        assert next(lines) == f"mesh {len(verts)} {len(tris)}", (name, MM.NAMES[mode])
-        got = np.array([next(lines).split() for _ in range(len(verts))], np.float64).reshape(-1, 3).astype(np.float32)
+        assert (len(got), len(rows)) == (len(verts), len(tris)), (name, MM.NAMES[mode])
         assert got.tobytes() == verts.tobytes(), (name, MM.NAMES[mode])
-        rows = np.array([next(lines).split() for _ in range(len(tris))], np.int64).reshape(-1, 4)
         assert np.array_equal(rows[:, :3], tris), (name, MM.NAMES[mode])
         if mrgb is not None:
             assert [M.word_bytes(int(w)) for w in rows[:, 3]] == [tuple(b) for b in out.tolist()], (name, MM.NAMES[mode])
         merged += mode == MM.RUNS and len(tris) < len(MM.mesh(pos, mrgb, MM.FACES)[1])
-    assert merged > 10 and next(lines) == ""
+    assert merged > 10

@@ -434,36 +434,59 @@ def key_cases():
         n = int(rng.integers(1, 300))
         cells = (rng.integers(0, side, (n, 3)) + origin).astype(np.int16)
         cases.append((cells, colours(n), [(int(rng.choice(M.OPS)), int(rng.choice(M.CONNECTIVITIES)), int(rng.integers(1, 4)))]))
+    # steps through carries and borrows of 6 to 14 bits, and patches on every face, edge and corner of the range (list_families.py)
+    import list_families as LF
+    for case in (LF.seams()[0], LF.range_faces()[0]):
+        cases.append((case.pos, case.mrgb, [(M.DILATE, 26, 1), (M.ERODE, 18, 1), (M.SURFACE, 26, 1), (M.MARGIN, 6, 1), (M.DILATE, 6, 2)]))
     return cases
 
 
-def test_the_kernels_arithmetic_under_the_sanitizers(tmp_path):
+SANITIZED = ["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=undefined,address", "-fno-sanitize-recover=all", "-static-libasan"]
+
+
+def build_rule_program(tmp_path, driver=None):
+    """DRIVER (or another file's) compiled under the sanitizers into a program of its own -> its path"""
     src = tmp_path / "rule.cpp"
-    src.write_text(DRIVER)
+    src.write_text(DRIVER if driver is None else driver)
     exe = tmp_path / "rule"
-    build = subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=undefined,address", "-fno-sanitize-recover=all", "-static-libasan",
-                            "-I", CSRC, str(src), "-o", str(exe)], capture_output=True, text=True)
+    build = subprocess.run(SANITIZED + ["-I", CSRC, str(src), "-o", str(exe)], capture_output=True, text=True)
     assert build.returncode == 0, build.stderr
+    return str(exe)
+
+
+def run_rule_program(exe, runs):
+    """runs: [(keys, words, op, c, steps)] through the program -> [[(key, word)]] per run, each held to the count the program
+    prints behind it; the table it prints first is held to the model's."""
+    text = "".join(f"{op} {c} {steps} {len(keys)}\n" + "".join(f"{k} {w}\n" for k, w in zip(keys, words)) for keys, words, op, c, steps in runs)
+    run = subprocess.run([exe], input=text, capture_output=True, text=True)
+    assert run.returncode == 0 and not run.stderr.strip(), (run.returncode, run.stderr[-2000:])
+    lines = iter(run.stdout.split("\n"))
+    for r, o in enumerate(M.OFFSETS):
+        assert next(lines) == f"row {r} {o[0]} {o[1]} {o[2]} {M.OFFSETS.index((-o[0], -o[1], -o[2]))}"
+    results = []
+    for n, (keys, _, op, c, steps) in enumerate(runs):
+        got = []
+        for line in lines:
+            if line.startswith("end"):
+                assert line == f"end {len(got)}", (n, M.NAMES[op], c, steps, line, len(got))
+                break
+            got.append(tuple(int(v) for v in line.split()))
+        results.append(got)
+    assert next(lines) == ""
+    return results
+
+
+def test_the_kernels_arithmetic_under_the_sanitizers(tmp_path):
+    exe = build_rule_program(tmp_path)
     runs = []
     for pos, mrgb, params in key_cases():
         keys, words = M.sorted_keys_words(pos, mrgb)
         for op, c, steps in params:
             runs.append((keys, words, op, c, steps))
-    text = "".join(f"{op} {c} {steps} {len(keys)}\n" + "".join(f"{k} {w}\n" for k, w in zip(keys, words)) for keys, words, op, c, steps in runs)
-    run = subprocess.run([str(exe)], input=text, capture_output=True, text=True)
-    assert run.returncode == 0 and not run.stderr.strip(), (run.returncode, run.stderr[-2000:])
-    lines = iter(run.stdout.split("\n"))
-    for r, o in enumerate(M.OFFSETS):
-        assert next(lines) == f"row {r} {o[0]} {o[1]} {o[2]} {M.OFFSETS.index((-o[0], -o[1], -o[2]))}"
     kept_any = {op: 0 for op in M.OPS}
-    for n, (keys, words, op, c, steps) in enumerate(runs):
+    for n, ((keys, words, op, c, steps), got) in enumerate(zip(runs, run_rule_program(exe, runs))):
         want = M.morph_keys(keys, words, op, c, steps)
-        got = []
-        for line in lines:
-            if line.startswith("end"):
-                assert line == f"end {len(want)}", (n, M.NAMES[op], c, steps, line, len(want))
-                break
-            got.append(tuple(int(v) for v in line.split()))
+        assert len(got) == len(want), (n, M.NAMES[op], c, steps, len(got), len(want))
         assert got == want, (n, M.NAMES[op], c, steps, len(keys))
         kept_any[op] += len(want)
-    assert all(kept_any.values()) and next(lines) == ""
+    assert all(kept_any.values())

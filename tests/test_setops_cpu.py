@@ -362,28 +362,35 @@ def test_the_straddle_lists_straddle():
     assert sum(1 for p, q in pairs_at if p % 8 == 7) == 256 and (2047, 2048) in pairs_at      # a pair across every thread boundary, one across the block's
 
 
-def test_the_kernels_arithmetic_under_the_sanitizers(tmp_path):
-    src = tmp_path / "rule.cpp"
-    src.write_text(DRIVER)
-    exe = tmp_path / "rule"
-    build = subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=undefined,address", "-fno-sanitize-recover=all", "-static-libasan",
-                            "-I", CSRC, str(src), "-o", str(exe)], capture_output=True, text=True)
-    assert build.returncode == 0, build.stderr
-    cases = [(op, c) for c in key_cases() for op in S.OPS]
+def run_rule_program(exe, cases):
+    """cases: [(op, (a_keys, a_words, b_keys, b_words))] through the program (test_morph_cpu.build_rule_program of DRIVER) ->
+    [[(key, word)]] per case, each held to the count the program prints behind it."""
     text = "".join(f"{op} {len(c[0])} {len(c[2])}\n" + "".join(f"{k} {v}\n" for k, v in zip(c[0], c[1])) + "".join(f"{k} {v}\n" for k, v in zip(c[2], c[3]))
                    for op, c in cases)
-    run = subprocess.run([str(exe)], input=text, capture_output=True, text=True)
+    run = subprocess.run([exe], input=text, capture_output=True, text=True)
     assert run.returncode == 0 and not run.stderr.strip(), run.stderr[-2000:]
     lines = iter(run.stdout.split("\n"))
-    kept_any = {op: 0 for op in S.OPS}
+    results = []
     for n, (op, c) in enumerate(cases):
-        want = S.combine_keys(*c, op)
         got = []
         for line in lines:
             if line.startswith("end"):
-                assert line == f"end {len(want)}", (n, S.NAMES[op], line, len(want))
+                assert line == f"end {len(got)}", (n, S.NAMES[op], line, len(got))
                 break
             got.append(tuple(int(v) for v in line.split()))
+        results.append(got)
+    assert next(lines) == ""
+    return results
+
+
+def test_the_kernels_arithmetic_under_the_sanitizers(tmp_path):
+    from test_morph_cpu import build_rule_program
+    exe = build_rule_program(tmp_path, DRIVER)
+    cases = [(op, c) for c in key_cases() for op in S.OPS]
+    kept_any = {op: 0 for op in S.OPS}
+    for n, ((op, c), got) in enumerate(zip(cases, run_rule_program(exe, cases))):
+        want = S.combine_keys(*c, op)
+        assert len(got) == len(want), (n, S.NAMES[op], len(got), len(want))
         assert got == want, (n, S.NAMES[op], len(c[0]), len(c[2]))
         kept_any[op] += len(want)
-    assert all(kept_any.values()) and next(lines) == ""
+    assert all(kept_any.values())
