@@ -60,6 +60,8 @@ void free_images(vxrt_ctx* c) {
     }
     c->queues.clear();
     c->queue_bytes = 0;
+    for (uint4* p : c->first_hits) { if (p) (void)hipFree(p); }
+    c->first_hits.clear();
 }
 
 int alloc_images(vxrt_ctx* c) {
@@ -141,6 +143,13 @@ int alloc_images(vxrt_ctx* c) {
                 sq.rq.seg_capacity = unsigned(cap);
             }
         }
+    }
+    // shared primary rays (VXRT_OPT_SHARED_PRIMARY): a stream's first-hit records, 16 bytes per pixel of the band; never read before
+    // first_hit_kernel has written them in the same launch, so they start uninitialised
+    if (c->batch >= 2 && c->band.local_rows > 0) {
+        c->first_hits.resize(size_t(c->inflight), nullptr);
+        for (uint4*& p : c->first_hits)
+            HIP_TRY(hipMalloc(reinterpret_cast<void**>(&p), size_t(c->band.local_rows) * size_t(c->band.width) * sizeof(uint4)));
     }
     const size_t tiles = trace_tile_count(c->band.width, c->band.local_rows);
     c->schedules.resize(size_t(c->inflight));
@@ -332,6 +341,10 @@ int apply_option(vxrt_ctx* c, uint32_t option, uint32_t value, bool at_create) {
         case VXRT_OPT_FRAME_LANES:
             if (value > 1) { set_error("frame lanes must be 0 or 1"); return VXRT_E_INVALID; }
             c->frame_lanes = int(value);
+            return VXRT_OK;
+        case VXRT_OPT_SHARED_PRIMARY:
+            if (value > 1) { set_error("shared primary must be 0 or 1"); return VXRT_E_INVALID; }
+            c->shared_primary = int(value);
             return VXRT_OK;
         case VXRT_OPT_HALO_ROWS:
             if (value > 4096) { set_error("halo rows must be 0..4096"); return VXRT_E_INVALID; }
@@ -857,6 +870,7 @@ int vxrt_reset_stats(vxrt_ctx* c) try {
     c->ms[0] = c->ms[1] = c->ms[2] = c->ms[3] = c->ms[4] = 0.0;
     c->halo_exchanges = 0;
     c->frame_lane_launches = 0;
+    c->shared_primary_launches = 0;
     c->split_launches = 0;
     return VXRT_OK;
 } VXRT_CATCH

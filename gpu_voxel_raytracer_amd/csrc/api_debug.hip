@@ -182,6 +182,12 @@ int vxrt_debug_culled_pixels(vxrt_ctx* c, uint64_t* count) try {
     return VXRT_OK;
 } VXRT_CATCH
 
+int vxrt_debug_shared_primary_launches(vxrt_ctx* c, uint64_t* count) try {
+    if (!valid_ctx(c) || !count) { set_error("null argument"); return VXRT_E_INVALID; }
+    *count = c->shared_primary_launches;
+    return VXRT_OK;
+} VXRT_CATCH
+
 #if VXRT_VARIANTS
 // PROTOTYPE (csrc/trace_dda.hip; -DVXRT_VARIANTS=1 builds only): the same rays through the exact walk (cast_probe_kernel over the
 // context's scene format) and through the three-level DDA over a bit grid that is built on the device from the scene in place (first

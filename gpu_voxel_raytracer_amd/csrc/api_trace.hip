@@ -96,6 +96,7 @@ void frame_constants(const vxrt_ctx* c, TraceArgs& a) {
     a.launch_index = 0;
     a.block_first = 0;
     a.cull = 0;
+    a.first_hit = nullptr;
     a.stack_levels = c->depth < 1 ? 1 : int(c->depth);
 #if VXRT_VARIANTS
     a.touch_nodes = c->d_touch_nodes;
@@ -325,6 +326,21 @@ int trace_frames(vxrt_ctx* c, uint32_t g, bool timed, int* slots, Cam* cams, Cam
         // frames per launch the pair wins (0.123 ms per frame at 16 x 2)
         const bool one_at_a_time = g == 1 && c->inflight == 1;
         const int variant = (c->auto_tracer && (scene_bytes > (size_t(256) << 20) || one_at_a_time)) ? 0 : c->trace_variant;
+        // Shared primary rays (VXRT_OPT_SHARED_PRIMARY): when every frame of the launch has the camera of the first — decided by
+        // comparing the cameras, not by who called — first_hit_kernel walks the band's primary rays once, ahead of trace_kernel on
+        // this stream and inside the timed region, and trace_kernel's lanes load their pixel's record instead of casting.  The
+        // records belong to this launch alone: the next launch on the stream writes them again before it reads them.  Not for the
+        // wide records, nor for a scene beyond the Infinity Cache (its kernel stays as measured: DESIGN.md section 5).
+        bool share = c->shared_primary && g >= 2 && lane < c->first_hits.size() && c->first_hits[lane] != nullptr && !use_wide(c) &&
+                     scene_bytes <= (size_t(256) << 20);
+        for (uint32_t k = 1; share && k < g; k++) share = memcmp(&cams[k], &cams[0], sizeof(Cam)) == 0;
+        auto share_primary = [&]() -> int {
+            if (!share) return VXRT_OK;
+            a.first_hit = c->first_hits[lane];
+            HIP_TRY(launch_first_hit(a, ts));
+            c->shared_primary_launches++;
+            return VXRT_OK;
+        };
         if (variant == 0 || variant >= 4) {
             if (variant >= 4) {
                 // count sets rotate as in launch_trace_wavefront: launch J reads set J%3, writes (J+1)%3, clears (J+2)%3
@@ -405,6 +421,7 @@ int trace_frames(vxrt_ctx* c, uint32_t g, bool timed, int* slots, Cam* cams, Cam
                     HIP_TRY(hipEventRecord(c->aux_join[lane], c->aux_streams[lane]));
                 }
 #endif
+                if (int rc = share_primary()) return rc;
                 if (int rc = launch_trace_split(c, a, use_wide(c) && c->trace_variant == 4, scene_bytes > (size_t(256) << 20), ts, lane, g, long_blocks)) return rc;
 #if VXRT_VARIANTS
                 if (c->head_stagger) {
@@ -445,6 +462,7 @@ int trace_frames(vxrt_ctx* c, uint32_t g, bool timed, int* slots, Cam* cams, Cam
                 if (long_blocks != 0u) HIP_TRY(hipStreamWaitEvent(ts, c->aux_join[lane], 0));   // the launch is over when both grids are
                 }   // !fused_done
             } else {
+                if (int rc = share_primary()) return rc;
                 if (int rc = launch_trace_split(c, a, use_wide(c), scene_bytes > (size_t(256) << 20), ts, lane, g)) return rc;
                 if (a.frame_lanes && !use_wide(c) && scene_bytes <= (size_t(256) << 20)) c->frame_lane_launches++;
             }

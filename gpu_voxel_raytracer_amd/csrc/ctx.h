@@ -271,6 +271,10 @@ struct vxrt_ctx {
     unsigned wave_slots = 5120;   // waves of trace_kernel the device holds at once: CUs x 4 SIMDs x 5 (vxrt_create)
     int frame_lanes = 1;   // trace_kernel may put 8 frames of a pixel row into a wave (TraceArgs::frame_lanes; VXRT_OPT_FRAME_LANES)
     uint32_t frame_lane_launches = 0;
+    // VXRT_OPT_SHARED_PRIMARY: a launch of >= 2 frames of ONE camera walks each pixel's primary ray once (trace.hip: first_hit_kernel).
+    int shared_primary = 1;
+    uint64_t shared_primary_launches = 0;   // vxrt_debug_shared_primary_launches
+    std::vector<uint4*> first_hits;         // per trace stream: one 16-byte record per pixel of the band (contexts with frames_per_launch >= 2)
     int path_blocks = 512;  // tracer 5: blocks of path_kernel (each wave takes an equal range of the queue, >= 512 paths)
     int tail_from = 1;  // tracer 4: the hit number at which live paths move to the compacted launches
     unsigned tail_split = 0;  // ... bit k: the tail compacts again and starts a new launch at path segment k

@@ -149,6 +149,10 @@ struct TraceArgs {
     int frame_lanes;       // trace_kernel: 0, or the frames a wave holds: 8 (of a row of 8 pixels) or 4 (of two rows) — one camera for the launch, whole groups
     int cull;
     float cull_min[3], cull_max[3];
+    // Shared primary rays (VXRT_OPT_SHARED_PRIMARY; trace.hip: first_hit_kernel): when every frame of the launch has the camera cams[0],
+    // one record per pixel of the band — what cast_bounded_ray returns for that pixel's primary ray — written by first_hit_kernel ahead
+    // of trace_kernel on the same stream, and loaded by trace_block in place of a walking lane's first cast.  null: every frame casts.
+    uint4* first_hit;         // [local_rows * width]  (bits(hit.time), hit.node, normal as pack_axis x | y << 2 | z << 4, hit ? 1 : 0)
 #if VXRT_VARIANTS
     // Touch map (vxrt_debug_touch_map; -DVXRT_VARIANTS=1 only): when set, every scene load of the walk marks the 64-byte line it reads —
     // bit (index * record bytes) >> 6 of touch_nodes for a node record (8-byte or wide), of touch_leaves for a leaf word — so that the
@@ -236,6 +240,8 @@ size_t fused_ctl_profile_offset();
 hipError_t launch_fused(const TraceArgs& a, void* ctl, unsigned waves, const uint32_t* sort_scratch, uint32_t stamp, hipStream_t s);
 // blocks [block_first, block_first + block_count) of the launch's tiles x frames; block_count 0: all of them
 hipError_t launch_trace(const TraceArgs& a, bool wide, bool hbm_scene, hipStream_t s, unsigned block_first = 0, unsigned block_count = 0);
+// the primary rays of camera a.cams[0], one wave per 8 x 8 pixel tile of the band -> a.first_hit (TraceArgs::first_hit); 8-byte records only
+hipError_t launch_first_hit(const TraceArgs& a, hipStream_t s);
 // test hook: the walk (cast_ray) for caller-given rays; out = 8 floats per ray (hit, time, bits(leaf word), normal, 0, 0)
 hipError_t launch_path_log(const TraceArgs& a, bool wide, int x, int y, float* log, hipStream_t s);
 hipError_t launch_count_culled(const TraceArgs& a, unsigned long long* count, hipStream_t s);   // diagnostics: pixels the sky cull decides

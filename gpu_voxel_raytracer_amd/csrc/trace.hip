@@ -27,11 +27,40 @@ namespace vxrt {
 namespace {
 
 
-template <bool kWide, int kWaves, int kF>
+template <bool kWide, int kWaves, int kF, bool kShare>
 __global__ __launch_bounds__(kTB, kWaves) void trace_kernel(const TraceArgs a) {
     extern __shared__ uint4 lds_stack[];  // the threads' frames: Caster<kWide>
     // a launch may come as two grids (the longest tiles apart: VXRT_OPT_LONG_TILES)
-    trace_block<kWide, kF, false>(a, blockIdx.x + a.block_first, lds_stack, 0u);
+    trace_block<kWide, kF, false, kShare>(a, blockIdx.x + a.block_first, lds_stack, 0u);
+}
+
+// Shared primary rays (VXRT_OPT_SHARED_PRIMARY).  The frames of a launch that share one camera have, pixel by pixel, the same primary
+// ray — origin, direction and scene — and so the same first hit, bit for bit.  With frame lanes a wave of trace_kernel holds 8 copies
+// of 8 such rays and walks them once per group of 8 frames; here one wave walks the 64 DIFFERENT primary rays of an 8 x 8 pixel tile,
+// once per launch, and trace_block loads the result where it would cast.  Same ray expressions and the same sky cull as trace_block
+// (a culled or inactive lane stores nothing: trace_block never reads its entry), the same Caster — the regular walk or the shader's
+// literal one, by the ray.  Runs ahead of trace_kernel on the launch's stream; the stream's order is the only synchronisation.
+__global__ __launch_bounds__(64) void first_hit_kernel(const TraceArgs a) {
+    extern __shared__ uint4 lds_stack[];
+    const int lane = int(threadIdx.x);
+    const unsigned tiles_x = unsigned(a.band.width + 7) / 8u;
+    // with one-wave blocks the tiles are trace_kernel's: the longest of the previous frames first
+    const unsigned tile = (kTB == 64 && a.tile_order) ? a.tile_order[blockIdx.x] : blockIdx.x;
+    const int x = int(tile % tiles_x) * 8 + (lane & 7);
+    const int lrow = int(tile / tiles_x) * 8 + (lane >> 3);
+    const int y = frame_row(a.band, lrow);
+    if (!(x < a.band.width && lrow < a.band.local_rows && y < a.band.height)) return;
+    const Cam& cam = a.cams[0];
+    const f3 o = ld3(cam.o);
+    const f3 d = norm3((float(x) * ld3(cam.r) - float(y) * ld3(cam.u)) + ld3(cam.f));  // voxels.comp:299-303
+    if (primary_miss_is_certain(a, o, d)) return;
+    const Caster<false> caster(a, lds_stack, lane);
+    RayHit hit;
+    hit.time = 0.0f; hit.node = 0; hit.normal = splat3(0.0f);
+    const bool is_hit = caster.cast(o, d, hit);
+    const f3 n = hit.normal;
+    a.first_hit[size_t(lrow) * a.band.width + x] =
+        make_uint4(vx_f2u(hit.time), uint32_t(hit.node), pack_axis(n.x) | pack_axis(n.y) << 2 | pack_axis(n.z) << 4, is_hit ? 1u : 0u);
 }
 
 
@@ -275,25 +304,31 @@ hipError_t launch_trace(const TraceArgs& args, bool wide, bool hbm_scene, hipStr
     // those kernels exist with one frame per wave only (for a scene in HBM, config 5 at 16 spp, frame lanes measured 7 % slower: 14.9
     // against 13.9 ms per displayed frame — a wave's 64 pixels are neighbours in the tree, its 8 frames of 8 pixels less so)
     if (hbm_scene || wide || kTB != 64) a.frame_lanes = 0;
+    if (hbm_scene || wide) a.first_hit = nullptr;   // those kernels are compiled without the load (trace_block: kShare)
     const unsigned all_blocks = trace_tile_count(a.band.width, a.band.local_rows) * unsigned(a.batch);   // kF parts x batch / kF groups per tile
     if (block_first >= all_blocks) return hipSuccess;
     dim3 grid(block_count == 0u || block_count > all_blocks - block_first ? all_blocks - block_first : block_count);
     const size_t lds = caster_lds_bytes(a, wide, kTB);
 #if VXRT_VARIANTS
     if (wide) {
-        hipLaunchKernelGGL((trace_kernel<true, VXRT_TRACE_WAVES, 1>), grid, dim3(kTB), lds, s, a);
+        hipLaunchKernelGGL((trace_kernel<true, VXRT_TRACE_WAVES, 1, false>), grid, dim3(kTB), lds, s, a);
         return hipGetLastError();
     }
 #endif
     constexpr int kF8 = kTB == 64 ? 8 : 1, kF4 = kTB == 64 ? 4 : 1;
-    if (hbm_scene) hipLaunchKernelGGL((trace_kernel<false, VXRT_TRACE_WAVES_HBM, 1>), grid, dim3(kTB), lds, s, a);
-    else if (a.frame_lanes == 8) hipLaunchKernelGGL((trace_kernel<false, VXRT_TRACE_WAVES, kF8>), grid, dim3(kTB), lds, s, a);
-    else if (a.frame_lanes == 4) hipLaunchKernelGGL((trace_kernel<false, VXRT_TRACE_WAVES, kF4>), grid, dim3(kTB), lds, s, a);
-    else hipLaunchKernelGGL((trace_kernel<false, VXRT_TRACE_WAVES, 1>), grid, dim3(kTB), lds, s, a);
+    if (hbm_scene) hipLaunchKernelGGL((trace_kernel<false, VXRT_TRACE_WAVES_HBM, 1, false>), grid, dim3(kTB), lds, s, a);
+    else if (a.frame_lanes == 8) hipLaunchKernelGGL((trace_kernel<false, VXRT_TRACE_WAVES, kF8, true>), grid, dim3(kTB), lds, s, a);
+    else if (a.frame_lanes == 4) hipLaunchKernelGGL((trace_kernel<false, VXRT_TRACE_WAVES, kF4, true>), grid, dim3(kTB), lds, s, a);
+    else hipLaunchKernelGGL((trace_kernel<false, VXRT_TRACE_WAVES, 1, true>), grid, dim3(kTB), lds, s, a);
     return hipGetLastError();
 }
 
-
+hipError_t launch_first_hit(const TraceArgs& a, hipStream_t s) {
+    if (a.band.local_rows <= 0 || a.first_hit == nullptr) return hipSuccess;
+    const unsigned tiles = unsigned(a.band.width + 7) / 8u * (unsigned(a.band.local_rows + 7) / 8u);
+    hipLaunchKernelGGL(first_hit_kernel, dim3(tiles), dim3(64), caster_lds_bytes(a, false, kTB), s, a);
+    return hipGetLastError();
+}
 
 hipError_t launch_tile_order(uint32_t* cost, uint32_t* order, uint32_t* last_cost, uint32_t* scratch, unsigned tiles, unsigned waves_x_launches,
                              unsigned wave_slots, int spread_override, hipStream_t s) {

@@ -81,7 +81,9 @@ constexpr int kTileW = kTB == 64 ? 8 : 16, kTileH = kTB == 256 ? 16 : 8;
 // pixels x 8 frames, 64-byte segments, is priced 3 % better and measured 6 % worse).  The per-pixel operations are the same either way.
 // kFused: the block is one item of fused_kernel's head phase — `bid` comes from its work cursor, and a path that is handed over is
 // stored for a consumer that may be polling the record already (queue_store_fused).
-template <bool kWide, int kF, bool kFused>
+// kShare: the block may take its first hits from first_hit_kernel's records (TraceArgs::first_hit, when the launch carries them);
+// false for the kernels that never do — the wide records, the HBM-scene instantiation, fused_kernel — which stay as they were.
+template <bool kWide, int kF, bool kFused, bool kShare = false>
 __device__ __forceinline__ void trace_block(const TraceArgs& a, const unsigned bid, uint4* lds_stack, const uint32_t stamp) {
     static_assert(kF == 1 || ((kF == 4 || kF == 8) && kTB == 64), "frame lanes: one wave per block");
     const int tid = threadIdx.x;
@@ -168,7 +170,20 @@ __device__ __forceinline__ void trace_block(const TraceArgs& a, const unsigned b
         for (;;) {
             RayHit hit;
             rays++;
-            const bool is_hit = caster.cast(o, d, hit);
+            bool is_hit;
+            // Shared primary rays (TraceArgs::first_hit): the launch's frames have one camera, and first_hit_kernel has cast this
+            // pixel's primary ray already — the same ray, by the same Caster.  bounce == 0 outside the sun phase holds in a lane's
+            // first trip only, and the walking lanes of a wave make that trip together: all of them load, nobody walks.  The ray
+            // is counted as always (one cast_bounded_ray of the shader, like a culled primary ray).
+            if (kShare && a.first_hit != nullptr && bounce == 0 && !sun_phase) {
+                const uint4 r = a.first_hit[pix];
+                hit.time = vx_u2f(r.x);
+                hit.node = int32_t(r.y);
+                hit.normal = mk3(unpack_axis(r.z & 3u), unpack_axis((r.z >> 2) & 3u), unpack_axis((r.z >> 4) & 3u));
+                is_hit = r.w != 0u;
+            } else {
+                is_hit = caster.cast(o, d, hit);
+            }
 
 #if !VXRT_DEFER_SHADING
             if (sun_phase) {  // back from the sun shadow ray                 voxels.comp:357-371

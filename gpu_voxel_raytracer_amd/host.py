@@ -125,6 +125,7 @@ OPT_DENOISE_MODE, OPT_TAIL_CAPACITY, OPT_SCENE_FORMAT, OPT_HALO_ROWS, OPT_SKY_CU
 (OPT_TILE_ORDER, OPT_TILE_SPREAD, OPT_TRACE_BLOCKS, OPT_TAIL_FROM, OPT_TAIL_SPLIT, OPT_HOST_SCENE_BUILD, OPT_TRACER_OVERRIDE,
  OPT_TRACE_SPLIT, OPT_PATH_BLOCKS, OPT_SHADE_BLOCKS, OPT_RAYS_PER_WAVE, OPT_NODE_ORDER, OPT_HEAD_STAGGER, OPT_LONG_TILES, OPT_FUSED_TAIL,
  OPT_TRACE_PRIORITY, OPT_XCD_AFFINITY) = range(7, 24)      # include/vxrt_debug.h (the options of experiments)
+OPT_SHARED_PRIMARY = 24                                    # include/vxrt.h (a product option: the next free id)
 TILE_SPREAD_AUTO = 0xffffffff
 
 
@@ -142,7 +143,8 @@ ENV_KNOBS = {"VXRT_SKY_CULL": OPT_SKY_CULL, "VXRT_HALO_ROWS": OPT_HALO_ROWS, "VX
              "VXRT_RAYS_PER_WAVE": OPT_RAYS_PER_WAVE, "VXRT_TRACE_BLOCKS": OPT_TRACE_BLOCKS, "VXRT_FRAME_LANES": OPT_FRAME_LANES,
              "VXRT_SPREAD": OPT_TILE_SPREAD, "VXRT_TILE_ORDER": OPT_TILE_ORDER, "VXRT_TRACE_SPLIT": OPT_TRACE_SPLIT,
              "VXRT_HOST_BUILD": OPT_HOST_SCENE_BUILD, "VXRT_NODE_ORDER": OPT_NODE_ORDER, "VXRT_HEAD_STAGGER": OPT_HEAD_STAGGER, "VXRT_LONG_TILES": OPT_LONG_TILES, "VXRT_FUSED_TAIL": OPT_FUSED_TAIL,
-             "VXRT_TRACE_PRIORITY": OPT_TRACE_PRIORITY, "VXRT_XCD_AFFINITY": OPT_XCD_AFFINITY}
+             "VXRT_TRACE_PRIORITY": OPT_TRACE_PRIORITY, "VXRT_XCD_AFFINITY": OPT_XCD_AFFINITY,
+             "VXRT_SHARED_PRIMARY": OPT_SHARED_PRIMARY}
 _env_knobs_enabled = os.environ.get("VXRT_ENV_KNOBS") == "1"      # the explicit opt-in of the A/B scripts (scripts/*.sh)
 
 
@@ -1612,6 +1614,12 @@ class Context:
         n = C.c_uint64(0)
         self.update_bindings()
         self._chk(self._L.vxrt_debug_culled_pixels(self._h, C.byref(n)), "vxrt_debug_culled_pixels")
+        return int(n.value)
+
+    def shared_primary_launches(self):
+        """vxrt_debug_shared_primary_launches: trace launches whose frames shared one walk of the primary rays (OPT_SHARED_PRIMARY)."""
+        n = C.c_uint64(0)
+        self._chk(self._L.vxrt_debug_shared_primary_launches(self._h, C.byref(n)), "vxrt_debug_shared_primary_launches")
         return int(n.value)
 
     def set_option(self, option, value):

@@ -134,6 +134,10 @@ int vxrt_debug_tile_order(vxrt_ctx* ctx, uint32_t* order, uint32_t* cost, size_t
  * test instead of walking the octree.  They are counted in vxrt_stats.rays (each is one cast_bounded_ray of voxels.comp:134-247,
  * answered without a walk); for a camera at rest, rays per frame minus this = the rays that walked. */
 int vxrt_debug_culled_pixels(vxrt_ctx* ctx, uint64_t* count);
+/* Diagnostics: trace launches since create / vxrt_reset_stats whose frames took their first hits from ONE walk of the primary rays
+ * (vxrt.h: VXRT_OPT_SHARED_PRIMARY).  In the frames of such a launch after the first, a pixel that is not culled has its primary
+ * ray counted in vxrt_stats.rays without a walk of its own. */
+int vxrt_debug_shared_primary_launches(vxrt_ctx* ctx, uint64_t* count);
 /* Diagnostics of trace stream 0's last fused launch (VXRT_OPT_FUSED_TAIL): shader clocks to "every head block finished" and to the last
  * wave's end, chunks taken before / after that moment, idle sleeps, stamp polls, head claims, 0. */
 int vxrt_debug_fused_profile(vxrt_ctx* ctx, uint64_t out[8]);
