@@ -163,7 +163,7 @@ int vxrt_render(vxrt_ctx* c, uint32_t flags) try {
 // `count` frames; frame k through camera pose k of `path_pos` / `path_dir` (null: the camera at rest), one launch per `batch` frames
 static int render_sequence(vxrt_ctx* c, uint32_t flags, uint32_t count, const float (*path_pos)[3], const float (*path_dir)[3]) {
     const bool timed = (flags & VXRT_TIMED) != 0;
-    const uint32_t batch = (flags & VXRT_TRACE) && (c->trace_variant == 0 || c->trace_variant >= 4) ? uint32_t(c->batch) : 1u;
+    const uint32_t batch = (flags & VXRT_TRACE) && batches_frames(c->trace_variant) ? uint32_t(c->batch) : 1u;
     if (batch <= 1) {
         for (uint32_t i = 0; i < count; i++) {
             if (path_pos) {
@@ -219,7 +219,7 @@ int vxrt_render_spp(vxrt_ctx* c, uint32_t flags, uint32_t spp) try {
     const bool timed = (flags & VXRT_TIMED) != 0;
     const size_t pixels = size_t(c->band.local_rows) * c->band.width;
     if (spp > 1 && c->spp_sum == nullptr && pixels > 0) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->spp_sum), pixels * sizeof(float4)));
-    const uint32_t batch = (c->trace_variant == 0 || c->trace_variant >= 4) ? uint32_t(c->batch) : 1u;
+    const uint32_t batch = batches_frames(c->trace_variant) ? uint32_t(c->batch) : 1u;
     Cam first_old{};
     for (uint32_t done = 0; done < spp;) {
         const uint32_t g = spp - done < batch ? spp - done : batch;

@@ -210,38 +210,108 @@ static int xcd_affine_order(vxrt_ctx* c, vxrt_ctx::TileSchedule& sched, hipStrea
     return VXRT_OK;
 }
 
-// One launch of trace_kernel over all tiles — or, with VXRT_OPT_TRACE_PRIORITY and a tile order whose walking tiles are known, as TWO
-// grids: the tiles that walk (the first `heavy` of the plain longest-first order) on the high-priority trace stream, the tiles that
-// only store sky on the lane's low-priority stream, forked and joined by events, so that the dispatcher takes blocks of the long
-// chains first whenever both grids have blocks waiting.  Same blocks, same arithmetic.
-static int launch_trace_split(vxrt_ctx* c, const TraceArgs& a, bool wide, bool hbm, hipStream_t ts, size_t lane, unsigned g, unsigned first = 0) {
-    vxrt_ctx::TileSchedule& sched = c->schedules[lane];
-    if (c->trace_priority && sched.heavy_pending && hipEventQuery(sched.heavy_ready) == hipSuccess) {
-        sched.heavy = sched.host_heavy[0];
-        sched.heavy_pending = false;
+// ---- the trace launch: what plan_trace decided (ctx.h: TracePlan), issued by one function per path -------------------------------
+
+// The three counter sets of a stream rotate as in launch_trace_wavefront: launch J reads set J % 3, writes (J + 1) % 3, clears (J + 2) % 3.
+struct CountSets {
+    unsigned* sets[3] = {nullptr, nullptr, nullptr};
+    unsigned J = 0;
+    CountSets() = default;
+    explicit CountSets(const vxrt_ctx::StreamQueues& sq) : sets{sq.counts3, sq.counts3 + 64 * 16, sq.counts3 + 2 * 64 * 16}, J(sq.launches) {}
+    unsigned* read() const { return sets[J % 3]; }
+    unsigned* written() const { return sets[(J + 1) % 3]; }
+    unsigned* cleared() const { return sets[(J + 2) % 3]; }
+};
+
+// one launch: what its steps share.  plan, a and counts are filled by the steps named after them, in that order
+struct TraceLaunch {
+    vxrt_ctx* c; hipStream_t ts; size_t lane; uint32_t g; const int* slots;
+    TracePlan plan{};
+    TraceArgs a;
+    CountSets counts;   // the stream's counter sets as this launch finds them (tracers with queues)
+    TraceLaunch(vxrt_ctx* c_, hipStream_t ts_, size_t lane_, uint32_t g_, const int* slots_) : c(c_), ts(ts_), lane(lane_), g(g_), slots(slots_) {}
+};
+
+// A camera path: the frames of a wave have cameras of their own, and what they share shrinks with the image motion across a group of
+// F frames — estimated in pixels from the poses (rotation, and translation seen from the scene's centre), the worst group's.  NaN poses
+// give NaN.  Measured on an orbit of the bench scene: + 4 % at 0.16-0.4 degrees (2-5 pixels) per 8 frames, + 2 % at 0.8 (11 pixels),
+// - 1 % at 1.6 (21), - 3 % at 4 degrees (55)
+static float path_motion_px(const vxrt_ctx* c, uint32_t g, uint32_t F, const float (*path_pos)[3], const float (*path_dir)[3]) {
+    const float f_px = 0.5f * float(c->cfg.height) / tanf(0.5f * c->cam_fov);
+    float worst = 0.0f;
+    for (uint32_t k = 0; k + F <= g; k += F) {
+        const float* p0 = path_pos[k]; const float* p1 = path_pos[k + F - 1];
+        const float* d0 = path_dir[k]; const float* d1 = path_dir[k + F - 1];
+        const float n0 = sqrtf(d0[0] * d0[0] + d0[1] * d0[1] + d0[2] * d0[2]), n1 = sqrtf(d1[0] * d1[0] + d1[1] * d1[1] + d1[2] * d1[2]);
+        float cosang = (d0[0] * d1[0] + d0[1] * d1[1] + d0[2] * d1[2]) / (n0 * n1);
+        cosang = cosang > 1.0f ? 1.0f : (cosang < -1.0f ? -1.0f : cosang);
+        const float ang = acosf(cosang);
+        const float dp = sqrtf((p1[0] - p0[0]) * (p1[0] - p0[0]) + (p1[1] - p0[1]) * (p1[1] - p0[1]) + (p1[2] - p0[2]) * (p1[2] - p0[2]));
+        float dist = sqrtf((p0[0] - c->root_center[0]) * (p0[0] - c->root_center[0]) + (p0[1] - c->root_center[1]) * (p0[1] - c->root_center[1]) +
+                           (p0[2] - c->root_center[2]) * (p0[2] - c->root_center[2]));
+        dist = dist < 0.05f * c->root_size ? 0.05f * c->root_size : dist;
+        const float px = f_px * (ang > dp / dist ? ang : dp / dist);
+        worst = !(px <= worst) ? px : worst;
     }
-    const unsigned tiles = trace_tile_count(c->band.width, c->band.local_rows);
-    const unsigned heavy = (c->trace_priority && a.tile_order != nullptr && !sched.heavy_pending && first == 0) ? sched.heavy : 0u;
-    if (heavy == 0u || heavy >= tiles) {
-        HIP_TRY(launch_trace(a, wide, hbm, ts, first, 0u));
-        return VXRT_OK;
-    }
-    HIP_TRY(hipEventRecord(c->low_fork[lane], ts));                         // after everything this launch waits for
-    HIP_TRY(hipStreamWaitEvent(c->low_streams[lane], c->low_fork[lane], 0));
-    HIP_TRY(launch_trace(a, wide, hbm, ts, 0u, heavy * g));                  // high priority: the chains
-    HIP_TRY(launch_trace(a, wide, hbm, c->low_streams[lane], heavy * g, 0u));   // low priority: the stores
-    HIP_TRY(hipEventRecord(c->low_join[lane], c->low_streams[lane]));
-    c->split_launches++;
-    return VXRT_OK;
+    return worst;
 }
 
-// The trace stage of the next g frames (parameters at rest) as ONE launch of the tracer: g ring slots, frame numbers
-// frame_number+1 .. +g.  g > 1 only with the trace_kernel-based tracers (1, 4, 5).  slots[k] = ring slot of frame k.
-// path: optional g camera poses (position, direction), one per frame; null = the camera stays where it is.  cams / olds
-// (g entries each): the camera and the "old" camera of every frame, as temporal.comp and denoise.comp of that frame see them.
-int trace_frames(vxrt_ctx* c, uint32_t g, bool timed, int* slots, Cam* cams, Cam* olds, const float (*path_pos)[3], const float (*path_dir)[3],
-                 uint32_t gbuf_frames) {
-    const uint32_t first_frame_number = c->uniforms.frame_number + 1;
+// Everything a launch of g frames on stream `lane` will do, decided here and nowhere else, into p (all zero on entry).  Calls no HIP API and changes nothing: it
+// reads the context as absorb_feedback left it (tail capacity, walking-tile count), the launch's cameras and the optional path poses.
+static void plan_trace(TracePlan& p, const vxrt_ctx* c, uint32_t g, const Cam* cams, const float (*path_pos)[3], const float (*path_dir)[3], size_t lane) {
+    const bool wide = use_wide(c);
+    const vxrt_ctx::TileSchedule& sched = c->schedules[lane];
+    const bool ordered = c->use_tile_order && sched.valid;
+    const unsigned tiles = trace_tile_count(c->band.width, c->band.local_rows);
+    p.hbm = c->svo_count * sizeof(SvoRecord) + c->leaf_count * sizeof(int32_t) > kInfinityCacheBytes;
+    // tracer 0 (auto) takes the all-in-one kernel (a) for scenes beyond the Infinity Cache (see auto_tracer) and (b) for ONE frame at
+    // a time on one stream — the latency case of a render loop that calls vxrt_render per frame: the head + tail pair waits twice
+    // for a longest wave (0.357 ms per 1080p bench frame), the single kernel once (0.267 ms); with frames in flight or several
+    // frames per launch the pair wins (0.123 ms per frame at 16 x 2)
+    p.tracer = (c->auto_tracer && (p.hbm || (g == 1 && c->inflight == 1))) ? 0 : c->trace_variant;
+    p.wide_head = wide && (p.tracer == 0 || p.tracer == 4);
+    p.wide_tail = wide;
+    // when the tail is ONE launch its counters are copied back behind it (copy_counts); a tail that compacts again starts further launches
+    p.single_tail_launch = p.tracer == 4;
+    for (int k = c->tail_from + 1; p.single_tail_launch && k < int(c->cfg.max_bounces); k++)
+        if (c->queues[lane].hitq[1] && ((c->tail_split >> k) & 1u)) p.single_tail_launch = false;
+    // Fused head + tail (VXRT_OPT_FUSED_TAIL): one grid of persistent waves takes the launch's blocks and then its queued
+    // paths, chunk by chunk as they become complete (trace.hip: fused_kernel).  For tails of ONE launch (the 4-bounce
+    // benchmark; a tail that compacts again keeps its launches), the 8-byte records, scenes in cache.
+    const bool fused = c->fused_tail && p.single_tail_launch && !wide && !p.hbm && c->tail_from < int(c->cfg.max_bounces);
+    p.path = p.tracer == 0 ? TracePath::all_in_one : p.tracer == 2 ? TracePath::wavefront : p.tracer < 4 ? TracePath::ray_queue :
+             fused ? TracePath::fused : p.tracer == 5 ? TracePath::head_paths : TracePath::head_bounces;
+    const bool trace_kernel_head = p.path == TracePath::all_in_one || p.path == TracePath::head_bounces || p.path == TracePath::head_paths;
+    // a wave of trace_kernel holds 8 (4) frames of one (two) rows of 8 pixels when the launch has whole groups of 8 (4) frames of ONE
+    // camera — or of a slow camera path: at most 16 pixels across a group.  Not the wide records' kernel, nor the one for a scene in HBM:
+    // those exist with one frame per wave only (trace.hip: launch_trace)
+    p.frame_lanes = (c->frame_lanes && !wide && !p.hbm) ? (g % 8u == 0u ? 8 : (g % 4u == 0u ? 4 : 0)) : 0;
+    if (p.frame_lanes && path_pos != nullptr && !(path_motion_px(c, g, uint32_t(p.frame_lanes), path_pos, path_dir) <= 16.0f)) p.frame_lanes = 0;
+    // Shared primary rays (VXRT_OPT_SHARED_PRIMARY): when every frame of the launch has the camera of the first — decided by
+    // comparing the cameras, not by who called — first_hit_kernel walks the band's primary rays once, ahead of trace_kernel on
+    // this stream and inside the timed region, and trace_kernel's lanes load their pixel's record instead of casting.  The
+    // records belong to this launch alone: the next launch on the stream writes them again before it reads them.  Not for the
+    // wide records, nor for a scene beyond the Infinity Cache (its kernel stays as measured: DESIGN.md section 5).
+    p.share = trace_kernel_head && c->shared_primary && g >= 2 && lane < c->first_hits.size() && c->first_hits[lane] != nullptr && !wide && !p.hbm;
+    for (uint32_t k = 1; p.share && k < g; k++) p.share = memcmp(&cams[k], &cams[0], sizeof(Cam)) == 0;
+    // (-DVXRT_VARIANTS=1 only: measured slower — the rest of the tiles are as chain-bound as the longest.)  The longest tiles apart
+    // (VXRT_OPT_LONG_TILES, per mille of the tiles): the first tiles of the launch order — the longest chains of the last frames — run
+    // as an all-in-one grid of their own on a second stream (fork_long_tiles), beside the head + tail pair of all other tiles.
+    if (p.path == TracePath::head_bounces && c->long_tiles_permille > 0 && ordered && p.tracer == 4 && !wide && !p.hbm) {
+        const unsigned n = unsigned((unsigned long long)tiles * c->long_tiles_permille / 1000u);
+        p.long_blocks = (n < 1u ? 1u : (n >= tiles ? tiles - 1u : n)) * g;
+    }
+    // the priority split (issue_trace_kernel) needs the walking tiles first in the order and their number on the host
+    if (trace_kernel_head && c->trace_priority && ordered && !sched.heavy_pending && p.long_blocks == 0u && sched.heavy < tiles) p.split_heavy = sched.heavy;
+    // Re-sort the tiles for this stream's coming frames from the costs just measured: after its first
+    // frame, then every 8th (costs keep accumulating as a running maximum in between; ~7 us per sort).
+    if (batches_frames(p.tracer) && c->use_tile_order && (!sched.valid || sched.age >= 8))
+        p.sort = (c->xcd_affinity > 0 && g == 1 && p.hbm) ? TileSort::xcd_affine : TileSort::longest_first;
+}
+
+// step 1: the cameras of the next g frames (path: optional poses, one per frame) and their frame slots: the next ones of the ring, never
+// the temporal history
+static void next_frames(vxrt_ctx* c, uint32_t g, int* slots, Cam* cams, Cam* olds, const float (*path_pos)[3], const float (*path_dir)[3]) {
     for (uint32_t k = 0; k < g; k++) {
         if (path_pos) {
             memcpy(c->cam_pos, path_pos[k], sizeof c->cam_pos);
@@ -251,16 +321,16 @@ int trace_frames(vxrt_ctx* c, uint32_t g, bool timed, int* slots, Cam* cams, Cam
         cams[k] = c->cam;
         olds[k] = c->old_cam;
     }
-    // next frame slots (never the temporal history) and the trace stream of this launch
     int s = c->slot;
     for (uint32_t k = 0; k < g; k++) {
         s = (s + 1) % int(c->ring.size());
         if (c->has_history && s == c->hist_slot) s = (s + 1) % int(c->ring.size());
         slots[k] = s;
     }
-    const size_t lane = size_t(c->trace_launches % uint64_t(c->inflight));
-    hipStream_t ts = c->trace_streams[lane];
-    vxrt_ctx::TileSchedule& sched = c->schedules[lane];
+}
+
+// step 2: the trace stream waits for whatever last used the slots
+static int wait_for_slots(vxrt_ctx* c, uint32_t g, const int* slots, hipStream_t ts) {
     hipEvent_t waited = nullptr;
     for (uint32_t k = 0; k < g; k++) {   // the slots of an earlier launch share its event: wait for each event once
         vxrt_ctx::Slot& sl = c->ring[size_t(slots[k])];
@@ -269,250 +339,255 @@ int trace_frames(vxrt_ctx* c, uint32_t g, bool timed, int* slots, Cam* cams, Cam
             waited = sl.last_use;
         }
     }
+    return VXRT_OK;
+}
 
-    TraceArgs a;
+// step 3: what earlier launches of this stream reported, polled BEFORE the launch's timed region starts and before it is planned: the
+// room its tail wanted (the queues grow: host wait + reallocation) and the number of walking tiles its last sort found
+static int absorb_feedback(vxrt_ctx* c, size_t lane) {
+    if (c->trace_variant >= 4 && !c->queues.empty()) { if (int rc = grow_tail_queues(c, lane)) return rc; }
+    vxrt_ctx::TileSchedule& sched = c->schedules[lane];
+    if (c->trace_priority && sched.heavy_pending && hipEventQuery(sched.heavy_ready) == hipSuccess) {
+        sched.heavy = sched.host_heavy[0];
+        sched.heavy_pending = false;
+    }
+    return VXRT_OK;
+}
+
+// step 5: the kernels' arguments for the planned launch
+static void fill_trace_args(TraceLaunch& L, const Cam* cams, uint32_t gbuf_frames, uint32_t first_frame_number) {
+    const vxrt_ctx* c = L.c;
+    TraceArgs& a = L.a;
+    const uint32_t g = L.g;
+    const vxrt_ctx::TileSchedule& sched = c->schedules[L.lane];
     frame_constants(c, a);
     for (uint32_t k = 0; k < g; k++) {
-        const vxrt_ctx::Slot& sl = c->ring[size_t(slots[k])];
+        const vxrt_ctx::Slot& sl = c->ring[size_t(L.slots[k])];
         a.out[k] = FrameOut{sl.sampled_color, sl.nd, sl.albedo};
+        a.cams[k] = cams[k];
     }
     a.out_color = a.out[0].color; a.out_nd = a.out[0].nd; a.out_albedo = a.out[0].albedo;
     a.batch = int(g);
     a.gbuf_frames = gbuf_frames;
-    // a wave of trace_kernel holds 8 (4) frames of one (two) rows of 8 pixels when the launch has whole groups of 8 (4) frames of ONE camera
-    a.frame_lanes = (c->frame_lanes && !use_wide(c)) ? (g % 8u == 0u ? 8 : (g % 4u == 0u ? 4 : 0)) : 0;
-    if (a.frame_lanes && path_pos != nullptr) {
-        // a camera path: the frames of a wave have cameras of their own, and what they share shrinks with the image motion across the
-        // group — estimated in pixels from the poses (rotation, and translation seen from the scene's centre).  Measured on an orbit
-        // of the bench scene: + 4 % at 0.16-0.4 degrees (2-5 pixels) per 8 frames, + 2 % at 0.8 (11 pixels), - 1 % at 1.6 (21), - 3 % at 4 degrees (55)
-        const float f_px = 0.5f * float(c->cfg.height) / tanf(0.5f * c->cam_fov);
-        float worst = 0.0f;
-        const uint32_t F = uint32_t(a.frame_lanes);
-        for (uint32_t k = 0; k + F <= g; k += F) {
-            const float* p0 = path_pos[k]; const float* p1 = path_pos[k + F - 1];
-            const float* d0 = path_dir[k]; const float* d1 = path_dir[k + F - 1];
-            const float n0 = sqrtf(d0[0] * d0[0] + d0[1] * d0[1] + d0[2] * d0[2]), n1 = sqrtf(d1[0] * d1[0] + d1[1] * d1[1] + d1[2] * d1[2]);
-            float cosang = (d0[0] * d1[0] + d0[1] * d1[1] + d0[2] * d1[2]) / (n0 * n1);
-            cosang = cosang > 1.0f ? 1.0f : (cosang < -1.0f ? -1.0f : cosang);
-            const float ang = acosf(cosang);
-            const float dp = sqrtf((p1[0] - p0[0]) * (p1[0] - p0[0]) + (p1[1] - p0[1]) * (p1[1] - p0[1]) + (p1[2] - p0[2]) * (p1[2] - p0[2]));
-            float dist = sqrtf((p0[0] - c->root_center[0]) * (p0[0] - c->root_center[0]) + (p0[1] - c->root_center[1]) * (p0[1] - c->root_center[1]) +
-                               (p0[2] - c->root_center[2]) * (p0[2] - c->root_center[2]));
-            dist = dist < 0.05f * c->root_size ? 0.05f * c->root_size : dist;
-            const float px = f_px * (ang > dp / dist ? ang : dp / dist);
-            worst = !(px <= worst) ? px : worst;   // NaN poses: no frame lanes
-        }
-        if (!(worst <= 16.0f)) a.frame_lanes = 0;
-    }
+    a.frame_lanes = L.plan.frame_lanes;
     set_cull(c, a, cams, g);
     a.ray_counter = c->d_rays;
     a.tile_order = (c->use_tile_order && sched.valid) ? sched.order : nullptr;
     a.tile_cost = c->use_tile_order ? sched.cost : nullptr;
     a.frame_number = first_frame_number;
     a.cam = cams[0];
-    for (uint32_t k = 0; k < g; k++) a.cams[k] = cams[k];
-    if (c->band.local_rows > 0) {
-        // the tail queues grow (host wait + reallocation) BEFORE the launch's timed region starts
-        if (c->trace_variant >= 4 && !c->queues.empty()) { if (int rc = grow_tail_queues(c, lane)) return rc; }
-        EventPair p;
-        if (timed) { p = take_pair(c, 0); HIP_TRY(hipEventRecord(p.a, ts)); }
-        a.tail = PathQueue{nullptr, nullptr, 0};
-        a.tail_zero = nullptr;
-        a.tail_from = 0;
-        const size_t scene_bytes = c->svo_count * sizeof(SvoRecord) + c->leaf_count * sizeof(int32_t);
-        // tracer 0 (auto) takes the all-in-one kernel (a) for scenes beyond the Infinity Cache (see auto_tracer) and (b) for ONE frame at
-        // a time on one stream — the latency case of a render loop that calls vxrt_render per frame: the head + tail pair waits twice
-        // for a longest wave (0.357 ms per 1080p bench frame), the single kernel once (0.267 ms); with frames in flight or several
-        // frames per launch the pair wins (0.123 ms per frame at 16 x 2)
-        const bool one_at_a_time = g == 1 && c->inflight == 1;
-        const int variant = (c->auto_tracer && (scene_bytes > (size_t(256) << 20) || one_at_a_time)) ? 0 : c->trace_variant;
-        // Shared primary rays (VXRT_OPT_SHARED_PRIMARY): when every frame of the launch has the camera of the first — decided by
-        // comparing the cameras, not by who called — first_hit_kernel walks the band's primary rays once, ahead of trace_kernel on
-        // this stream and inside the timed region, and trace_kernel's lanes load their pixel's record instead of casting.  The
-        // records belong to this launch alone: the next launch on the stream writes them again before it reads them.  Not for the
-        // wide records, nor for a scene beyond the Infinity Cache (its kernel stays as measured: DESIGN.md section 5).
-        bool share = c->shared_primary && g >= 2 && lane < c->first_hits.size() && c->first_hits[lane] != nullptr && !use_wide(c) &&
-                     scene_bytes <= (size_t(256) << 20);
-        for (uint32_t k = 1; share && k < g; k++) share = memcmp(&cams[k], &cams[0], sizeof(Cam)) == 0;
-        auto share_primary = [&]() -> int {
-            if (!share) return VXRT_OK;
-            a.first_hit = c->first_hits[lane];
-            HIP_TRY(launch_first_hit(a, ts));
-            c->shared_primary_launches++;
-            return VXRT_OK;
-        };
-        if (variant == 0 || variant >= 4) {
-            if (variant >= 4) {
-                // count sets rotate as in launch_trace_wavefront: launch J reads set J%3, writes (J+1)%3, clears (J+2)%3
-                vxrt_ctx::StreamQueues& sq = c->queues[lane];
-                unsigned* sets[3] = {sq.counts3, sq.counts3 + 64 * 16, sq.counts3 + 2 * 64 * 16};
-                const unsigned J = sq.launches;
-                a.tail = PathQueue{sq.hitq[0], sets[(J + 1) % 3], c->shard_capacity};
-                a.tail_zero = sets[(J + 2) % 3];
-                a.tail_from = c->tail_from;
-                // head stagger (VXRT_OPT_HEAD_STAGGER): this launch's head starts when the previous launch's head (another stream) has
-                // finished, so that a head runs beside the previous launch's tail instead of beside its head
-#if VXRT_VARIANTS
-                if (c->head_stagger && c->last_head_lane >= 0 && size_t(c->last_head_lane) != lane)
-                    HIP_TRY(hipStreamWaitEvent(ts, c->head_events[size_t(c->last_head_lane)], 0));
-#endif
-                // Fused head + tail (VXRT_OPT_FUSED_TAIL): one grid of persistent waves takes the launch's blocks and then its queued
-                // paths, chunk by chunk as they become complete (trace.hip: fused_kernel).  For tails of ONE launch (the 4-bounce
-                // benchmark; a tail that compacts again keeps its launches), the 8-byte records, scenes in cache.
-                bool fused_done = false;
-#if VXRT_VARIANTS
-                bool one_tail_launch = true;
-                for (int k = c->tail_from + 1; k < int(c->cfg.max_bounces); k++)
-                    if (sq.hitq[1] && ((c->tail_split >> k) & 1u)) one_tail_launch = false;
-                if (c->fused_tail && c->trace_variant == 4 && one_tail_launch && !use_wide(c) && scene_bytes <= (size_t(256) << 20) && c->tail_from < int(c->cfg.max_bounces)) {
-                    if (sq.fused_ctl == nullptr) {
-                        HIP_TRY(hipMalloc(&sq.fused_ctl, fused_ctl_bytes()));
-                        HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&sq.host_ctl), 64, hipHostMallocDefault));    // word 2: the kernel's error word
-                        memset(sq.host_ctl, 0, 64);
-                    }
-                    if (!sq.stamps_clean) {   // once per allocation of the queue: every slot's stamp must read 0
-                        HIP_TRY(hipMemsetAsync(sq.hitq[0], 0, (size_t(c->shard_capacity) * 64 + 1) * 64, ts));
-                        sq.stamps_clean = true;
-                    }
-                    HIP_TRY(hipMemsetAsync(sq.fused_ctl, 0, fused_ctl_bytes(), ts));
-                    const uint32_t stamp = (sq.fused_launches++ % 65535u) + 1u;
-                    const unsigned all_blocks = trace_tile_count(c->band.width, c->band.local_rows) * g;
-                    const unsigned fused_slots = c->wave_slots / 5u * 4u;      // fused_kernel is compiled for 4 waves per SIMD (trace.hip: VXRT_FUSED_WAVES)
-                    HIP_TRY(launch_fused(a, sq.fused_ctl, fused_slots < all_blocks ? fused_slots : all_blocks, a.tile_order ? sched.scratch : nullptr, stamp, ts));
-                    if (a.frame_lanes) c->frame_lane_launches++;
-                    sq.launches = J + 1;          // one kernel: it wrote set (J + 1) % 3 and cleared (J + 2) % 3, which the next launch writes
-                    if (!sq.counts_pending) {
-                        HIP_TRY(hipMemcpyAsync(sq.host_counts, sets[(J + 1) % 3], 64 * 64, hipMemcpyDeviceToHost, ts));
-                        HIP_TRY(hipMemcpyAsync(sq.host_ctl + 2, static_cast<char*>(sq.fused_ctl) + fused_ctl_error_offset(), 4, hipMemcpyDeviceToHost, ts));
-                        HIP_TRY(hipEventRecord(sq.counts_ready, ts));
-                        sq.counts_pending = true;
-                        sq.counts_capacity = c->shard_capacity;
-                    }
-                    fused_done = true;
-                }
-#endif
-                if (!fused_done) {
-                // (-DVXRT_VARIANTS=1 only: measured slower — the rest of the tiles are as chain-bound as the longest.)  The longest tiles apart (VXRT_OPT_LONG_TILES, per mille of the tiles): the first tiles of the launch order — the
-                // longest chains of the last frames — run as an all-in-one grid of their own on a second stream (no hand-over: a
-                // path's whole chain in ONE wave, begun at the launch's start), beside the head + tail pair of all other tiles.  A
-                // launch that is little more than its chains (a rank's share of a short block on 8 GPUs) is two chains long as head +
-                // tail and one as the all-in-one kernel, which in turn needs 1.3 x the instructions: this takes the one chain where
-                // it matters and the cheaper instructions everywhere else.  Same pixels, same arithmetic, either way.
-                unsigned long_blocks = 0;
-#if VXRT_VARIANTS
-                if (c->long_tiles_permille > 0 && a.tile_order != nullptr && c->trace_variant == 4 && !use_wide(c) && scene_bytes <= (size_t(256) << 20)) {
-                    const unsigned tiles = trace_tile_count(c->band.width, c->band.local_rows);
-                    unsigned n = unsigned((unsigned long long)tiles * c->long_tiles_permille / 1000u);
-                    n = n < 1u ? 1u : (n >= tiles ? tiles - 1u : n);
-                    long_blocks = n * g;
-                    if (c->aux_streams.size() <= lane) c->aux_streams.resize(lane + 1, nullptr);
-                    if (c->aux_fork.size() <= lane) { c->aux_fork.resize(lane + 1, nullptr); c->aux_join.resize(lane + 1, nullptr); }
-                    if (c->aux_streams[lane] == nullptr) {
-                        HIP_TRY(hipStreamCreateWithFlags(&c->aux_streams[lane], hipStreamNonBlocking));
-                        HIP_TRY(hipEventCreateWithFlags(&c->aux_fork[lane], hipEventDisableTiming));
-                        HIP_TRY(hipEventCreateWithFlags(&c->aux_join[lane], hipEventDisableTiming));
-                    }
-                    TraceArgs al = a;
-                    al.tail = PathQueue{nullptr, nullptr, 0};     // nothing is handed over: trace_kernel follows these paths to their end
-                    al.tail_zero = nullptr;
-                    HIP_TRY(hipEventRecord(c->aux_fork[lane], ts));                       // after everything this launch waits for
-                    HIP_TRY(hipStreamWaitEvent(c->aux_streams[lane], c->aux_fork[lane], 0));
-                    HIP_TRY(launch_trace(al, false, false, c->aux_streams[lane], 0u, long_blocks));
-                    HIP_TRY(hipEventRecord(c->aux_join[lane], c->aux_streams[lane]));
-                }
-#endif
-                if (int rc = share_primary()) return rc;
-                if (int rc = launch_trace_split(c, a, use_wide(c) && c->trace_variant == 4, scene_bytes > (size_t(256) << 20), ts, lane, g, long_blocks)) return rc;
-#if VXRT_VARIANTS
-                if (c->head_stagger) {
-                    HIP_TRY(hipEventRecord(c->head_events[lane], ts));
-                    c->last_head_lane = int(lane);
-                }
-#endif
-                if (a.frame_lanes && !(use_wide(c) && c->trace_variant == 4) && scene_bytes <= (size_t(256) << 20)) c->frame_lane_launches++;
-                sq.launches = J + 1;
-                // how much room this launch wanted: its counter set, copied back for grow_tail_queues.  The set stays untouched until
-                // launch J + 2 clears it, so when the tail is ONE launch (J + 1) the copy goes behind it — a copy between the head and
-                // the tail costs the stream ~10 us of copy-engine hand-over on a block's critical path (round 5: the time line of a
-                // rank of 8 showed trace_kernel -> 4 us copy -> 5.6 us gap -> bounce_kernel); a tail of several launches clears it sooner
-                bool single_tail_launch = c->trace_variant == 4;
-                for (int k = c->tail_from + 1; k < int(c->cfg.max_bounces); k++)
-                    if (sq.hitq[1] && ((c->tail_split >> k) & 1u)) single_tail_launch = false;
-                auto copy_counts = [&]() -> int {
-                    if (sq.counts_pending) return VXRT_OK;
-                    HIP_TRY(hipMemcpyAsync(sq.host_counts, sets[(J + 1) % 3], 64 * 64, hipMemcpyDeviceToHost, ts));
-                    HIP_TRY(hipEventRecord(sq.counts_ready, ts));
-                    sq.counts_pending = true;
-                    sq.counts_capacity = c->shard_capacity;
-                    return VXRT_OK;
-                };
-                if (!single_tail_launch) { if (int rc = copy_counts()) return rc; }
-#if VXRT_VARIANTS
-                if (c->trace_variant == 5) {
-                    HIP_TRY(launch_paths(a, a.tail, sets[J % 3], c->tail_from, c->path_blocks, ts));
-                    sq.launches = J + 2;
-                } else
-#endif
-                {
-                    // without a second queue (tail_split == 0) nothing is appended to queues[1]: its capacity 0 says so
-                    PathQueue queues[2] = {{sq.hitq[0], nullptr, c->shard_capacity}, {sq.hitq[1], nullptr, sq.hitq[1] ? c->shard_capacity : 0u}};
-                    HIP_TRY(launch_bounces(a, use_wide(c), queues, sets, &sq.launches, c->trace_blocks, sq.hitq[1] ? c->tail_split : 0u, c->tail_from, ts));
-                }
-                if (single_tail_launch) { if (int rc = copy_counts()) return rc; }
-                if (long_blocks != 0u) HIP_TRY(hipStreamWaitEvent(ts, c->aux_join[lane], 0));   // the launch is over when both grids are
-                }   // !fused_done
-            } else {
-                if (int rc = share_primary()) return rc;
-                if (int rc = launch_trace_split(c, a, use_wide(c), scene_bytes > (size_t(256) << 20), ts, lane, g)) return rc;
-                if (a.frame_lanes && !use_wide(c) && scene_bytes <= (size_t(256) << 20)) c->frame_lane_launches++;
-            }
-            if (c->trace_priority) HIP_TRY(hipStreamWaitEvent(ts, c->low_join[lane], 0));   // the launch is over when both grids are (a no-op before the first split)
-            if (timed) HIP_TRY(hipEventRecord(p.b, ts));
-            // Re-sort the tiles for this stream's coming frames from the costs just measured: after its first
-            // frame, then every 8th (costs keep accumulating as a running maximum in between; ~7 us per sort).
-            if (c->use_tile_order && (!sched.valid || sched.age >= 8)) {
-                const unsigned tiles = trace_tile_count(c->band.width, c->band.local_rows);
-                if (c->xcd_affinity > 0 && g == 1 && scene_bytes > (size_t(256) << 20)) {
-                    if (int rc = xcd_affine_order(c, sched, ts)) return rc;
-                } else {
-                // (the priority split needs the walking tiles FIRST in the order: no spreading; and their number on the host)
-                HIP_TRY(launch_tile_order(sched.cost, sched.order, sched.last_cost, sched.scratch, tiles, g * unsigned(c->inflight), c->wave_slots,
-                                          c->trace_priority ? 0 : c->spread_override, ts));
-                if (c->trace_priority) {
-                    if (sched.heavy_pending) HIP_TRY(hipEventSynchronize(sched.heavy_ready));
-                    HIP_TRY(hipMemcpyAsync(sched.host_heavy, sched.scratch + 128 * 64, sizeof(unsigned), hipMemcpyDeviceToHost, ts));
-                    HIP_TRY(hipEventRecord(sched.heavy_ready, ts));
-                    sched.heavy_pending = true;
-                }
-                }
-                sched.valid = true;
-                sched.age = 0;
-            }
-            sched.age++;
-        }
-#if VXRT_VARIANTS
-        else {
-            vxrt_ctx::StreamQueues& sq = c->queues[lane];
-            PathQueue queues[2] = {{sq.hitq[0], nullptr, c->shard_capacity}, {sq.hitq[1], nullptr, c->shard_capacity}};
-            unsigned* sets[3] = {sq.counts3, sq.counts3 + 64 * 16, sq.counts3 + 2 * 64 * 16};
-            if (c->trace_variant == 2)
-                HIP_TRY(launch_trace_wavefront(a, queues, sets, &sq.launches, c->trace_blocks, c->trace_split, ts));
-            else
-                HIP_TRY(launch_trace_rayqueue(a, queues[0], sets, &sq.launches, sq.rq, c->shade_blocks, c->trace_blocks, c->rays_per_wave, ts));
-            if (timed) HIP_TRY(hipEventRecord(p.b, ts));
-        }
-#endif
-        if (timed) c->pending.push_back(p);
+    a.tail = PathQueue{nullptr, nullptr, 0};
+    a.tail_zero = nullptr;
+    a.tail_from = 0;
+    if (L.plan.tracer != 0) L.counts = CountSets(c->queues[L.lane]);
+    if (L.plan.tracer >= 4) {   // the head hands its live paths over: to the set this launch writes, clearing the next launch's
+        a.tail = PathQueue{c->queues[L.lane].hitq[0], L.counts.written(), c->shard_capacity};
+        a.tail_zero = L.counts.cleared();
+        a.tail_from = c->tail_from;
     }
+}
+
+// How much room this launch wanted: its counter set (and, for fused_kernel, its error word: `also`), copied back for grow_tail_queues;
+// skipped while an earlier copy is pending.  The set stays untouched until launch J + 2 clears it, so when the tail is ONE launch
+// (J + 1) the copy goes behind it — a copy between the head and the tail costs the stream ~10 us of copy-engine hand-over on a block's
+// critical path (round 5: the time line of a rank of 8 showed trace_kernel -> 4 us copy -> 5.6 us gap -> bounce_kernel); a tail of
+// several launches clears it sooner
+static int copy_counts(vxrt_ctx* c, vxrt_ctx::StreamQueues& sq, const unsigned* written, hipStream_t ts, void* also_to = nullptr, const void* also_from = nullptr) {
+    if (sq.counts_pending) return VXRT_OK;
+    HIP_TRY(hipMemcpyAsync(sq.host_counts, written, 64 * 64, hipMemcpyDeviceToHost, ts));
+    if (also_to) HIP_TRY(hipMemcpyAsync(also_to, also_from, 4, hipMemcpyDeviceToHost, ts));
+    HIP_TRY(hipEventRecord(sq.counts_ready, ts));
+    sq.counts_pending = true;
+    sq.counts_capacity = c->shard_capacity;
+    return VXRT_OK;
+}
+
+// One launch of trace_kernel over the launch's tiles from block plan.long_blocks on — or, with VXRT_OPT_TRACE_PRIORITY and a tile order
+// whose walking tiles are known, as TWO grids: the tiles that walk (the first `split_heavy` of the plain longest-first order) on the
+// high-priority trace stream, the tiles that only store sky on the lane's low-priority stream, forked and joined by events, so that
+// the dispatcher takes blocks of the long chains first whenever both grids have blocks waiting.  Same blocks, same arithmetic.
+static int issue_trace_kernel(TraceLaunch& L) {
+    vxrt_ctx* c = L.c;
+    const TracePlan& p = L.plan;
+    if (p.split_heavy == 0u) {
+        HIP_TRY(launch_trace(L.a, p.wide_head, p.hbm, L.ts, p.long_blocks, 0u));
+        return VXRT_OK;
+    }
+    HIP_TRY(hipEventRecord(c->low_fork[L.lane], L.ts));                         // after everything this launch waits for
+    HIP_TRY(hipStreamWaitEvent(c->low_streams[L.lane], c->low_fork[L.lane], 0));
+    HIP_TRY(launch_trace(L.a, p.wide_head, p.hbm, L.ts, 0u, p.split_heavy * L.g));                        // high priority: the chains
+    HIP_TRY(launch_trace(L.a, p.wide_head, p.hbm, c->low_streams[L.lane], p.split_heavy * L.g, 0u));      // low priority: the stores
+    HIP_TRY(hipEventRecord(c->low_join[L.lane], c->low_streams[L.lane]));
+    return VXRT_OK;
+}
+
+// The longest tiles as an all-in-one grid of their own on the lane's second stream (no hand-over: a path's whole chain in ONE wave,
+// begun at the launch's start).  A launch that is little more than its chains (a rank's share of a short block on 8 GPUs) is two
+// chains long as head + tail and one as the all-in-one kernel, which in turn needs 1.3 x the instructions: this takes the one chain
+// where it matters and the cheaper instructions everywhere else.  Same pixels, same arithmetic, either way.
+static int fork_long_tiles(TraceLaunch& L) {
+    vxrt_ctx* c = L.c;
+    const size_t lane = L.lane;
+    if (c->aux_streams.size() <= lane) c->aux_streams.resize(lane + 1, nullptr);
+    if (c->aux_fork.size() <= lane) { c->aux_fork.resize(lane + 1, nullptr); c->aux_join.resize(lane + 1, nullptr); }
+    if (c->aux_streams[lane] == nullptr) {
+        HIP_TRY(hipStreamCreateWithFlags(&c->aux_streams[lane], hipStreamNonBlocking));
+        HIP_TRY(hipEventCreateWithFlags(&c->aux_fork[lane], hipEventDisableTiming));
+        HIP_TRY(hipEventCreateWithFlags(&c->aux_join[lane], hipEventDisableTiming));
+    }
+    TraceArgs al = L.a;
+    al.tail = PathQueue{nullptr, nullptr, 0};     // nothing is handed over: trace_kernel follows these paths to their end
+    al.tail_zero = nullptr;
+    HIP_TRY(hipEventRecord(c->aux_fork[lane], L.ts));                       // after everything this launch waits for
+    HIP_TRY(hipStreamWaitEvent(c->aux_streams[lane], c->aux_fork[lane], 0));
+    HIP_TRY(launch_trace(al, false, false, c->aux_streams[lane], 0u, L.plan.long_blocks));
+    HIP_TRY(hipEventRecord(c->aux_join[lane], c->aux_streams[lane]));
+    return VXRT_OK;
+}
+
+// The all-in-one launch, and the head of a head + tail pair: the long tiles' grid (its arguments are copied before the first hits are
+// set: it casts its own), first_hit_kernel when the launch shares its primary rays, trace_kernel.
+static int issue_head(TraceLaunch& L) {
+    if (L.plan.long_blocks != 0u) { if (int rc = fork_long_tiles(L)) return rc; }
+    if (L.plan.share) {
+        L.a.first_hit = L.c->first_hits[L.lane];
+        HIP_TRY(launch_first_hit(L.a, L.ts));
+    }
+    return issue_trace_kernel(L);
+}
+
+// the tail as launches of bounce_kernel; without a second queue (tail_split == 0) nothing is appended to queues[1]: its capacity 0 says so
+static int tail_bounces(TraceLaunch& L) {
+    vxrt_ctx* c = L.c;
+    vxrt_ctx::StreamQueues& sq = c->queues[L.lane];
+    PathQueue queues[2] = {{sq.hitq[0], nullptr, c->shard_capacity}, {sq.hitq[1], nullptr, sq.hitq[1] ? c->shard_capacity : 0u}};
+    HIP_TRY(launch_bounces(L.a, L.plan.wide_tail, queues, L.counts.sets, &sq.launches, c->trace_blocks, sq.hitq[1] ? c->tail_split : 0u, c->tail_from, L.ts));
+    return VXRT_OK;
+}
+
+#if VXRT_VARIANTS
+// the tail as one launch of path_kernel, which reads the set the head wrote and clears the one launch J read
+static int tail_paths(TraceLaunch& L) {
+    HIP_TRY(launch_paths(L.a, L.a.tail, L.counts.read(), L.c->tail_from, L.c->path_blocks, L.ts));
+    L.c->queues[L.lane].launches = L.counts.J + 2;
+    return VXRT_OK;
+}
+#endif
+
+// head + tail: trace_kernel hands the paths alive at hit tail_from to `tail`
+static int issue_head_tail(TraceLaunch& L, int (*tail)(TraceLaunch&)) {
+    vxrt_ctx* c = L.c;
+    vxrt_ctx::StreamQueues& sq = c->queues[L.lane];
+    const CountSets& counts = L.counts;
+    if (int rc = issue_head(L)) return rc;
+    if (c->head_stagger) {
+        HIP_TRY(hipEventRecord(c->head_events[L.lane], L.ts));
+        c->last_head_lane = int(L.lane);
+    }
+    sq.launches = counts.J + 1;
+    if (!L.plan.single_tail_launch) { if (int rc = copy_counts(c, sq, counts.written(), L.ts)) return rc; }
+    if (int rc = tail(L)) return rc;
+    if (L.plan.single_tail_launch) { if (int rc = copy_counts(c, sq, counts.written(), L.ts)) return rc; }
+    if (L.plan.long_blocks != 0u) HIP_TRY(hipStreamWaitEvent(L.ts, c->aux_join[L.lane], 0));   // the launch is over when both grids are
+    return VXRT_OK;
+}
+
+#if VXRT_VARIANTS
+// head and tail as ONE grid of persistent waves (plan_trace: fused).  It wrote set (J + 1) % 3 and cleared (J + 2) % 3, which the next launch writes.
+static int issue_fused(TraceLaunch& L) {
+    vxrt_ctx* c = L.c;
+    vxrt_ctx::StreamQueues& sq = c->queues[L.lane];
+    const CountSets& counts = L.counts;
+    if (sq.fused_ctl == nullptr) {
+        HIP_TRY(hipMalloc(&sq.fused_ctl, fused_ctl_bytes()));
+        HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&sq.host_ctl), 64, hipHostMallocDefault));    // word 2: the kernel's error word
+        memset(sq.host_ctl, 0, 64);
+    }
+    if (!sq.stamps_clean) {   // once per allocation of the queue: every slot's stamp must read 0
+        HIP_TRY(hipMemsetAsync(sq.hitq[0], 0, (size_t(c->shard_capacity) * 64 + 1) * 64, L.ts));
+        sq.stamps_clean = true;
+    }
+    HIP_TRY(hipMemsetAsync(sq.fused_ctl, 0, fused_ctl_bytes(), L.ts));
+    const uint32_t stamp = (sq.fused_launches++ % 65535u) + 1u;
+    const unsigned all_blocks = trace_tile_count(c->band.width, c->band.local_rows) * L.g;
+    const unsigned fused_slots = c->wave_slots / 5u * 4u;      // fused_kernel is compiled for 4 waves per SIMD (trace.hip: VXRT_FUSED_WAVES)
+    HIP_TRY(launch_fused(L.a, sq.fused_ctl, fused_slots < all_blocks ? fused_slots : all_blocks, L.a.tile_order ? c->schedules[L.lane].scratch : nullptr, stamp, L.ts));
+    sq.launches = counts.J + 1;
+    return copy_counts(c, sq, counts.written(), L.ts, sq.host_ctl + 2, static_cast<char*>(sq.fused_ctl) + fused_ctl_error_offset());
+}
+
+// tracers 2 and 3: the launches per path segment of the wavefront and of the ray queues
+static int issue_queued(TraceLaunch& L) {
+    vxrt_ctx* c = L.c;
+    vxrt_ctx::StreamQueues& sq = c->queues[L.lane];
+    PathQueue queues[2] = {{sq.hitq[0], nullptr, c->shard_capacity}, {sq.hitq[1], nullptr, c->shard_capacity}};
+    CountSets& counts = L.counts;
+    if (L.plan.path == TracePath::wavefront)
+        HIP_TRY(launch_trace_wavefront(L.a, queues, counts.sets, &sq.launches, c->trace_blocks, c->trace_split, L.ts));
+    else
+        HIP_TRY(launch_trace_rayqueue(L.a, queues[0], counts.sets, &sq.launches, sq.rq, c->shade_blocks, c->trace_blocks, c->rays_per_wave, L.ts));
+    return VXRT_OK;
+}
+#endif
+
+// step 6: the planned path's launches.  Head stagger (VXRT_OPT_HEAD_STAGGER): the head of a head + tail launch starts when the previous
+// launch's head (another stream) has finished, so that a head runs beside the previous launch's tail instead of beside its head
+static int issue(TraceLaunch& L) {
+    vxrt_ctx* c = L.c;
+    if (L.plan.tracer >= 4 && c->head_stagger && c->last_head_lane >= 0 && size_t(c->last_head_lane) != L.lane)
+        HIP_TRY(hipStreamWaitEvent(L.ts, c->head_events[size_t(c->last_head_lane)], 0));
+    switch (L.plan.path) {
+        case TracePath::all_in_one: return issue_head(L);
+        case TracePath::head_bounces: return issue_head_tail(L, tail_bounces);
+#if VXRT_VARIANTS
+        case TracePath::head_paths: return issue_head_tail(L, tail_paths);
+        case TracePath::fused: return issue_fused(L);
+        case TracePath::wavefront:
+        case TracePath::ray_queue: return issue_queued(L);
+#endif
+        default: return VXRT_OK;   // a tracer this build does not hold: vxrt_create refuses it
+    }
+}
+
+// step 7: the stream's tile order for its coming frames (plan_trace: sort), after the timed region
+static int resort_tiles(TraceLaunch& L) {
+    vxrt_ctx* c = L.c;
+    const TileSort sort = L.plan.sort;
+    hipStream_t ts = L.ts;
+    vxrt_ctx::TileSchedule& sched = c->schedules[L.lane];
+    if (!batches_frames(L.plan.tracer)) return VXRT_OK;   // the queue-based tracers take their tiles in raster order
+    if (sort == TileSort::xcd_affine) {
+        if (int rc = xcd_affine_order(c, sched, ts)) return rc;
+    } else if (sort == TileSort::longest_first) {
+        // (the priority split needs the walking tiles FIRST in the order: no spreading; and their number on the host)
+        HIP_TRY(launch_tile_order(sched.cost, sched.order, sched.last_cost, sched.scratch, trace_tile_count(c->band.width, c->band.local_rows),
+                                  L.g * unsigned(c->inflight), c->wave_slots, c->trace_priority ? 0 : c->spread_override, ts));
+        if (c->trace_priority) {
+            if (sched.heavy_pending) HIP_TRY(hipEventSynchronize(sched.heavy_ready));
+            HIP_TRY(hipMemcpyAsync(sched.host_heavy, sched.scratch + 128 * 64, sizeof(unsigned), hipMemcpyDeviceToHost, ts));
+            HIP_TRY(hipEventRecord(sched.heavy_ready, ts));
+            sched.heavy_pending = true;
+        }
+    }
+    if (sort != TileSort::none) { sched.valid = true; sched.age = 0; }
+    sched.age++;
+    return VXRT_OK;
+}
+
+// step 8: one event for the whole launch, the slots' and the context's books, and the three counters of what went out
+static int finish_launch(TraceLaunch& L, bool timed) {
+    vxrt_ctx* c = L.c;
+    const size_t lane = L.lane;
+    const uint32_t g = L.g;
     hipEvent_t done = c->launch_events[lane * 2 + (c->launch_event_turn[lane]++ & 1u)];
-    HIP_TRY(hipEventRecord(done, ts));   // one event for the whole launch
+    HIP_TRY(hipEventRecord(done, L.ts));
     for (uint32_t k = 0; k < g; k++) {
-        vxrt_ctx::Slot& sl = c->ring[size_t(slots[k])];
+        vxrt_ctx::Slot& sl = c->ring[size_t(L.slots[k])];
         sl.trace_done = done;
         sl.last_use = done;              // until a later stage reads the slot, the trace is its last use
         sl.last_use_recorded = true;
     }
-    c->slot = slots[g - 1];
+    c->slot = L.slots[g - 1];
     c->last_schedule = int(lane);
     c->trace_launches += 1;
     c->traced += g;
@@ -521,8 +596,40 @@ int trace_frames(vxrt_ctx* c, uint32_t g, bool timed, int* slots, Cam* cams, Cam
     if (timed) { c->timed_frames += g; c->timed_launches += 1; }
     c->accum_is_sampled = true;
     c->halo_valid = false;
+    if (L.plan.frame_lanes) c->frame_lane_launches++;
+    if (L.plan.share) c->shared_primary_launches++;
+    if (L.plan.split_heavy) c->split_launches++;
     return VXRT_OK;
 }
 
+// The trace stage of the next g frames (parameters at rest) as ONE launch of the tracer: g ring slots, frame numbers
+// frame_number+1 .. +g.  g > 1 only with the tracers that take several frames per launch (ctx.h: batches_frames).  slots[k] = ring slot
+// of frame k.  path: optional g camera poses (position, direction), one per frame; null = the camera stays where it is.  cams / olds
+// (g entries each): the camera and the "old" camera of every frame, as temporal.comp and denoise.comp of that frame see them.
+// The steps: cameras and slots, waits, feedback of earlier launches, the plan, the kernels' arguments, the planned path's launches
+// between the timed pair's events, the tile re-sort, the books.  A rank without rows launches nothing and plans nothing.
+int trace_frames(vxrt_ctx* c, uint32_t g, bool timed, int* slots, Cam* cams, Cam* olds, const float (*path_pos)[3], const float (*path_dir)[3],
+                 uint32_t gbuf_frames) {
+    const uint32_t first_frame_number = c->uniforms.frame_number + 1;
+    next_frames(c, g, slots, cams, olds, path_pos, path_dir);
+    const size_t lane = size_t(c->trace_launches % uint64_t(c->inflight));
+    hipStream_t ts = c->trace_streams[lane];
+    if (int rc = wait_for_slots(c, g, slots, ts)) return rc;
+    TraceLaunch L(c, ts, lane, g, slots);
+    if (c->band.local_rows > 0) {
+        if (int rc = absorb_feedback(c, lane)) return rc;
+        plan_trace(L.plan, c, g, cams, path_pos, path_dir, lane);
+        fill_trace_args(L, cams, gbuf_frames, first_frame_number);
+        EventPair p;
+        if (timed) { p = take_pair(c, 0); HIP_TRY(hipEventRecord(p.a, ts)); }
+        if (int rc = issue(L)) return rc;
+        // the launch is over when both grids of a priority split are (a no-op before the first split)
+        if (c->trace_priority && batches_frames(L.plan.tracer)) HIP_TRY(hipStreamWaitEvent(ts, c->low_join[lane], 0));
+        if (timed) HIP_TRY(hipEventRecord(p.b, ts));
+        if (int rc = resort_tiles(L)) return rc;
+        if (timed) c->pending.push_back(p);
+    }
+    return finish_launch(L, timed);
+}
 
 }  // namespace vxrt

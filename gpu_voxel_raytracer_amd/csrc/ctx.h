@@ -318,6 +318,25 @@ struct vxrt_ctx {
 };
 
 namespace vxrt {
+// ---- the plan of one trace launch: every decision about it, made once by plan_trace and carried out by trace_frames (api_trace.hip)
+constexpr size_t kInfinityCacheBytes = size_t(256) << 20;   // a scene larger than this waits for HBM: compared in ONE place, TracePlan::hbm
+// tracers (internal numbers) that take several frames per launch: the all-in-one kernel (0) and the head + tail pairs (4, 5)
+inline bool batches_frames(int tracer) { return tracer == 0 || tracer >= 4; }
+enum class TracePath { all_in_one, head_bounces, head_paths, fused, wavefront, ray_queue };   // trace_kernel | + bounce_kernel | + path_kernel | fused_kernel | tracers 2, 3
+enum class TileSort { none, longest_first, xcd_affine };
+struct TracePlan {
+    bool hbm;                  // the scene is beyond the Infinity Cache: trace_kernel's instantiation for it, the all-in-one schedule under tracer auto
+    bool wide_head, wide_tail; // the head / the tail walks the wide records
+    int tracer;                // the tracer that really runs: 0 where auto falls back to the all-in-one kernel, else vxrt_ctx::trace_variant
+    TracePath path;
+    int frame_lanes;           // frames a wave of the head holds, as the kernel really uses it (TraceArgs::frame_lanes): 8, 4 or 0
+    bool share;                // first_hit_kernel walks the primary rays once for all frames
+    unsigned long_blocks;      // blocks of the longest tiles that go out as a grid of their own (0: none); the head starts behind them
+    bool single_tail_launch;   // the tail is exactly one launch: the counter copy-back goes behind it
+    unsigned split_heavy;      // priority split: the first split_heavy tiles of the order on the trace stream, the rest on the low-priority one (0: one grid)
+    TileSort sort;             // how this launch re-sorts the stream's tiles when it is over
+};
+
 // a new scene: the touch maps were sized for the old one (vxrt_debug_touch_map)
 inline void drop_touch_maps(vxrt_ctx* c) {
     for (uint32_t** p : {&c->d_touch_nodes, &c->d_touch_leaves}) { if (*p) (void)hipFree(*p); *p = nullptr; }
