@@ -13,7 +13,7 @@ SOURCES = ["api_context.hip", "api_scene.hip", "api_trace.hip", "api_frame.hip",
 # -DVXRT_VARIANTS=1 (scripts/test_variants.sh): the schedules and the scene format that measured slower and are kept for comparison —
 # tracers 2 (wavefront), 3 (ray queues), 5 (per-lane path refill) and the wide records (two tree levels per 16-byte record)
 VARIANT_SOURCES = ["trace_wavefront.hip", "trace_paths.hip", "trace_pool.hip", "trace_dda.hip", "trace_fused.hip"]
-HEADERS = ["block_scan.h", "compact.h", "ctx.h", "device_build.h", "edit.h", "extract.h", "grid.h", "grid_edit.h", "halo_view.h", "kernels.h", "list_ops.h", "trace_common.h", "trace_block.h", "trace_tail_body.h", "ray_queue.h", "walk_wide.h", "scene_host.h", "vx_vec.h", "voxelize.h", "solid.h", "components.h", "pieces.h", "query.h", "transform.h", "transform_rule.h", "setops.h", "setops_rule.h", "morph.h", "morph_rule.h", "mesh.h", "mesh_rule.h", os.path.join("..", "..", "include", "vxrt.h"),
+HEADERS = ["block_scan.h", "compact.h", "ctx.h", "device_build.h", "edit.h", "extract.h", "grid.h", "grid_edit.h", "halo_view.h", "kernels.h", "list_ops.h", "owned.h", "trace_common.h", "trace_block.h", "trace_tail_body.h", "ray_queue.h", "walk_wide.h", "scene_host.h", "vx_vec.h", "voxelize.h", "solid.h", "components.h", "pieces.h", "query.h", "transform.h", "transform_rule.h", "setops.h", "setops_rule.h", "morph.h", "morph_rule.h", "mesh.h", "mesh_rule.h", os.path.join("..", "..", "include", "vxrt.h"),
            os.path.join("..", "..", "include", "vxrt_host.h"), os.path.join("..", "..", "include", "vxrt_debug.h"), os.path.join("..", "..", "include", "vxrt_edit.h"), os.path.join("..", "..", "include", "vxrt_extract.h"),
            os.path.join("..", "..", "include", "vxrt_device_scene.h"), os.path.join("..", "..", "include", "vxrt_grid.h"),
            os.path.join("..", "..", "include", "vxrt_grid_edit.h"), os.path.join("..", "..", "include", "vxrt_scene_depth.h"),

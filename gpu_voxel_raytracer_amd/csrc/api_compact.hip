@@ -22,18 +22,18 @@ int miscounted(uint64_t found, size_t live) {
 
 // The context's tree in new arrays (exactly sized; the caller's on VXRT_OK): *svo with c->live_nodes records, *leaves with
 // *leaf_count words.  The context is drained and is not changed; nothing is left allocated on failure.
-int relayout(vxrt_ctx* c, ScratchBuffer* svo, ScratchBuffer* leaves, size_t* leaf_count) {
+int relayout(vxrt_ctx* c, DeviceBuf<SvoRecord>* svo, DeviceBuf<int32_t>* leaves, size_t* leaf_count) {
     const size_t live = c->live_nodes;
     const uint32_t L = c->depth;
     if (live == 0 || live > c->svo_count) return miscounted(0, live);
-    if (int rc = alloc_scratch(svo, live * sizeof(SvoRecord), kWho, "the records")) return rc;
+    if (hipError_t e = svo->alloc(live); e != hipSuccess) return alloc_failed(e, kWho, "the records");
     if ((c->root_rec.masks & 0xffffu) == 0u) {
         // an empty scene: what upload_svo gives an empty list (flatten_svo: the root {0, 1}, and one zero leaf word)
         if (live != 1) return miscounted(1, live);
-        if (int rc = alloc_scratch(leaves, sizeof(int32_t), kWho, "the leaf words")) return rc;
+        if (hipError_t e = leaves->alloc(1); e != hipSuccess) return alloc_failed(e, kWho, "the leaf words");
         const SvoRecord root{0u, 1u};
-        HIP_TRY(hipMemcpyAsync(svo->p, &root, sizeof root, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemsetAsync(leaves->p, 0, sizeof(int32_t), c->stream));
+        HIP_TRY(hipMemcpyAsync(svo->get(), &root, sizeof root, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemsetAsync(leaves->get(), 0, sizeof(int32_t), c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
         *leaf_count = 1;
         return VXRT_OK;
@@ -45,7 +45,7 @@ int relayout(vxrt_ctx* c, ScratchBuffer* svo, ScratchBuffer* leaves, size_t* lea
     a.src_leaves = c->d_leaves;
     a.src_count = uint32_t(c->svo_count);
     a.src_leaf_count = uint32_t(c->leaf_count);
-    a.dst = svo->as<SvoRecord>();
+    a.dst = svo->get();
     a.dst_count = uint32_t(live);
     a.part = part.as<uint64_t>();
     HIP_TRY(hipMemsetAsync(a.dst, 0, sizeof(SvoRecord), c->stream));   // the root: {0, old record 0}
@@ -61,8 +61,8 @@ int relayout(vxrt_ctx* c, ScratchBuffer* svo, ScratchBuffer* leaves, size_t* lea
         if (a.leaf) {
             if (start + n != live) return miscounted(start + n, live);
             if (total == 0 || total > c->leaf_count) { set_error(std::string(kWho) + ": the leaf parents hold " + std::to_string(total) + " leaf words"); return VXRT_E_SCENE; }
-            if (int rc = alloc_scratch(leaves, size_t(total) * sizeof(int32_t), kWho, "the leaf words")) return rc;
-            a.dst_leaves = leaves->as<int32_t>();
+            if (hipError_t e = leaves->alloc(size_t(total)); e != hipSuccess) return alloc_failed(e, kWho, "the leaf words");
+            a.dst_leaves = leaves->get();
             a.dst_leaf_count = uint32_t(total);
             *leaf_count = size_t(total);
         } else if (total == 0 || start + n + total > live) {
@@ -88,25 +88,19 @@ int vxrt_compact_scene(vxrt_ctx* c) try {
     HIP_TRY(hipSetDevice(c->cfg.device));
     if (int rc = sync_all(c)) return rc;   // frames enqueued before the call read the old arrays
     if (!c->edited && c->svo_cap == 0 && c->leaf_cap == 0) return VXRT_OK;   // as built: breadth first, tight, exactly sized
-    ScratchBuffer svo, leaves;
+    DeviceBuf<SvoRecord> svo;
+    DeviceBuf<int32_t> leaves;
     size_t leaf_count = 0;
     if (int rc = relayout(c, &svo, &leaves, &leaf_count)) return rc;
     const SvoRecord root{c->root_rec.masks, (c->root_rec.masks & 0xffffu) == 0u || c->depth != 0 ? 1u : 0u};   // the new record 0
     bool box_valid = false;
     float box_min[3] = {0, 0, 0}, box_max[3] = {0, 0, 0};
-    if (int rc = device_scene_box(svo.as<SvoRecord>(), c->live_nodes, c->depth, root, c->root_center, c->root_size, &box_valid, box_min, box_max))
+    if (int rc = device_scene_box(svo, c->live_nodes, c->depth, root, c->root_center, c->root_size, &box_valid, box_min, box_max))
         return rc;
     // from here on the change happens: the new arrays replace the old, with a fresh scene's bookkeeping
-    (void)hipFree(c->d_svo);
-    (void)hipFree(c->d_leaves);
-    c->d_svo = svo.as<SvoRecord>();
-    c->d_leaves = leaves.as<int32_t>();
-    svo.p = leaves.p = nullptr;
-    c->svo_count = c->live_nodes;
-    c->leaf_count = leaf_count;
+    replace_scene_arrays(c, std::move(svo), c->live_nodes, std::move(leaves), leaf_count, {}, 0);
     c->root_rec = root;
     scene_replaced(c);
-    drop_touch_maps(c);
     c->box_valid = box_valid;
     for (int ax = 0; ax < 3; ax++) { c->box_min[ax] = box_min[ax]; c->box_max[ax] = box_max[ax]; }
     return VXRT_OK;

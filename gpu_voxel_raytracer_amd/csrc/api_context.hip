@@ -2,6 +2,7 @@
 // outputs and statistics.  Stands where Context::new / create_bindings / resize / update_bindings stand in the reference
 // (src/context.rs:595-660, 936-1016, 1430-1461, 2136-2162); each entry point cites its call site in vxrt.h.
 #include <chrono>
+#include <memory>
 
 #include "ctx.h"
 
@@ -25,42 +26,16 @@ int local_band_count(const BandMap& b) {
     return bands <= b.rank ? 0 : (bands - b.rank + b.nranks - 1) / b.nranks;
 }
 
+// everything alloc_images makes, and what was sized for the old frame (spp_sum, display: made again on their next use)
 void free_images(vxrt_ctx* c) {
-    for (vxrt_ctx::Slot& sl : c->ring) {
-        sl.sampled_color = sl.albedo = sl.nd = nullptr;   // pieces of ring_arena
-        if (sl.own) (void)hipEventDestroy(sl.own);
-    }
-    if (c->ring_arena) (void)hipFree(c->ring_arena);
-    c->ring_arena = nullptr;
     c->ring.clear();
+    c->ring_arena.reset();
     free_halo(c);
-    float4** imgs[] = {&c->accum[0], &c->accum[1], &c->denoised, &c->spp_sum};
-    for (float4** p : imgs) {
-        if (*p) (void)hipFree(*p);
-        *p = nullptr;
-    }
-    if (c->display) (void)hipFree(c->display);   // sized for the old frame: made again on its next use
-    c->display = nullptr;
-    for (vxrt_ctx::TileSchedule& t : c->schedules)
-    {
-        for (uint32_t** p : {&t.cost, &t.order, &t.last_cost, &t.scratch}) { if (*p) (void)hipFree(*p); *p = nullptr; }
-        if (t.host_heavy) (void)hipHostFree(t.host_heavy);
-        if (t.heavy_ready) (void)hipEventDestroy(t.heavy_ready);
-        t.host_heavy = nullptr; t.heavy_ready = nullptr;
-    }
+    for (DeviceBuf<float4>* p : {&c->accum[0], &c->accum[1], &c->denoised, &c->spp_sum}) p->reset();
+    c->display.reset();
     c->schedules.clear();
-    for (vxrt_ctx::StreamQueues& sq : c->queues) {
-        for (float4** p : {&sq.hitq[0], &sq.hitq[1]}) { if (*p) (void)hipFree(*p); *p = nullptr; }
-        if (sq.counts3) (void)hipFree(sq.counts3);
-        if (sq.rq_block) (void)hipFree(sq.rq_block);
-        if (sq.host_counts) (void)hipHostFree(sq.host_counts);
-        if (sq.host_ctl) (void)hipHostFree(sq.host_ctl);
-        if (sq.fused_ctl) (void)hipFree(sq.fused_ctl);
-        if (sq.counts_ready) (void)hipEventDestroy(sq.counts_ready);
-    }
     c->queues.clear();
     c->queue_bytes = 0;
-    for (uint4* p : c->first_hits) { if (p) (void)hipFree(p); }
     c->first_hits.clear();
 }
 
@@ -76,21 +51,18 @@ int alloc_images(vxrt_ctx* c) {
     // ONE allocation for the whole ring (each image on a 2 MiB boundary): a hundred separate 33 MB allocations land wherever the
     // driver finds room, and the trace stage's rate then differs by up to 4 % from process to process (101.3 .. 105.6 ms per 960
     // bench frames, each process steady to 0.1 %)
-    c->ring.resize(size_t(c->inflight) * size_t(c->batch) + 2);
+    c->ring.resize(size_t(c->inflight) * size_t(c->batch) + 2);   // fresh slots, queues and schedules (free_images cleared them): their flags and counters start at the defaults
     const size_t pitch = (bytes + (size_t(2) << 20) - 1) & ~((size_t(2) << 20) - 1);
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->ring_arena), pitch * 3 * c->ring.size()));
+    HIP_TRY(c->ring_arena.alloc(pitch * 3 * c->ring.size()));
     HIP_TRY(hipMemsetAsync(c->ring_arena, 0, pitch * 3 * c->ring.size(), c->stream));
     size_t piece = 0;
     for (vxrt_ctx::Slot& sl : c->ring) {
         for (float4** p : {&sl.sampled_color, &sl.albedo, &sl.nd}) *p = reinterpret_cast<float4*>(c->ring_arena + pitch * piece++);
-        HIP_TRY(hipEventCreateWithFlags(&sl.own, hipEventDisableTiming));
-        sl.trace_done = sl.last_use = nullptr;
-        sl.last_use_recorded = false;
+        HIP_TRY(sl.own.create(hipEventDisableTiming));
     }
-    float4** imgs[] = {&c->accum[0], &c->accum[1], &c->denoised};
-    for (float4** p : imgs) {
-        HIP_TRY(hipMalloc(reinterpret_cast<void**>(p), bytes));
-        HIP_TRY(hipMemsetAsync(*p, 0, bytes, c->stream));
+    for (DeviceBuf<float4>* p : {&c->accum[0], &c->accum[1], &c->denoised}) {
+        HIP_TRY(p->alloc(bytes / sizeof(float4)));
+        HIP_TRY(hipMemsetAsync(p->get(), 0, bytes, c->stream));
     }
     // path queues: every 8x8-pixel wave of the primary launch appends to shard (wave index % 64)
     // Worst case: all 64 lanes of each of a shard's waves append (a launch's waves are dealt to the 64 shards round robin).
@@ -114,16 +86,14 @@ int alloc_images(vxrt_ctx* c) {
             // the second queue: the wavefront tracer's ping-pong partner; for the compacted tail only when it compacts again
             const int nq = c->trace_variant == 3 ? 1 : ((c->trace_variant >= 4 && c->tail_split == 0u) ? 1 : 2);
             for (int i = 0; i < nq; i++) {
-                HIP_TRY(hipMalloc(reinterpret_cast<void**>(&sq.hitq[i]), hit_bytes));
+                HIP_TRY(sq.hitq[i].alloc(hit_bytes / sizeof(float4)));
                 c->queue_bytes += hit_bytes;
             }
-            HIP_TRY(hipMalloc(reinterpret_cast<void**>(&sq.counts3), 3 * 64 * 64));
+            HIP_TRY(sq.counts3.alloc(3 * 64 * 64 / sizeof(unsigned)));
             HIP_TRY(hipMemsetAsync(sq.counts3, 0, 3 * 64 * 64, c->stream));
-            HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&sq.host_counts), 64 * 64, hipHostMallocDefault));
+            HIP_TRY(sq.host_counts.alloc(64 * 64 / sizeof(unsigned)));
             memset(sq.host_counts, 0, 64 * 64);
-            HIP_TRY(hipEventCreateWithFlags(&sq.counts_ready, hipEventDisableTiming));
-            sq.counts_pending = false;
-            sq.launches = 0;
+            HIP_TRY(sq.counts_ready.create(hipEventDisableTiming));
             if (c->trace_variant == 3) {
                 // Dense queues in kSegments segments.  A shade launch of G blocks (G a multiple of 8) hands every segment
                 // G/8 blocks x 256 items per trip, so a segment receives at most its eighth of the paths rounded up to
@@ -131,8 +101,8 @@ int alloc_images(vxrt_ctx* c) {
                 const size_t cap = waves * 64 / kSegments + size_t(c->shade_blocks) * 32 + 1024;
                 const size_t per_path = 2 * 64 + 2 * 64 + 2 * 32;  // state x2, rays x2, results x2
                 const size_t counts_bytes = size_t(c->cfg.max_bounces + 1) * (kSegments + 1) * 64;   // + the ray pool's cursor per stage
-                HIP_TRY(hipMalloc(&sq.rq_block, kSegments * cap * per_path + counts_bytes + 256));
-                char* p = static_cast<char*>(sq.rq_block);
+                HIP_TRY(sq.rq_block.alloc(kSegments * cap * per_path + counts_bytes + 256));
+                char* p = sq.rq_block;
                 sq.rq.state[0] = reinterpret_cast<float4*>(p); p += kSegments * cap * 64;
                 sq.rq.state[1] = reinterpret_cast<float4*>(p); p += kSegments * cap * 64;
                 sq.rq.rays[0] = reinterpret_cast<float4*>(p); p += kSegments * cap * 64;
@@ -147,24 +117,21 @@ int alloc_images(vxrt_ctx* c) {
     // shared primary rays (VXRT_OPT_SHARED_PRIMARY): a stream's first-hit records, 16 bytes per pixel of the band; never read before
     // first_hit_kernel has written them in the same launch, so they start uninitialised
     if (c->batch >= 2 && c->band.local_rows > 0) {
-        c->first_hits.resize(size_t(c->inflight), nullptr);
-        for (uint4*& p : c->first_hits)
-            HIP_TRY(hipMalloc(reinterpret_cast<void**>(&p), size_t(c->band.local_rows) * size_t(c->band.width) * sizeof(uint4)));
+        c->first_hits.resize(size_t(c->inflight));
+        for (DeviceBuf<uint4>& p : c->first_hits) HIP_TRY(p.alloc(size_t(c->band.local_rows) * size_t(c->band.width)));
     }
     const size_t tiles = trace_tile_count(c->band.width, c->band.local_rows);
     c->schedules.resize(size_t(c->inflight));
     for (vxrt_ctx::TileSchedule& t : c->schedules) {
-        for (uint32_t** p : {&t.cost, &t.order, &t.last_cost}) {
-            HIP_TRY(hipMalloc(reinterpret_cast<void**>(p), (tiles + 1) * sizeof(uint32_t)));
-            HIP_TRY(hipMemsetAsync(*p, 0, (tiles + 1) * sizeof(uint32_t), c->stream));
+        for (DeviceBuf<uint32_t>* p : {&t.cost, &t.order, &t.last_cost}) {
+            HIP_TRY(p->alloc(tiles + 1));
+            HIP_TRY(hipMemsetAsync(p->get(), 0, (tiles + 1) * sizeof(uint32_t), c->stream));
         }
-        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&t.scratch), 256 * 128 * sizeof(uint32_t)));
-        t.valid = false;
-        t.heavy = 0; t.heavy_pending = false;
+        HIP_TRY(t.scratch.alloc(256 * 128));
         if (c->trace_priority) {
-            HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&t.host_heavy), 64, hipHostMallocDefault));
+            HIP_TRY(t.host_heavy.alloc(64 / sizeof(unsigned)));
             t.host_heavy[0] = 0u;
-            HIP_TRY(hipEventCreateWithFlags(&t.heavy_ready, hipEventDisableTiming));
+            HIP_TRY(t.heavy_ready.create(hipEventDisableTiming));
         }
     }
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -249,8 +216,12 @@ EventPair take_pair(vxrt_ctx* c, int stage) {
         p = c->free_pairs.back();
         c->free_pairs.pop_back();
     } else {
-        (void)hipEventCreate(&p.a);
-        (void)hipEventCreate(&p.b);
+        for (hipEvent_t* e : {&p.a, &p.b}) {   // owned by the context (pair_events); a failed create leaves a null handle
+            Event made;
+            (void)made.create(hipEventDefault);
+            *e = made;
+            c->pair_events.push_back(std::move(made));
+        }
     }
     p.stage = stage;
     return p;
@@ -284,7 +255,7 @@ static int encode_display(vxrt_ctx* c, vxrt_image which, uint32_t* dst) {
 static int encode_display_buffer(vxrt_ctx* c, vxrt_image which) {
     if (c->display == nullptr) {
         const size_t bytes = display_bytes(c);
-        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->display), bytes ? bytes : 16u));
+        HIP_TRY(c->display.alloc(bytes ? bytes / 4u : 4u));
     }
     return encode_display(c, which, c->display);
 }
@@ -499,25 +470,25 @@ int vxrt_create_tuned(const vxrt_config* cfg, const vxrt_tuning* tuning, size_t 
     if (cfg->device < 0 || cfg->device >= ndev) { set_error("device ordinal out of range"); return VXRT_E_INVALID; }
     HIP_TRY(hipSetDevice(cfg->device));
 
-    vxrt_ctx* c = new vxrt_ctx();
+    // owned here until it is handed out: every early return below releases what the context holds so far
+    std::unique_ptr<vxrt_ctx> owner(new vxrt_ctx());
+    vxrt_ctx* c = owner.get();
     c->cfg = *cfg;
     c->cfg.noise = nullptr;  // borrowed for this call only
     vxrt_default_uniforms(&c->uniforms);
     vxrt_default_temporal(&c->temporal);
     vxrt_default_denoise(&c->denoise);
-    int rc = VXRT_OK;
-    auto fail = [&](int code) { vxrt_destroy(c); return code; };
     {
         int cus = 0;
         if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, cfg->device) == hipSuccess && cus > 0) c->wave_slots = unsigned(cus) * 4u * 5u;
     }
-    if (hipEventCreateWithFlags(&c->halo_event, hipEventDisableTiming) != hipSuccess) return fail(hip_fail(hipGetLastError(), "hipEventCreate"));
+    HIP_TRY(c->halo_event.create(hipEventDisableTiming));
     c->inflight = cfg->frames_in_flight == 0 ? 1 : int(cfg->frames_in_flight);
     // vxrt_config.tracer: 0 auto, 1 monolithic, 2 wavefront, 3 ray queues, 4 monolithic head + compacted tail (internally
     // 0, 2, 3, 4).  Measured on MI355X with frames in flight (menger 1080p 4 bounces / monu10 4K 8 bounces, ms per frame):
     // tracer 1: 0.219 / 0.52-1.53, tracer 3: 0.275 / 0.82-1.10, tracer 4: 0.175 / 0.54-0.94 -> auto = 4 whenever a path
     // can have a second hit, with further compactions from 6 bounces on (below).
-    if (cfg->tracer > 5) { set_error("tracer must be 0..5"); return fail(VXRT_E_INVALID); }
+    if (cfg->tracer > 5) { set_error("tracer must be 0..5"); return VXRT_E_INVALID; }
     c->trace_variant = cfg->tracer == 0 ? 4 : (cfg->tracer == 1 ? 0 : int(cfg->tracer));
     c->auto_tracer = cfg->tracer == 0;
     // From 6 bounces on the tail compacts its live paths again, in launches of their own, at path segments 2, 3 and 5 (round 4; one
@@ -528,98 +499,72 @@ int vxrt_create_tuned(const vxrt_config* cfg, const vxrt_tuning* tuning, size_t 
 #if !VXRT_VARIANTS
     if (c->trace_variant == 2 || c->trace_variant == 3 || c->trace_variant == 5) {
         set_error("tracers 2, 3 and 5 are not in this build of libvxrt (compile with -DVXRT_VARIANTS=1: scripts/test_variants.sh)");
-        return fail(VXRT_E_INVALID);
+        return VXRT_E_INVALID;
     }
 #endif
     if (c->trace_variant >= 4 && cfg->max_bounces < 2) c->trace_variant = 0;  // no tail to compact
     // The library reads NO environment variable: what an experiment or a test wants different from the defaults arrives here, as
     // (option, value) pairs (vxrt_create_tuned), or later through vxrt_set_option.
     for (size_t i = 0; i < ntuning; i++)
-        if ((rc = apply_option(c, tuning[i].option, tuning[i].value, true)) != VXRT_OK) return fail(rc);
+        if (int rc = apply_option(c, tuning[i].option, tuning[i].value, true)) return rc;
     if (c->tail_from < 0 || c->tail_from >= int(cfg->max_bounces)) c->tail_from = 1;
     c->shade_blocks = (c->shade_blocks < 8 ? 8 : (c->shade_blocks > 2048 ? 2048 : c->shade_blocks) + 7) / 8 * 8;
-    if (c->inflight < 1 || c->inflight > 16) { set_error("frames_in_flight must be 1..16"); return fail(VXRT_E_INVALID); }
+    if (c->inflight < 1 || c->inflight > 16) { set_error("frames_in_flight must be 1..16"); return VXRT_E_INVALID; }
     c->batch = cfg->frames_per_launch == 0 ? 1 : int(cfg->frames_per_launch);
-    if (c->batch < 1 || c->batch > kMaxBatch) { set_error("frames_per_launch must be 1..32"); return fail(VXRT_E_INVALID); }
+    if (c->batch < 1 || c->batch > kMaxBatch) { set_error("frames_per_launch must be 1..32"); return VXRT_E_INVALID; }
     // VXRT_OPT_TRACE_PRIORITY: the streams that carry trace launches at the device's highest priority (numerically lowest), one
     // low-priority stream per trace stream for the grid of tiles that only store sky (trace_frames)
     int prio_least = 0, prio_greatest = 0;
     if (c->trace_priority) (void)hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest);
-    auto make_stream = [&](hipStream_t* st, bool trace) {
-        return (c->trace_priority && trace) ? hipStreamCreateWithPriority(st, hipStreamNonBlocking, prio_greatest) : hipStreamCreateWithFlags(st, hipStreamNonBlocking);
+    auto make_stream = [&](Stream& st, bool trace) {
+        return (c->trace_priority && trace) ? st.create(hipStreamNonBlocking, prio_greatest) : st.create(hipStreamNonBlocking);
     };
-    if (make_stream(&c->stream, c->inflight == 1) != hipSuccess) return fail(hip_fail(hipGetLastError(), "hipStreamCreate"));
-    c->trace_streams.assign(size_t(c->inflight), nullptr);
+    HIP_TRY(make_stream(c->stream, c->inflight == 1));
     if (c->inflight == 1) {
-        c->trace_streams[0] = c->stream;
+        c->trace_streams.assign(1, c->stream);
     } else {
-        for (hipStream_t& t : c->trace_streams)
-            if (make_stream(&t, true) != hipSuccess) return fail(hip_fail(hipGetLastError(), "hipStreamCreate"));
-    }
-    if (c->trace_priority) {
-        c->low_streams.assign(size_t(c->inflight), nullptr);
-        c->low_fork.assign(size_t(c->inflight), nullptr);
-        c->low_join.assign(size_t(c->inflight), nullptr);
-        for (size_t i = 0; i < size_t(c->inflight); i++) {
-            if (hipStreamCreateWithPriority(&c->low_streams[i], hipStreamNonBlocking, prio_least) != hipSuccess) return fail(hip_fail(hipGetLastError(), "hipStreamCreateWithPriority"));
-            if (hipEventCreateWithFlags(&c->low_fork[i], hipEventDisableTiming) != hipSuccess) return fail(hip_fail(hipGetLastError(), "hipEventCreate"));
-            if (hipEventCreateWithFlags(&c->low_join[i], hipEventDisableTiming) != hipSuccess) return fail(hip_fail(hipGetLastError(), "hipEventCreate"));
+        c->own_trace_streams.resize(size_t(c->inflight));
+        for (Stream& t : c->own_trace_streams) {
+            HIP_TRY(make_stream(t, true));
+            c->trace_streams.push_back(t);
         }
     }
-    c->launch_events.assign(size_t(c->inflight) * 2, nullptr);
-    c->launch_event_turn.assign(size_t(c->inflight), 0u);
-    c->head_events.assign(size_t(c->inflight), nullptr);
-    for (hipEvent_t& e : c->head_events)
-        if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) return fail(hip_fail(hipGetLastError(), "hipEventCreate"));
-    for (hipEvent_t& e : c->launch_events)
-        if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) return fail(hip_fail(hipGetLastError(), "hipEventCreate"));
-    set_band(c, cfg->width, cfg->height);
-    if ((rc = alloc_images(c)) != VXRT_OK) return fail(rc);
-    if (hipMalloc(reinterpret_cast<void**>(&c->d_noise), kNoiseCount * sizeof(float)) != hipSuccess) return fail(hip_fail(hipGetLastError(), "hipMalloc noise"));
-    if (cfg->noise) {
-        if (hipMemcpy(c->d_noise, cfg->noise, kNoiseCount * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) return fail(hip_fail(hipGetLastError(), "noise upload"));
-    } else {
-        if (launch_noise_fill(c->d_noise, cfg->noise_seed, kNoiseCount, c->stream) != hipSuccess) return fail(hip_fail(hipGetLastError(), "noise fill"));
+    if (c->trace_priority) {
+        c->low_streams.resize(size_t(c->inflight));
+        c->low_fork.resize(size_t(c->inflight));
+        c->low_join.resize(size_t(c->inflight));
+        for (size_t i = 0; i < size_t(c->inflight); i++) {
+            HIP_TRY(c->low_streams[i].create(hipStreamNonBlocking, prio_least));
+            HIP_TRY(c->low_fork[i].create(hipEventDisableTiming));
+            HIP_TRY(c->low_join[i].create(hipEventDisableTiming));
+        }
     }
-    if (hipMalloc(reinterpret_cast<void**>(&c->d_rays), kRaySlots * 64) != hipSuccess) return fail(hip_fail(hipGetLastError(), "hipMalloc counter"));
-    if (hipMemsetAsync(c->d_rays, 0, kRaySlots * 64, c->stream) != hipSuccess) return fail(hip_fail(hipGetLastError(), "memset counter"));
-    if (hipStreamSynchronize(c->stream) != hipSuccess) return fail(hip_fail(hipGetLastError(), "sync"));
-    *out = c;
+    c->launch_events.resize(size_t(c->inflight) * 2);
+    c->launch_event_turn.assign(size_t(c->inflight), 0u);
+    c->head_events.resize(size_t(c->inflight));
+    for (Event& e : c->head_events) HIP_TRY(e.create(hipEventDisableTiming));
+    for (Event& e : c->launch_events) HIP_TRY(e.create(hipEventDisableTiming));
+    set_band(c, cfg->width, cfg->height);
+    if (int rc = alloc_images(c)) return rc;
+    HIP_TRY(c->d_noise.alloc(kNoiseCount));
+    if (cfg->noise) HIP_TRY(hipMemcpy(c->d_noise, cfg->noise, kNoiseCount * sizeof(float), hipMemcpyHostToDevice));
+    else HIP_TRY(launch_noise_fill(c->d_noise, cfg->noise_seed, kNoiseCount, c->stream));
+    HIP_TRY(c->d_rays.alloc(kRaySlots * 64 / sizeof(unsigned long long)));
+    HIP_TRY(hipMemsetAsync(c->d_rays, 0, kRaySlots * 64, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    *out = owner.release();
     return VXRT_OK;
 } VXRT_CATCH
 
+// The streams are drained while everything they may still use is alive; then the context's members release what they own, the streams
+// last (ctx.h: the order of declaration).
 int vxrt_destroy(vxrt_ctx* c) try {
     if (!c) return VXRT_OK;
     (void)hipSetDevice(c->cfg.device);
     for (hipStream_t t : c->trace_streams) if (t) (void)hipStreamSynchronize(t);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    for (auto* v : {&c->pending, &c->free_pairs})
-        for (EventPair& p : *v) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
-    free_images(c);
-    if (c->d_svo) (void)hipFree(c->d_svo);
-    if (c->d_wide) (void)hipFree(c->d_wide);
-    if (c->d_leaves) (void)hipFree(c->d_leaves);
-    if (c->d_noise) (void)hipFree(c->d_noise);
-    if (c->d_rays) (void)hipFree(c->d_rays);
-    for (hipStream_t t : c->trace_streams) if (t && t != c->stream) (void)hipStreamDestroy(t);
-    if (c->halo_event) (void)hipEventDestroy(c->halo_event);
-    for (hipEvent_t e : c->launch_events) if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : c->head_events) if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : c->aux_fork) if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : c->aux_join) if (e) (void)hipEventDestroy(e);
-    for (hipStream_t t : c->aux_streams) if (t) (void)hipStreamDestroy(t);
-    for (hipStream_t t : c->low_streams) if (t) { (void)hipStreamSynchronize(t); (void)hipStreamDestroy(t); }
-    for (hipEvent_t e : c->low_fork) if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : c->low_join) if (e) (void)hipEventDestroy(e);
-    if (c->copy_stream) { (void)hipStreamSynchronize(c->copy_stream); (void)hipStreamDestroy(c->copy_stream); }
-    for (vxrt_ctx::ReadSlot& rs : c->read_slots) {
-        if (rs.stage) (void)hipFree(rs.stage);
-        if (rs.snap) (void)hipEventDestroy(rs.snap);
-        if (rs.arrived) (void)hipEventDestroy(rs.arrived);
-    }
-    drop_touch_maps(c);
-    free_extract(c);
-    if (c->stream) (void)hipStreamDestroy(c->stream);
+    for (hipStream_t t : c->low_streams) if (t) (void)hipStreamSynchronize(t);
+    if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);
     delete c;
     return VXRT_OK;
 } VXRT_CATCH
@@ -729,17 +674,17 @@ int vxrt_read_async(vxrt_ctx* c, vxrt_image which, float* dst, size_t bytes, uin
     if (!display && bytes != image_bytes(c)) { set_error("vxrt_read_async: bytes must equal local_rows*width*16"); return VXRT_E_INVALID; }
     HIP_TRY(hipSetDevice(c->cfg.device));
     vxrt_ctx::ReadSlot& rs = c->read_slots[slot];
-    if (c->copy_stream == nullptr) HIP_TRY(hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
-    if (rs.snap == nullptr) {
-        HIP_TRY(hipEventCreateWithFlags(&rs.snap, hipEventDisableTiming));
-        HIP_TRY(hipEventCreateWithFlags(&rs.arrived, hipEventDisableTiming));
+    if (c->copy_stream == nullptr) HIP_TRY(c->copy_stream.create(hipStreamNonBlocking));
+    if (rs.arrived == nullptr) {
+        HIP_TRY(rs.snap.create(hipEventDisableTiming));
+        HIP_TRY(rs.arrived.create(hipEventDisableTiming));
     }
     if (rs.stage_bytes < bytes) {    // first use, or after vxrt_resize: a new stage (the old one's transfer must have arrived)
         if (rs.in_flight) HIP_TRY(hipEventSynchronize(rs.arrived));
         rs.in_flight = false;
-        if (rs.stage) (void)hipFree(rs.stage);
-        rs.stage = nullptr; rs.stage_bytes = 0;
-        if (bytes) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&rs.stage), bytes));
+        rs.stage.reset();
+        rs.stage_bytes = 0;
+        if (bytes) HIP_TRY(rs.stage.alloc(bytes));
         rs.stage_bytes = bytes;
     }
     if (bytes == 0) { rs.in_flight = false; return VXRT_OK; }
@@ -749,7 +694,7 @@ int vxrt_read_async(vxrt_ctx* c, vxrt_image which, float* dst, size_t bytes, uin
     vxrt_ctx::Slot& cur = c->ring[size_t(c->slot)];
     if (trace_image && cur.trace_done != nullptr) HIP_TRY(hipStreamWaitEvent(c->stream, cur.trace_done, 0));
     if (display) {   // the encode IS the snapshot: it writes the 4-byte pixels straight into the stage
-        if (int rc = encode_display(c, which, reinterpret_cast<uint32_t*>(rs.stage))) return rc;
+        if (int rc = encode_display(c, which, reinterpret_cast<uint32_t*>(rs.stage.get()))) return rc;
     } else {
         HIP_TRY(hipMemcpyAsync(rs.stage, src, bytes, hipMemcpyDeviceToDevice, c->stream));
     }
@@ -777,6 +722,7 @@ int vxrt_read_wait(vxrt_ctx* c, uint32_t slot) try {
     return VXRT_OK;
 } VXRT_CATCH
 
+// Pinned memory for the caller, who owns it until vxrt_host_free: the one pair of raw hipHostMalloc / hipHostFree outside owned.h
 int vxrt_host_alloc(size_t bytes, void** out) try {
     if (!out) { set_error("null argument"); return VXRT_E_INVALID; }
     *out = nullptr;

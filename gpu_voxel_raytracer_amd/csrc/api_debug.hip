@@ -188,7 +188,6 @@ int vxrt_debug_shared_primary_launches(vxrt_ctx* c, uint64_t* count) try {
     return VXRT_OK;
 } VXRT_CATCH
 
-#if VXRT_VARIANTS
 // PROTOTYPE (csrc/trace_dda.hip; -DVXRT_VARIANTS=1 builds only): the same rays through the exact walk (cast_probe_kernel over the
 // context's scene format) and through the three-level DDA over a bit grid that is built on the device from the scene in place (first
 // call; kept until the scene changes), both timed with HIP events (the second of two launches each).  flags: bit 0 = the certificate,
@@ -199,6 +198,10 @@ int vxrt_debug_shared_primary_launches(vxrt_ctx* c, uint64_t* count) try {
 int vxrt_debug_dda_rays(vxrt_ctx* c, const float* origins, const float* dirs, size_t n, uint32_t flags, float margin_scale, uint32_t max_steps,
                         float* out_walk, float* out_dda, double ms[4]) try {
     if (!valid_ctx(c) || !origins || !dirs || !out_dda || !ms || (!out_walk && !(flags & 4u))) { set_error("null argument"); return VXRT_E_INVALID; }
+#if !VXRT_VARIANTS
+    set_error("the DDA prototype is not in this build of libvxrt (compile with -DVXRT_VARIANTS=1)");
+    return VXRT_E_INVALID;
+#else
     if (!c->has_scene) { set_error("no scene set"); return VXRT_E_NOSCENE; }
     const int levels = int(c->depth) + 1;
     if (levels < 3 || levels > 12) { set_error("the DDA grid wants a tree of depth 2..11 (4 .. 4096 cells per axis)"); return VXRT_E_INVALID; }
@@ -214,18 +217,18 @@ int vxrt_debug_dda_rays(vxrt_ctx* c, const float* origins, const float* dirs, si
     memcpy(a.root_center, c->root_center, sizeof a.root_center);
     a.root_size = c->root_size;
     a.stack_levels = c->depth < 1 ? 1 : int(c->depth);
-    hipEvent_t e0, e1;
-    HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1));
+    Event e0, e1;
+    HIP_TRY(e0.create(hipEventDefault)); HIP_TRY(e1.create(hipEventDefault));
     float t = 0.0f;
     ms[0] = ms[1] = ms[2] = ms[3] = 0.0;
     size_t sz[4] = {0, 0, 0, 0};
     dda_grid_sizes(levels, &sz[0], &sz[1], &sz[2], &sz[3]);
     const bool dda = !(flags & 8u);
     if (dda && (c->dda_grid[0] == nullptr || c->dda_levels != levels)) {
-        drop_touch_maps(c);
+        drop_dda_grid(c);   // the touch maps are the caller's: they stay
         for (int k = 0; k < 4; k++) {
             if (sz[k] == 0) continue;
-            HIP_TRY(hipMalloc(&c->dda_grid[k], sz[k]));
+            HIP_TRY(c->dda_grid[k].alloc(sz[k]));
             HIP_TRY(hipMemsetAsync(c->dda_grid[k], 0, sz[k], c->stream));
         }
         HIP_TRY(hipEventRecord(e0, c->stream));
@@ -259,12 +262,11 @@ int vxrt_debug_dda_rays(vxrt_ctx* c, const float* origins, const float* dirs, si
         HIP_TRY(hipEventElapsedTime(&t, e0, e1));
         ms[1] = double(t);
     }
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
     if (!(flags & 4u)) HIP_TRY(hipMemcpy(out_walk, b_w.as<float>(), n * 32, hipMemcpyDeviceToHost));
     if (dda) HIP_TRY(hipMemcpy(out_dda, b_x.as<float>(), n * 32, hipMemcpyDeviceToHost));
     return VXRT_OK;
-} VXRT_CATCH
 #endif
+} VXRT_CATCH
 
 }  // extern "C"
 // ---- touch map (vxrt_debug.h): which 64-byte lines of the scene does a frame read? ---------------------------------------------
@@ -292,7 +294,8 @@ int vxrt_debug_touch_map(vxrt_ctx* c, uint32_t enable) try {
 #else
     HIP_TRY(hipSetDevice(c->cfg.device));
     if (int rc = vxrt_sync(c)) return rc;
-    for (uint32_t** p : {&c->d_touch_nodes, &c->d_touch_leaves}) { if (*p) (void)hipFree(*p); *p = nullptr; }
+    c->d_touch_nodes.reset();
+    c->d_touch_leaves.reset();
     c->touch_node_lines = c->touch_leaf_lines = 0;
     if (!enable) return VXRT_OK;
     if (!c->has_scene) { set_error("no scene set"); return VXRT_E_NOSCENE; }
@@ -300,8 +303,8 @@ int vxrt_debug_touch_map(vxrt_ctx* c, uint32_t enable) try {
     c->touch_node_lines = (node_bytes + 63) / 64;
     c->touch_leaf_lines = (c->leaf_count * sizeof(int32_t) + 63) / 64;
     const size_t wn = (c->touch_node_lines + 31) / 32 + 1, wl = (c->touch_leaf_lines + 31) / 32 + 1;
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->d_touch_nodes), wn * 4));
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->d_touch_leaves), wl * 4));
+    HIP_TRY(c->d_touch_nodes.alloc(wn));
+    HIP_TRY(c->d_touch_leaves.alloc(wl));
     HIP_TRY(hipMemsetAsync(c->d_touch_nodes, 0, wn * 4, c->stream));
     HIP_TRY(hipMemsetAsync(c->d_touch_leaves, 0, wl * 4, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -316,7 +319,7 @@ int vxrt_debug_touch_count(vxrt_ctx* c, uint64_t out[6], uint32_t reset) try {
     if (int rc = vxrt_sync(c)) return rc;
     ScratchBuffer b;
     HIP_TRY(b.alloc(4 * sizeof(unsigned long long)));
-    HIP_TRY(hipMemsetAsync(b.p, 0, 4 * sizeof(unsigned long long), c->stream));
+    HIP_TRY(hipMemsetAsync(b.get(), 0, 4 * sizeof(unsigned long long), c->stream));
     const size_t wn = (c->touch_node_lines + 31) / 32 + 1, wl = (c->touch_leaf_lines + 31) / 32 + 1;
     hipLaunchKernelGGL(touch_count_kernel, dim3(1024), dim3(256), 0, c->stream, c->d_touch_nodes, wn, b.as<unsigned long long>());
     hipLaunchKernelGGL(touch_count_kernel, dim3(1024), dim3(256), 0, c->stream, c->d_touch_leaves, wl, b.as<unsigned long long>() + 2);
@@ -327,7 +330,7 @@ int vxrt_debug_touch_count(vxrt_ctx* c, uint64_t out[6], uint32_t reset) try {
     }
     HIP_TRY(hipStreamSynchronize(c->stream));
     unsigned long long h[4] = {0, 0, 0, 0};
-    HIP_TRY(hipMemcpy(h, b.p, sizeof h, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(h, b.get(), sizeof h, hipMemcpyDeviceToHost));
     out[0] = h[0]; out[1] = h[2]; out[2] = h[1]; out[3] = h[3];
     out[4] = c->touch_node_lines; out[5] = c->touch_leaf_lines;
     return VXRT_OK;
@@ -361,10 +364,10 @@ int vxrt_debug_display_encode(int32_t device, const float* rgba, size_t n_pixels
     ScratchBuffer bin, bout;
     HIP_TRY(bin.alloc(n_pixels * 16));
     HIP_TRY(bout.alloc(n_pixels * 4));
-    HIP_TRY(hipMemcpy(bin.p, rgba, n_pixels * 16, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(bin.get(), rgba, n_pixels * 16, hipMemcpyHostToDevice));
     HIP_TRY(launch_display_encode(bin.as<float4>(), bout.as<uint32_t>(), n_pixels, format == VXRT_DISPLAY_BGRA8_SRGB, nullptr));
     HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(out, bout.p, n_pixels * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out, bout.get(), n_pixels * 4, hipMemcpyDeviceToHost));
     return VXRT_OK;
 } VXRT_CATCH
 

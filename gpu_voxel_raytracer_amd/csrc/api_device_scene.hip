@@ -8,9 +8,11 @@
 namespace vxrt {
 
 int install_device_tree(vxrt_ctx* c, const DeviceTree& t, const char* who) {
-    ScratchBuffer svo, leaves, wide;   // owned here until installed
-    svo.p = t.svo;
-    leaves.p = t.leaves;
+    DeviceBuf<SvoRecord> svo;   // owned here until installed
+    DeviceBuf<int32_t> leaves;
+    DeviceBuf<WideRec> wide;
+    svo.adopt(t.svo);
+    leaves.adopt(t.leaves);
     size_t nwide = 0;
     WideRec wide_root{0, 0, 0, 0};
     if (c->scene_format == 1) {   // the wide records (variants only): from the built records on the host, as upload_svo makes them
@@ -18,14 +20,12 @@ int install_device_tree(vxrt_ctx* c, const DeviceTree& t, const char* who) {
         HIP_TRY(hipMemcpy(recs.data(), t.svo, t.svo_count * sizeof(SvoRecord), hipMemcpyDeviceToHost));
         std::vector<WideRec> w;
         if (int rc = widen_svo(recs, t.depth, &w)) return rc;
-        if (int rc = alloc_scratch(&wide, w.size() * sizeof(WideRec), who, "the wide records")) return rc;
-        HIP_TRY(hipMemcpy(wide.p, w.data(), w.size() * sizeof(WideRec), hipMemcpyHostToDevice));
+        if (hipError_t e = wide.alloc(w.size()); e != hipSuccess) return alloc_failed(e, who, "the wide records");
+        HIP_TRY(hipMemcpy(wide, w.data(), w.size() * sizeof(WideRec), hipMemcpyHostToDevice));
         nwide = w.size();
         wide_root = w[0];
     }
-    WideRec* d_wide = wide.as<WideRec>();
-    svo.p = leaves.p = wide.p = nullptr;
-    return install_scene(c, t.svo, t.svo_count, t.leaves, t.leaf_count, t.depth, t.root, d_wide, nwide, wide_root);
+    return install_scene(c, std::move(svo), t.svo_count, std::move(leaves), t.leaf_count, t.depth, t.root, std::move(wide), nwide, wide_root);
 }
 
 }  // namespace vxrt

@@ -42,15 +42,12 @@ void sort_by_key(std::vector<uint64_t>& key, std::vector<uint32_t>& idx, uint32_
     }
 }
 
-// a device array of `cap` entries holding the first `used` of `*p` (cap > used) and zeros after them (so that the unused entries of
-// the 8-entry blocks edits allocate are the same in every context); nothing changes when an allocation fails
-template <typename T> hipError_t grow_to(T** p, size_t used, size_t cap, T** fresh) {
-    *fresh = nullptr;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(fresh), cap * sizeof(T));
-    if (e != hipSuccess) { *fresh = nullptr; return e; }
-    e = hipMemcpy(*fresh, *p, used * sizeof(T), hipMemcpyDeviceToDevice);
-    if (e == hipSuccess) e = hipMemset(*fresh + used, 0, (cap - used) * sizeof(T));
-    if (e != hipSuccess) { (void)hipFree(*fresh); *fresh = nullptr; }
+// a device array of `cap` entries holding the first `used` of `p` (cap > used) and zeros after them (so that the unused entries of
+// the 8-entry blocks edits allocate are the same in every context)
+template <typename T> hipError_t grow_to(const T* p, size_t used, size_t cap, DeviceBuf<T>* fresh) {
+    hipError_t e = fresh->alloc(cap);
+    if (e == hipSuccess) e = hipMemcpy(fresh->get(), p, used * sizeof(T), hipMemcpyDeviceToDevice);
+    if (e == hipSuccess) e = hipMemset(fresh->get() + used, 0, (cap - used) * sizeof(T));
     return e;
 }
 
@@ -59,39 +56,32 @@ size_t grown_capacity(size_t cap, size_t need) { return std::max(need, cap + cap
 
 }  // namespace
 
-// the storage for `svo_need` records and `leaf_need` leaf words: fresh arrays (*new_svo / *new_leaves, at the capacities *svo_grow /
-// *leaf_grow) where the current ones are too small, nullptr where they are not.  Nothing changes in the context; nothing is left
-// allocated on failure.
-int grow_storage(vxrt_ctx* c, size_t svo_need, size_t leaf_need, SvoRecord** new_svo, int32_t** new_leaves, size_t* svo_grow,
-                 size_t* leaf_grow) {
-    *new_svo = nullptr;
-    *new_leaves = nullptr;
+// the storage for `svo_need` records and `leaf_need` leaf words (edit.h): all or nothing, built in a local and handed over whole
+int grow_storage(vxrt_ctx* c, size_t svo_need, size_t leaf_need, GrownStorage* out) {
+    GrownStorage g;
     const size_t svo_cap = c->svo_cap ? c->svo_cap : c->svo_count, leaf_cap = c->leaf_cap ? c->leaf_cap : c->leaf_count;
     if (svo_need >= (size_t(1) << 32) || leaf_need >= (size_t(1) << 32)) { set_error("the edited scene would exceed 2^32 records"); return VXRT_E_SCENE; }
-    *svo_grow = svo_need > svo_cap ? grown_capacity(svo_cap, svo_need) : 0;
-    *leaf_grow = leaf_need > leaf_cap ? grown_capacity(leaf_cap, leaf_need) : 0;
-    if (*svo_grow) HIP_TRY(grow_to(&c->d_svo, c->svo_count, *svo_grow, new_svo));
-    if (*leaf_grow) {
-        const hipError_t e = grow_to(&c->d_leaves, c->leaf_count, *leaf_grow, new_leaves);
-        if (e != hipSuccess) { if (*new_svo) (void)hipFree(*new_svo); *new_svo = nullptr; return hip_fail(e, "growing the scene's leaf words"); }
+    g.svo_cap = svo_need > svo_cap ? grown_capacity(svo_cap, svo_need) : 0;
+    g.leaf_cap = leaf_need > leaf_cap ? grown_capacity(leaf_cap, leaf_need) : 0;
+    if (g.svo_cap) HIP_TRY(grow_to(c->d_svo.get(), c->svo_count, g.svo_cap, &g.svo));
+    if (g.leaf_cap) {
+        if (hipError_t e = grow_to(c->d_leaves.get(), c->leaf_count, g.leaf_cap, &g.leaves); e != hipSuccess) return hip_fail(e, "growing the scene's leaf words");
     }
-    if (*svo_grow || *leaf_grow) HIP_TRY(hipDeviceSynchronize());   // the copies and fills ran on the null stream; the edit runs on c->stream
+    if (g.svo_cap || g.leaf_cap) HIP_TRY(hipDeviceSynchronize());   // the copies and fills ran on the null stream; the edit runs on c->stream
+    *out = std::move(g);
     return VXRT_OK;
 }
 
-// the grown storage replaces the old
-void commit_storage(vxrt_ctx* c, SvoRecord* new_svo, int32_t* new_leaves, size_t svo_grow, size_t leaf_grow) {
-    if (new_svo) { (void)hipFree(c->d_svo); c->d_svo = new_svo; c->svo_cap = svo_grow; }
-    if (new_leaves) { (void)hipFree(c->d_leaves); c->d_leaves = new_leaves; c->leaf_cap = leaf_grow; }
+// the grown storage replaces the old: the same records in larger arrays, so the counts, the touch maps and the DDA grid stay
+void commit_storage(vxrt_ctx* c, GrownStorage&& g) {
+    if (g.svo) { c->d_svo = std::move(g.svo); c->svo_cap = g.svo_cap; }
+    if (g.leaves) { c->d_leaves = std::move(g.leaves); c->leaf_cap = g.leaf_cap; }
 }
 
 int reserve_edit_storage(vxrt_ctx* c, size_t nodes, size_t parents) {
-    SvoRecord* new_svo;
-    int32_t* new_leaves;
-    size_t svo_grow, leaf_grow;
-    if (int rc = grow_storage(c, c->svo_count + 8 * nodes, c->leaf_count + 8 * parents, &new_svo, &new_leaves, &svo_grow, &leaf_grow))
-        return rc;
-    commit_storage(c, new_svo, new_leaves, svo_grow, leaf_grow);
+    GrownStorage g;
+    if (int rc = grow_storage(c, c->svo_count + 8 * nodes, c->leaf_count + 8 * parents, &g)) return rc;
+    commit_storage(c, std::move(g));
     return VXRT_OK;
 }
 
@@ -107,23 +97,17 @@ int apply_edit_batch(vxrt_ctx* c, const EditBatch& b) {
 
     HIP_TRY(hipSetDevice(c->cfg.device));
     if (int rc = sync_all(c)) return rc;   // frames enqueued before the edit see the old scene
-    SvoRecord* new_svo = nullptr;
-    int32_t* new_leaves = nullptr;
-    size_t svo_grow = 0, leaf_grow = 0;
-    if (int rc = grow_storage(c, svo_need, leaf_need, &new_svo, &new_leaves, &svo_grow, &leaf_grow)) return rc;
+    GrownStorage grown;
+    if (int rc = grow_storage(c, svo_need, leaf_need, &grown)) return rc;
     // host batches: one scratch of  the arrays | node scratch | flag scratch | out
     const size_t o_node = (b.host_bytes + 3) & ~size_t(3), o_flag = o_node + node_segs * 4;
     const size_t o_out = (o_flag + node_segs + 15) & ~size_t(15), bytes = o_out + 8 * 4;
     ScratchBuffer scratch;
     if (b.host) {
-        if (hipError_t e = scratch.alloc(bytes); e != hipSuccess) {
-            if (new_svo) (void)hipFree(new_svo);
-            if (new_leaves) (void)hipFree(new_leaves);
-            return hip_fail(e, "edit batch");
-        }
+        if (hipError_t e = scratch.alloc(bytes); e != hipSuccess) return hip_fail(e, "edit batch");
     }
     // from here on the edit happens
-    commit_storage(c, new_svo, new_leaves, svo_grow, leaf_grow);
+    commit_storage(c, std::move(grown));
     if (!c->edited) { c->edited = true; c->svo_built = c->svo_count; c->leaf_built = c->leaf_count; }
     EditArgs a{};
     memcpy(a.seg_off, b.seg_off, sizeof a.seg_off);
@@ -291,11 +275,11 @@ int vxrt_pick(vxrt_ctx* c, const float (*origins)[3], const float (*dirs)[3], si
     HIP_TRY(b_o.alloc(n * 12));
     HIP_TRY(b_d.alloc(n * 12));
     HIP_TRY(b_out.alloc(n * sizeof(vxrt_pick_hit)));
-    HIP_TRY(hipMemcpy(b_o.p, origins, n * 12, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(b_d.p, dirs, n * 12, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(b_o.get(), origins, n * 12, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(b_d.get(), dirs, n * 12, hipMemcpyHostToDevice));
     HIP_TRY(launch_query_pick(pick_args(c), b_o.as<float>(), b_d.as<float>(), nullptr, b_out.as<vxrt_pick_hit>(), unsigned(n), c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    HIP_TRY(hipMemcpy(out, b_out.p, n * sizeof(vxrt_pick_hit), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out, b_out.get(), n * sizeof(vxrt_pick_hit), hipMemcpyDeviceToHost));
     return VXRT_OK;
 } VXRT_CATCH
 

@@ -16,38 +16,25 @@
 namespace vxrt {
 namespace {
 
-// `*p` holds at least `need` bytes afterwards; growth is geometric (x 1.5).  A failed allocation leaves the old buffer in place.
+// `g` holds at least `need` bytes afterwards; growth is geometric (x 1.5).  A failed allocation leaves the old buffer in place.
 // The contents are not kept (every buffer here is written before it is read, within one call).
-hipError_t ensure(void** p, size_t* cap, size_t need) {
-    if (need <= *cap && *p != nullptr) return hipSuccess;
-    const size_t want = std::max(need, *cap + *cap / 2);
-    void* fresh = nullptr;
-    hipError_t e = hipMalloc(&fresh, want);
-    if (e != hipSuccess) {
+hipError_t ensure(vxrt_ctx::GrowBuf& g, size_t need) {
+    if (need <= g.cap && g.buf) return hipSuccess;
+    size_t want = std::max(need, g.cap + g.cap / 2);
+    DeviceBuf<void> fresh;
+    hipError_t e = fresh.alloc(want);
+    if (e != hipSuccess && want != need) {
         (void)hipGetLastError();
-        fresh = nullptr;
-        if (want == need) return e;
-        e = hipMalloc(&fresh, need);   // the geometric step did not fit: exactly what is needed
-        if (e != hipSuccess) { (void)hipGetLastError(); return e; }
-        if (*p) (void)hipFree(*p);
-        *p = fresh;
-        *cap = need;
-        return hipSuccess;
+        want = need;
+        e = fresh.alloc(want);   // the geometric step did not fit: exactly what is needed
     }
-    if (*p) (void)hipFree(*p);
-    *p = fresh;
-    *cap = want;
+    if (e != hipSuccess) { (void)hipGetLastError(); return e; }
+    g.buf.swap(fresh);
+    g.cap = want;
     return hipSuccess;
 }
 
 }  // namespace
-
-void free_extract(vxrt_ctx* c) {
-    vxrt_ctx::ExtractScratch& x = c->extract;
-    for (void** p : {&x.front[0], &x.front[1], &x.part, &x.pos, &x.mrgb})
-        if (*p) { (void)hipFree(*p); *p = nullptr; }
-    x.front_cap[0] = x.front_cap[1] = x.part_cap = x.pos_cap = x.mrgb_cap = 0;
-}
 
 // vxrt_get_voxels (device = false: pos / mrgb are host arrays) and vxrt_get_voxels_device (device memory of the context's device)
 static int get_voxels(vxrt_ctx* c, const int32_t box_min[3], const int32_t box_max[3], int16_t (*pos)[3], uint8_t (*mrgb)[4], size_t cap, size_t* n,
@@ -81,29 +68,29 @@ static int get_voxels(vxrt_ctx* c, const int32_t box_min[3], const int32_t box_m
     }
     vxrt_ctx::ExtractScratch& x = c->extract;
     // the root: record 0 at cell 0 (the decode runs on the context's stream, behind everything enqueued on it)
-    if (hipError_t e = ensure(&x.front[0], &x.front_cap[0], sizeof(uint4)); e != hipSuccess) return alloc_failed(e, who, "the frontier");
-    HIP_TRY(hipMemsetAsync(x.front[0], 0, sizeof(uint4), c->stream));
+    if (hipError_t e = ensure(x.front[0], sizeof(uint4)); e != hipSuccess) return alloc_failed(e, who, "the frontier");
+    HIP_TRY(hipMemsetAsync(x.front[0].buf, 0, sizeof(uint4), c->stream));
     int cur = 0;
     uint64_t count = 0;
     uint32_t frontier = 1;
     for (uint32_t l = 0; l <= L; l++) {
         a.leaf = l == L ? 1u : 0u;
         a.shift = L - l;
-        a.front = static_cast<const uint4*>(x.front[cur]);
+        a.front = x.front[cur].buf.as<const uint4>();
         a.n = frontier;
         const uint32_t blocks = extract_blocks(frontier);
-        if (hipError_t e = ensure(&x.part, &x.part_cap, (size_t(blocks) + 1) * sizeof(uint64_t)); e != hipSuccess)
+        if (hipError_t e = ensure(x.part, (size_t(blocks) + 1) * sizeof(uint64_t)); e != hipSuccess)
             return alloc_failed(e, who, "the scan partials");
-        a.part = static_cast<uint64_t*>(x.part);
+        a.part = x.part.buf.as<uint64_t>();
         HIP_TRY(launch_extract_count(a, c->stream));
         uint64_t total = 0;
         if (int rc = scan_total(a.part, blocks, c->stream, &total)) return rc;
         if (total == 0) break;
         if (a.leaf) { count = total; break; }
         if (total >= (uint64_t(1) << 32)) { set_error(std::string(who) + ": a tree level of 2^32 nodes or more"); return VXRT_E_INVALID; }
-        if (hipError_t e = ensure(&x.front[cur ^ 1], &x.front_cap[cur ^ 1], size_t(total) * sizeof(uint4)); e != hipSuccess)
+        if (hipError_t e = ensure(x.front[cur ^ 1], size_t(total) * sizeof(uint4)); e != hipSuccess)
             return alloc_failed(e, who, "the frontier");
-        a.next = static_cast<uint4*>(x.front[cur ^ 1]);
+        a.next = x.front[cur ^ 1].buf.as<uint4>();
         HIP_TRY(launch_extract_expand(a, c->stream));
         a.next = nullptr;
         cur ^= 1;
@@ -123,16 +110,16 @@ static int get_voxels(vxrt_ctx* c, const int32_t box_min[3], const int32_t box_m
         a.pos = reinterpret_cast<int16_t*>(pos);
         a.mrgb = reinterpret_cast<uint32_t*>(mrgb);
     } else {
-        if (hipError_t e = ensure(&x.pos, &x.pos_cap, size_t(count) * 3 * sizeof(int16_t)); e != hipSuccess) return alloc_failed(e, who, "the positions");
-        if (hipError_t e = ensure(&x.mrgb, &x.mrgb_cap, size_t(count) * 4); e != hipSuccess) return alloc_failed(e, who, "the leaf words");
-        a.pos = static_cast<int16_t*>(x.pos);
-        a.mrgb = static_cast<uint32_t*>(x.mrgb);
+        if (hipError_t e = ensure(x.pos, size_t(count) * 3 * sizeof(int16_t)); e != hipSuccess) return alloc_failed(e, who, "the positions");
+        if (hipError_t e = ensure(x.mrgb, size_t(count) * 4); e != hipSuccess) return alloc_failed(e, who, "the leaf words");
+        a.pos = x.pos.buf.as<int16_t>();
+        a.mrgb = x.mrgb.buf.as<uint32_t>();
     }
     HIP_TRY(launch_extract_expand(a, c->stream));
     if (!direct) {
         const hipMemcpyKind kind = device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-        HIP_TRY(hipMemcpyAsync(pos, x.pos, size_t(count) * 3 * sizeof(int16_t), kind, c->stream));
-        HIP_TRY(hipMemcpyAsync(mrgb, x.mrgb, size_t(count) * 4, kind, c->stream));
+        HIP_TRY(hipMemcpyAsync(pos, x.pos.buf, size_t(count) * 3 * sizeof(int16_t), kind, c->stream));
+        HIP_TRY(hipMemcpyAsync(mrgb, x.mrgb.buf, size_t(count) * 4, kind, c->stream));
     }
     HIP_TRY(hipStreamSynchronize(c->stream));
     *n = size_t(count);

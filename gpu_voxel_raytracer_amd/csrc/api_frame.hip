@@ -218,7 +218,7 @@ int vxrt_render_spp(vxrt_ctx* c, uint32_t flags, uint32_t spp) try {
     HIP_TRY(hipSetDevice(c->cfg.device));
     const bool timed = (flags & VXRT_TIMED) != 0;
     const size_t pixels = size_t(c->band.local_rows) * c->band.width;
-    if (spp > 1 && c->spp_sum == nullptr && pixels > 0) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->spp_sum), pixels * sizeof(float4)));
+    if (spp > 1 && c->spp_sum == nullptr && pixels > 0) HIP_TRY(c->spp_sum.alloc(pixels));
     const uint32_t batch = batches_frames(c->trace_variant) ? uint32_t(c->batch) : 1u;
     Cam first_old{};
     for (uint32_t done = 0; done < spp;) {

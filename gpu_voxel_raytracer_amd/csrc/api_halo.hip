@@ -46,10 +46,8 @@ uint32_t halo_rows_wanted(const vxrt_ctx* c) {
 }
 
 void free_halo(vxrt_ctx* c) {
-    if (c->halo) (void)hipFree(c->halo);
-    if (c->d_tile_rows) (void)hipFree(c->d_tile_rows);
-    c->halo = nullptr;
-    c->d_tile_rows = nullptr;
+    c->halo.reset();
+    c->d_tile_rows.reset();
     c->halo_store_f4 = 0;
     c->halo_view = HaloView{nullptr, 0, 0, 0, 0};
     c->halo_valid = false;
@@ -60,8 +58,7 @@ void free_halo(vxrt_ctx* c) {
 // are a band's first tile row when a band lies above it and its last one when a band lies below — whatever the radius (>= 1).
 int build_tile_rows(vxrt_ctx* c) {
     const BandMap& b = c->band;
-    if (c->d_tile_rows) (void)hipFree(c->d_tile_rows);
-    c->d_tile_rows = nullptr;
+    c->d_tile_rows.reset();
     c->tile_rows_interior = c->tile_rows_edge = 0;
     const int tile_rows = (b.local_rows + 15) / 16;
     if (tile_rows == 0 || tile_rows > 65535 || b.band_rows % 16 != 0) return VXRT_OK;   // 8-row bands: no denoise window (check_render)
@@ -78,7 +75,7 @@ int build_tile_rows(vxrt_ctx* c) {
     c->tile_rows_interior = uint32_t(interior.size());
     c->tile_rows_edge = uint32_t(edge.size());
     interior.insert(interior.end(), edge.begin(), edge.end());
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->d_tile_rows), interior.size() * sizeof(uint16_t)));
+    HIP_TRY(c->d_tile_rows.alloc(interior.size()));
     HIP_TRY(hipMemcpy(c->d_tile_rows, interior.data(), interior.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
     return VXRT_OK;
 }
@@ -153,10 +150,9 @@ int vxrt_halo_unpack(vxrt_ctx* c, const void* dev_from_prev, const void* dev_fro
     HaloView v = view_for(c, rows);
     if (c->halo == nullptr || c->halo_store_f4 < 2 * v.message) {
         HIP_TRY(hipStreamSynchronize(c->stream));   // a stage that reads the old store may still be running (only when the layout grows)
-        if (c->halo) (void)hipFree(c->halo);
-        c->halo = nullptr;
+        c->halo.reset();
         c->halo_store_f4 = 0;
-        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->halo), 2 * v.message * sizeof(float4)));
+        HIP_TRY(c->halo.alloc(2 * v.message));
         c->halo_store_f4 = 2 * v.message;
     }
     EventPair p = take_pair(c, 4);

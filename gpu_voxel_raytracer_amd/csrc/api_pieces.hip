@@ -24,7 +24,7 @@ int reduce_pieces(Labelling* l, uint32_t anchored, const char* who, ScratchBuffe
 
 // The selected components marked at their labels, in l->uhead (the reduce was its last reader), zeroed first.
 int mark_pieces(Labelling* l, uint32_t n, uint32_t min_voxels, uint32_t max_voxels, PieceAcc* accs, hipStream_t s) {
-    HIP_TRY(hipMemsetAsync(l->uhead.p, 0, size_t(n) * sizeof(uint32_t), s));
+    HIP_TRY(hipMemsetAsync(l->uhead.get(), 0, size_t(n) * sizeof(uint32_t), s));
     HIP_TRY(pieces_mark(accs, uint32_t(l->components), n, min_voxels, max_voxels, l->uhead.as<uint32_t>(), s));
     return VXRT_OK;
 }
@@ -38,7 +38,7 @@ int scene_list(vxrt_ctx* c, const char* who, ScratchBuffer* pos, ScratchBuffer* 
     if (int rc = alloc_scratch(pos, *total * 3 * sizeof(int16_t), who, "the scene's positions")) return rc;
     if (int rc = alloc_scratch(mrgb, *total * 4, who, "the scene's mrgb words")) return rc;
     size_t got = 0;
-    return vxrt_get_voxels_device(c, nullptr, nullptr, reinterpret_cast<int16_t(*)[3]>(pos->p), reinterpret_cast<uint8_t(*)[4]>(mrgb->p), *total, &got);
+    return vxrt_get_voxels_device(c, nullptr, nullptr, reinterpret_cast<int16_t(*)[3]>(pos->get()), reinterpret_cast<uint8_t(*)[4]>(mrgb->get()), *total, &got);
 }
 
 }  // namespace

@@ -11,7 +11,8 @@ namespace vxrt {
 int build_menger_svo(uint32_t level, uint32_t clip, const uint8_t mrgb[4], uint32_t emissive_period, std::vector<SvoRecord>* recs,
                      std::vector<int32_t>* leaves, uint32_t* depth_out);
 bool menger_device_build_supported(uint32_t level, uint32_t clip);
-int reorder_bottom_treelets(SvoRecord** d_svo, size_t n, const std::vector<size_t>& level_first, uint32_t depth, int levels, hipStream_t stream);
+int reorder_bottom_treelets(const SvoRecord* svo, size_t n, const std::vector<size_t>& level_first, uint32_t depth, int levels, hipStream_t stream,
+                            DeviceBuf<SvoRecord>* out);
 int build_menger_svo_device(uint32_t level, uint32_t clip, const uint8_t mrgb[4], uint32_t emissive_period, hipStream_t stream,
                             SvoRecord** d_svo, size_t* svo_count, int32_t** d_leaves, size_t* leaf_count, uint32_t* depth_out, SvoRecord* root);
 }
@@ -143,7 +144,10 @@ int apply_node_order(vxrt_ctx* c) {
         first[l] = r.base;
         HIP_TRY(hipMemcpy(&r, c->d_svo + r.base, sizeof r, hipMemcpyDeviceToHost));
     }
-    if (int rc = reorder_bottom_treelets(&c->d_svo, c->svo_count, first, c->depth, c->node_order, c->stream)) return rc;
+    DeviceBuf<SvoRecord> ordered;
+    if (int rc = reorder_bottom_treelets(c->d_svo, c->svo_count, first, c->depth, c->node_order, c->stream, &ordered)) return rc;
+    // the same tree in another order: the leaf words and the wide records stay (moved onto themselves)
+    replace_scene_arrays(c, std::move(ordered), c->svo_count, std::move(c->d_leaves), c->leaf_count, std::move(c->d_wide), c->wide_count);
     c->node_order_applied = c->node_order;
     return VXRT_OK;
 }
@@ -169,25 +173,34 @@ int device_scene_box(const SvoRecord* svo, size_t nsvo, uint32_t depth, SvoRecor
     return VXRT_OK;
 }
 
-// Device arrays built for the context become its scene (the context owns them from here; the old scene's arrays are freed): the
-// tail of every device build (vxrt_set_menger, vxrt_set_voxels_device).  The caller has drained the context (sync_all).  wide: the
-// same tree's wide records (VXRT_OPT_SCENE_FORMAT 1) or null.
-int install_scene(vxrt_ctx* c, SvoRecord* svo, size_t nsvo, int32_t* lw, size_t nlw, uint32_t depth, SvoRecord root, WideRec* wide,
-                  size_t nwide, WideRec wide_root) {
-    if (c->d_svo) (void)hipFree(c->d_svo);
-    if (c->d_leaves) (void)hipFree(c->d_leaves);
-    if (c->d_wide) (void)hipFree(c->d_wide);
+void replace_scene_arrays(vxrt_ctx* c, DeviceBuf<SvoRecord>&& svo, size_t nsvo, DeviceBuf<int32_t>&& leaves, size_t nleaves, DeviceBuf<WideRec>&& wide,
+                          size_t nwide) {
+    c->d_svo = std::move(svo);
+    c->d_leaves = std::move(leaves);
+    c->d_wide = std::move(wide);
+    c->svo_count = nsvo; c->leaf_count = nleaves; c->wide_count = nwide;
     drop_touch_maps(c);
-    c->d_svo = svo; c->d_leaves = lw; c->d_wide = wide;
-    c->svo_count = nsvo; c->leaf_count = nlw; c->wide_count = nwide;
+}
+
+// the rest of a new scene's bookkeeping, shared by install_scene and upload_svo: the root cube of a tree of `depth`, none of it edited
+static void scene_set(vxrt_ctx* c, uint32_t depth, SvoRecord root, WideRec wide_root) {
     c->root_rec = root;
     c->wide_root = wide_root;
-    c->root_center[0] = c->root_center[1] = c->root_center[2] = 0.0f;
-    c->root_size = float(1u << depth);
+    c->root_center[0] = c->root_center[1] = c->root_center[2] = 0.0f;  // src/context.rs:782-786
+    c->root_size = float(1u << depth);                                   // src/context.rs:779
     c->depth = depth;
     c->has_scene = true;
     scene_replaced(c);
-    if (int rc = device_scene_box(svo, nsvo, depth, root, c->root_center, c->root_size, &c->box_valid, c->box_min, c->box_max)) return rc;
+}
+
+// Device arrays built for the context become its scene (the context owns them from here; the old scene's arrays are freed): the
+// tail of every device build (vxrt_set_menger, vxrt_set_voxels_device).  The caller has drained the context (sync_all).  wide: the
+// same tree's wide records (VXRT_OPT_SCENE_FORMAT 1) or empty.
+int install_scene(vxrt_ctx* c, DeviceBuf<SvoRecord>&& svo, size_t nsvo, DeviceBuf<int32_t>&& lw, size_t nlw, uint32_t depth, SvoRecord root,
+                  DeviceBuf<WideRec>&& wide, size_t nwide, WideRec wide_root) {
+    replace_scene_arrays(c, std::move(svo), nsvo, std::move(lw), nlw, std::move(wide), nwide);
+    scene_set(c, depth, root, wide_root);
+    if (int rc = device_scene_box(c->d_svo, nsvo, depth, root, c->root_center, c->root_size, &c->box_valid, c->box_min, c->box_max)) return rc;
     return c->scene_format == 1 ? VXRT_OK : apply_node_order(c);
 }
 
@@ -200,32 +213,23 @@ int upload_svo(vxrt_ctx* c, std::vector<SvoRecord>& recs, std::vector<int32_t>& 
     // default never uses them and does not pay for their memory.
     std::vector<WideRec> wide;
     if (c->scene_format == 1) { if (int rc = widen_svo(recs, depth, &wide)) return rc; }
-    if (c->d_svo) (void)hipFree(c->d_svo);
-    if (c->d_leaves) (void)hipFree(c->d_leaves);
-    if (c->d_wide) (void)hipFree(c->d_wide);
-    drop_touch_maps(c);
-    c->d_svo = nullptr;
-    c->d_leaves = nullptr;
-    c->d_wide = nullptr;
-    c->wide_count = wide.size();
-    c->wide_root = WideRec{0, 0, 0, 0};
+    // The old scene goes before the new one is allocated (both at once would double the peak of a scene of gigabytes), so a failure
+    // from here on leaves the context without a scene: has_scene implies the arrays.
+    replace_scene_arrays(c, {}, 0, {}, 0, {}, 0);
+    c->has_scene = false;
+    DeviceBuf<SvoRecord> d_svo;
+    DeviceBuf<int32_t> d_leaves;
+    DeviceBuf<WideRec> d_wide;
     if (!wide.empty()) {
-        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->d_wide), wide.size() * sizeof(WideRec)));
-        HIP_TRY(hipMemcpy(c->d_wide, wide.data(), wide.size() * sizeof(WideRec), hipMemcpyHostToDevice));
-        c->wide_root = wide[0];
+        HIP_TRY(d_wide.alloc(wide.size()));
+        HIP_TRY(hipMemcpy(d_wide, wide.data(), wide.size() * sizeof(WideRec), hipMemcpyHostToDevice));
     }
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->d_svo), recs.size() * sizeof(SvoRecord)));
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->d_leaves), leaves.size() * sizeof(int32_t)));
-    HIP_TRY(hipMemcpy(c->d_svo, recs.data(), recs.size() * sizeof(SvoRecord), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(c->d_leaves, leaves.data(), leaves.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-    c->svo_count = recs.size();
-    c->root_rec = recs.empty() ? SvoRecord{0, 0} : recs[0];
-    c->leaf_count = leaves.size();
-    c->root_center[0] = c->root_center[1] = c->root_center[2] = 0.0f;  // src/context.rs:782-786
-    c->root_size = float(1u << depth);                                   // src/context.rs:779
-    c->depth = depth;
-    c->has_scene = true;
-    scene_replaced(c);
+    HIP_TRY(d_svo.alloc(recs.size()));
+    HIP_TRY(d_leaves.alloc(leaves.size()));
+    HIP_TRY(hipMemcpy(d_svo, recs.data(), recs.size() * sizeof(SvoRecord), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_leaves, leaves.data(), leaves.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    replace_scene_arrays(c, std::move(d_svo), recs.size(), std::move(d_leaves), leaves.size(), std::move(d_wide), wide.size());
+    scene_set(c, depth, recs.empty() ? SvoRecord{0, 0} : recs[0], wide.empty() ? WideRec{0, 0, 0, 0} : wide[0]);
     c->box_valid = scene_box(recs.data(), recs.size(), depth, c->root_center, c->root_size, c->box_min, c->box_max);
     return c->scene_format == 1 ? VXRT_OK : apply_node_order(c);
 }
@@ -294,7 +298,11 @@ int vxrt_set_menger(vxrt_ctx* c, uint32_t level, uint32_t clip, const uint8_t mr
         size_t nsvo = 0, nlw = 0;
         SvoRecord root{0, 0};
         if (int rc = build_menger_svo_device(level, clip, mrgb, emissive_period, c->stream, &svo, &nsvo, &lw, &nlw, &depth, &root)) return rc;
-        return install_scene(c, svo, nsvo, lw, nlw, depth, root, nullptr, 0, WideRec{0, 0, 0, 0});
+        DeviceBuf<SvoRecord> d_svo;
+        DeviceBuf<int32_t> d_lw;
+        d_svo.adopt(svo);
+        d_lw.adopt(lw);
+        return install_scene(c, std::move(d_svo), nsvo, std::move(d_lw), nlw, depth, root, {}, 0, WideRec{0, 0, 0, 0});
     }
     std::vector<SvoRecord> recs;
     std::vector<int32_t> leaves;

@@ -21,7 +21,7 @@ int probe_depth(vxrt_ctx* c, const char* who, uint32_t* levels, bool* one) {
     if (int rc = alloc_scratch(&out, 2 * sizeof(uint32_t), who, "the probe's result")) return rc;
     HIP_TRY(launch_depth_probe(c->d_svo, c->root_rec, c->depth, out.as<uint32_t>(), c->stream));
     uint32_t h[2];
-    HIP_TRY(hipMemcpyAsync(h, out.p, sizeof h, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(h, out.get(), sizeof h, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     *levels = h[0];
     *one = h[1] != 0u;
@@ -42,12 +42,10 @@ int change_depth(vxrt_ctx* c, uint32_t to) {
     } else if (M != 0u && to == 0) {
         leaf_add = 8;
     }
-    SvoRecord* new_svo;
-    int32_t* new_leaves;
-    size_t svo_grow, leaf_grow;
-    if (int rc = grow_storage(c, c->svo_count + svo_add, c->leaf_count + leaf_add, &new_svo, &new_leaves, &svo_grow, &leaf_grow)) return rc;
+    GrownStorage grown;
+    if (int rc = grow_storage(c, c->svo_count + svo_add, c->leaf_count + leaf_add, &grown)) return rc;
     // from here on the change happens
-    commit_storage(c, new_svo, new_leaves, svo_grow, leaf_grow);
+    commit_storage(c, std::move(grown));
     if (!c->edited) { c->edited = true; c->svo_built = c->svo_count; c->leaf_built = c->leaf_count; }   // as apply_edit_batch
     SvoRecord root = c->root_rec;
     if (M != 0u && to > from) {

@@ -15,24 +15,18 @@ int resize_tail_queues(vxrt_ctx* c, unsigned want) {
     if (want == c->shard_capacity) return VXRT_OK;
     if (int rc = sync_all(c)) return rc;
     const size_t new_bytes = (size_t(want) * 64 + 1) * 64, old_bytes = (size_t(c->shard_capacity) * 64 + 1) * 64;
-    std::vector<float4*> fresh;
+    std::vector<DeviceBuf<float4>> fresh;
     for (vxrt_ctx::StreamQueues& q : c->queues)
-        for (float4* p : q.hitq)
+        for (DeviceBuf<float4>& p : q.hitq)
             if (p) {
-                float4* n = nullptr;
-                const hipError_t e = hipMalloc(reinterpret_cast<void**>(&n), new_bytes);
-                if (e != hipSuccess) {
-                    for (float4* f : fresh) (void)hipFree(f);
-                    return hip_fail(e, "hipMalloc (tail queues)");
-                }
-                fresh.push_back(n);
+                fresh.emplace_back();
+                if (hipError_t e = fresh.back().alloc(new_bytes / sizeof(float4)); e != hipSuccess) return hip_fail(e, "hipMalloc (tail queues)");
             }
     size_t k = 0;
     for (vxrt_ctx::StreamQueues& q : c->queues)
-        for (float4*& p : q.hitq)
+        for (DeviceBuf<float4>& p : q.hitq)
             if (p) {
-                (void)hipFree(p);
-                p = fresh[k++];
+                p.swap(fresh[k++]);   // the old queue goes with `fresh`
                 c->queue_bytes += new_bytes - old_bytes;
             }
     c->shard_capacity = want;
@@ -428,12 +422,12 @@ static int issue_trace_kernel(TraceLaunch& L) {
 static int fork_long_tiles(TraceLaunch& L) {
     vxrt_ctx* c = L.c;
     const size_t lane = L.lane;
-    if (c->aux_streams.size() <= lane) c->aux_streams.resize(lane + 1, nullptr);
-    if (c->aux_fork.size() <= lane) { c->aux_fork.resize(lane + 1, nullptr); c->aux_join.resize(lane + 1, nullptr); }
-    if (c->aux_streams[lane] == nullptr) {
-        HIP_TRY(hipStreamCreateWithFlags(&c->aux_streams[lane], hipStreamNonBlocking));
-        HIP_TRY(hipEventCreateWithFlags(&c->aux_fork[lane], hipEventDisableTiming));
-        HIP_TRY(hipEventCreateWithFlags(&c->aux_join[lane], hipEventDisableTiming));
+    if (c->aux_streams.size() <= lane) c->aux_streams.resize(lane + 1);
+    if (c->aux_fork.size() <= lane) { c->aux_fork.resize(lane + 1); c->aux_join.resize(lane + 1); }
+    if (c->aux_join[lane] == nullptr) {   // made last: all three are there
+        HIP_TRY(c->aux_streams[lane].create(hipStreamNonBlocking));
+        HIP_TRY(c->aux_fork[lane].create(hipEventDisableTiming));
+        HIP_TRY(c->aux_join[lane].create(hipEventDisableTiming));
     }
     TraceArgs al = L.a;
     al.tail = PathQueue{nullptr, nullptr, 0};     // nothing is handed over: trace_kernel follows these paths to their end
@@ -498,9 +492,9 @@ static int issue_fused(TraceLaunch& L) {
     vxrt_ctx* c = L.c;
     vxrt_ctx::StreamQueues& sq = c->queues[L.lane];
     const CountSets& counts = L.counts;
-    if (sq.fused_ctl == nullptr) {
-        HIP_TRY(hipMalloc(&sq.fused_ctl, fused_ctl_bytes()));
-        HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&sq.host_ctl), 64, hipHostMallocDefault));    // word 2: the kernel's error word
+    if (sq.host_ctl == nullptr) {   // made last: both are there
+        HIP_TRY(sq.fused_ctl.alloc(fused_ctl_bytes()));
+        HIP_TRY(sq.host_ctl.alloc(64 / sizeof(unsigned)));    // word 2: the kernel's error word
         memset(sq.host_ctl, 0, 64);
     }
     if (!sq.stamps_clean) {   // once per allocation of the queue: every slot's stamp must read 0
@@ -513,7 +507,7 @@ static int issue_fused(TraceLaunch& L) {
     const unsigned fused_slots = c->wave_slots / 5u * 4u;      // fused_kernel is compiled for 4 waves per SIMD (trace.hip: VXRT_FUSED_WAVES)
     HIP_TRY(launch_fused(L.a, sq.fused_ctl, fused_slots < all_blocks ? fused_slots : all_blocks, L.a.tile_order ? c->schedules[L.lane].scratch : nullptr, stamp, L.ts));
     sq.launches = counts.J + 1;
-    return copy_counts(c, sq, counts.written(), L.ts, sq.host_ctl + 2, static_cast<char*>(sq.fused_ctl) + fused_ctl_error_offset());
+    return copy_counts(c, sq, counts.written(), L.ts, sq.host_ctl + 2, sq.fused_ctl + fused_ctl_error_offset());
 }
 
 // tracers 2 and 3: the launches per path segment of the wavefront and of the ray queues

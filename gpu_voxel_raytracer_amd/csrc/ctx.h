@@ -33,6 +33,7 @@
 #include "../../include/vxrt_debug.h"
 #include "../../include/vxrt_host.h"
 #include "kernels.h"
+#include "owned.h"
 #include "scene_host.h"
 
 namespace vxrt {
@@ -56,13 +57,8 @@ inline int hip_fail(hipError_t e, const char* what) {
         if (e_ != hipSuccess) return vxrt::hip_fail(e_, #expr); \
     } while (0)
 
-// a device allocation that lives as long as the entry point that made it (released on every return path)
-struct ScratchBuffer {
-    void* p = nullptr;
-    ~ScratchBuffer() { if (p) (void)hipFree(p); }
-    hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes); }
-    template <typename T> T* as() const { return static_cast<T*>(p); }
-};
+// a device allocation of bytes; as a local it lives as long as the entry point that made it (released on every return path)
+using ScratchBuffer = DeviceBuf<void>;
 
 // A failed device allocation of an entry point: clears the HIP error, sets "<who>: allocating <what>: <hip error>", VXRT_E_DEVICE.
 inline int alloc_failed(hipError_t e, const char* who, const char* what) {
@@ -75,7 +71,6 @@ inline int alloc_failed(hipError_t e, const char* who, const char* what) {
 inline int alloc_scratch(ScratchBuffer* b, size_t bytes, const char* who, const char* what) {
     const hipError_t e = b->alloc(bytes ? bytes : 16);
     if (e == hipSuccess) return VXRT_OK;
-    b->p = nullptr;
     return alloc_failed(e, who, what);
 }
 
@@ -92,12 +87,12 @@ int write_voxels_staged(void* pos, void* mrgb, size_t count, hipStream_t s, cons
     if (int rc = alloc_scratch(&stage[0], count * 3 * sizeof(int16_t), who, "the positions")) return rc;
     if (int rc = alloc_scratch(&stage[1], count * 4, who, "the mrgb words")) return rc;
     HIP_TRY(write(stage[0].as<int16_t>(), stage[1].as<uint32_t>()));
-    HIP_TRY(hipMemcpyAsync(pos, stage[0].p, count * 3 * sizeof(int16_t), hipMemcpyDeviceToDevice, s));
-    HIP_TRY(hipMemcpyAsync(mrgb, stage[1].p, count * 4, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipMemcpyAsync(pos, stage[0].get(), count * 3 * sizeof(int16_t), hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipMemcpyAsync(mrgb, stage[1].get(), count * 4, hipMemcpyDeviceToDevice, s));
     return VXRT_OK;
 }
 
-struct EventPair {
+struct EventPair {   // handles, not owned: the events live in vxrt_ctx::pair_events
     hipEvent_t a = nullptr, b = nullptr;
     int stage = 0;  // 0 trace, 1 temporal, 2 denoise, 3 halo pack, 4 halo unpack
 };
@@ -108,17 +103,25 @@ using namespace vxrt;
 struct vxrt_ctx {
     vxrt_config cfg{};
     BandMap band{};
-    hipStream_t stream = nullptr;
+    // Ownership: every member that is a DeviceBuf, PinnedBuf, Event or Stream (owned.h) is released by the context's destructor;
+    // raw pointers and handles below are pieces or copies of an owned member and say so.  Members are destroyed in reverse order of
+    // declaration, so the streams, declared here before everything else that owns, outlive every buffer and every event.
+    Stream stream;
+    std::vector<Stream> own_trace_streams;    // the trace streams of a context with inflight >= 2 (none with inflight == 1)
+    std::vector<hipStream_t> trace_streams;   // handles, not owned: inflight entries; own_trace_streams, or `stream` when inflight == 1
+    std::vector<Stream> aux_streams;          // one per trace stream, made on first use: the all-in-one grid of the longest tiles (VXRT_OPT_LONG_TILES)
+    std::vector<Stream> low_streams;          // VXRT_OPT_TRACE_PRIORITY: one low-priority stream per trace stream
+    Stream copy_stream;                       // vxrt_read_async
 
     // scene
     bool has_scene = false;
-    SvoRecord* d_svo = nullptr;
+    DeviceBuf<SvoRecord> d_svo;               // with d_leaves and d_wide replaced only by replace_scene_arrays and commit_storage
     SvoRecord root_rec{0, 0};  // d_svo[0], passed to the kernels by value (every cast starts with it)
-    WideRec* d_wide = nullptr; // the same tree as wide records (kernels.h): two levels per 16-byte record
+    DeviceBuf<WideRec> d_wide; // the same tree as wide records (kernels.h): two levels per 16-byte record
     WideRec wide_root{0, 0, 0, 0};
     size_t wide_count = 0;
     int scene_format = 0;      // VXRT_OPT_SCENE_FORMAT: 0 the 8-byte records (default), 1 also build and walk the wide records
-    int32_t* d_leaves = nullptr;
+    DeviceBuf<int32_t> d_leaves;
     size_t svo_count = 0, leaf_count = 0;
     float root_center[3] = {0, 0, 0};
     float root_size = 1.0f;
@@ -127,22 +130,19 @@ struct vxrt_ctx {
     float box_min[3] = {0, 0, 0}, box_max[3] = {0, 0, 0};
     int sky_cull = 1;   // VXRT_OPT_SKY_CULL
     uint32_t depth = 0;
-    float* d_noise = nullptr;
+    DeviceBuf<float> d_noise;
     // in-place edits (api_edit.hip, vxrt_edit.h).  The first edit records how many records / leaf words the build produced: a block
     // below those counts is tight, one at or above them was allocated by an edit and holds 8 entries.  The storage grows only there.
     bool edited = false;
     size_t svo_built = 0, leaf_built = 0;
     size_t svo_cap = 0, leaf_cap = 0;   // entries allocated once an edit grew the storage (0: exactly svo_count / leaf_count)
     size_t live_nodes = 0;              // records in the tree (svo_count less the holes edits left: vxrt_stats.octree_nodes)
-    // vxrt_get_voxels (api_extract.hip): the decode's scratch, grown on demand (never shrunk), freed by vxrt_destroy
+    // vxrt_get_voxels (api_extract.hip): the decode's scratch, grown on demand (never shrunk), released with the context
+    struct GrowBuf { DeviceBuf<void> buf; size_t cap = 0; };   // cap: bytes
     struct ExtractScratch {
-        void* front[2] = {nullptr, nullptr};   // frontier double buffer: uint4 {record, u.x, u.y, u.z} per node
-        size_t front_cap[2] = {0, 0};          // bytes
-        void* part = nullptr;                  // uint64 scan partials, one per block of the frontier, + the total
-        size_t part_cap = 0;
-        void* pos = nullptr;                   // output staging: int16[3] and 4 bytes per voxel
-        void* mrgb = nullptr;
-        size_t pos_cap = 0, mrgb_cap = 0;
+        GrowBuf front[2];   // frontier double buffer: uint4 {record, u.x, u.y, u.z} per node
+        GrowBuf part;       // uint64 scan partials, one per block of the frontier, + the total
+        GrowBuf pos, mrgb;  // output staging: int16[3] and 4 bytes per voxel
     };
     ExtractScratch extract;
 
@@ -151,24 +151,22 @@ struct vxrt_ctx {
     // the temporal/denoise stages run in frame order on `stream`.  A slot is not re-used while it still is
     // the temporal history or while a stage that reads it is in flight (slot.last_use).
     struct Slot {
-        float4* sampled_color = nullptr;
+        float4* sampled_color = nullptr;   // pieces of ring_arena, not owned
         float4* albedo = nullptr;
         float4* nd = nullptr;
         // Events.  A trace launch covers up to 32 slots and is ONE event (launch_events, per trace stream): recording two events
         // per slot cost ~8 us of host time per frame of a launch — more than a rank of 8 can afford (scripts/exp_host_submit.py).
-        hipEvent_t own = nullptr;         // owned: recorded on the main stream by the stages that read the slot (temporal, denoise, halo pack, spp)
+        Event own;                        // recorded on the main stream by the stages that read the slot (temporal, denoise, halo pack, spp)
         hipEvent_t trace_done = nullptr;  // handle, not owned: the event of the launch that traced the slot
         hipEvent_t last_use = nullptr;    // handle: what must have finished before the slot is traced into again (`own` or a launch's event)
         bool last_use_recorded = false;
     };
     std::vector<Slot> ring;
     int inflight = 1;
-    std::vector<hipStream_t> trace_streams;   // inflight entries; entry 0 is `stream` when inflight == 1
-    char* ring_arena = nullptr;               // the ring's images: one allocation (alloc_images)
-    std::vector<hipEvent_t> launch_events;    // two per trace stream, used alternately: "this launch has finished"
-    std::vector<hipEvent_t> head_events;      // one per trace stream: "this stream's last trace_kernel has finished" (VXRT_OPT_HEAD_STAGGER)
-    std::vector<hipStream_t> aux_streams;     // one per trace stream, made on first use: the all-in-one grid of the longest tiles (VXRT_OPT_LONG_TILES)
-    std::vector<hipEvent_t> aux_fork, aux_join;
+    DeviceBuf<char> ring_arena;               // the ring's images: one allocation (alloc_images)
+    std::vector<Event> launch_events;    // two per trace stream, used alternately: "this launch has finished"
+    std::vector<Event> head_events;      // one per trace stream: "this stream's last trace_kernel has finished" (VXRT_OPT_HEAD_STAGGER)
+    std::vector<Event> aux_fork, aux_join;    // with aux_streams
     uint32_t long_tiles_permille = 0;         // 0: off
     int fused_tail = 0;                       // VXRT_OPT_FUSED_TAIL: head and compacted tail of a launch as one grid of persistent waves
     uint64_t fused_errors = 0;                // launches whose fused_kernel gave up a bounded wait (reported by vxrt_sync)
@@ -177,17 +175,17 @@ struct vxrt_ctx {
     std::vector<unsigned> launch_event_turn;
     int slot = 0;        // slot of the most recently traced frame
     int hist_slot = -1;  // slot whose normal/depth pairs with accum[hist] as the temporal history
-    float4* accum[2] = {nullptr, nullptr};
-    float4* denoised = nullptr;
-    float4* spp_sum = nullptr;  // running sum of vxrt_render_spp (allocated on first use)
+    DeviceBuf<float4> accum[2];
+    DeviceBuf<float4> denoised;
+    DeviceBuf<float4> spp_sum;  // running sum of vxrt_render_spp (allocated on first use)
     // multi-rank halo (api_halo.hip): the rows of the neighbouring ranks just outside this rank's bands, as last unpacked
-    float4* halo = nullptr;            // store: two messages (kernels.h: HaloView)
+    DeviceBuf<float4> halo;            // store: two messages (kernels.h: HaloView)
     size_t halo_store_f4 = 0;          // its size in float4
     HaloView halo_view{nullptr, 0, 0, 0, 0};   // what the store holds right now (rows = 0: nothing)
     uint32_t halo_min_rows = 1;        // VXRT_OPT_HALO_ROWS: rows that travel even without a denoise window (temporal's reprojection)
     bool halo_valid = false;           // the store holds the current frame's rows (cleared by the next trace)
-    hipEvent_t halo_event = nullptr;   // vxrt_stream_wait_context / vxrt_context_wait_stream
-    uint16_t* d_tile_rows = nullptr;   // denoise tile rows: [interior..., edge...] (those that need no halo, those that do)
+    Event halo_event;                  // vxrt_stream_wait_context / vxrt_context_wait_stream
+    DeviceBuf<uint16_t> d_tile_rows;   // denoise tile rows: [interior..., edge...] (those that need no halo, those that do)
     uint32_t tile_rows_interior = 0, tile_rows_edge = 0;
     uint64_t temporal_count = 0;       // temporal stages run so far ...
     uint64_t halo_epoch = ~0ull;       // ... and its value when the halo was last imported: equal -> the halo holds the
@@ -210,22 +208,22 @@ struct vxrt_ctx {
     bool old_cam_valid = false;
 
     // stats
-    unsigned long long* d_rays = nullptr;
+    DeviceBuf<unsigned long long> d_rays;
     // wavefront tracer: two path queues (ping-pong) and three rotating sets of 64 shard counters
     struct StreamQueues {  // per trace stream; allocated only for the queue-based variants
-        float4* hitq[2] = {nullptr, nullptr};  // sharded PathRec queues (variant 2: ping-pong; variant 3: [0] = primary hits)
-        unsigned* counts3 = nullptr;            // three rotating sets of 64 shard counters
+        DeviceBuf<float4> hitq[2];              // sharded PathRec queues (variant 2: ping-pong; variant 3: [0] = primary hits)
+        DeviceBuf<unsigned> counts3;            // three rotating sets of 64 shard counters
         unsigned launches = 0;
-        RayQueue rq{};                          // variant 3
-        void* rq_block = nullptr;
+        RayQueue rq{};                          // variant 3: pointers into rq_block, not owned
+        DeviceBuf<char> rq_block;
         // tail queue sized by need (variants 4 / 5): the counters trace_kernel wrote, copied back after every launch
-        unsigned* host_counts = nullptr;        // pinned, one set: 64 counters, 16 uints apart
-        hipEvent_t counts_ready = nullptr;
+        PinnedBuf<unsigned> host_counts;        // pinned, one set: 64 counters, 16 uints apart
+        Event counts_ready;
         bool counts_pending = false;
         unsigned counts_capacity = 0;           // the shard capacity of the launch whose counters host_counts holds
         // fused head + tail (VXRT_OPT_FUSED_TAIL; trace.hip: fused_kernel)
-        void* fused_ctl = nullptr;              // the launch's cursors, zeroed on the stream before every launch
-        unsigned* host_ctl = nullptr;           // pinned: the first 16 bytes of fused_ctl after a launch (word 2: a bounded wait ran out)
+        DeviceBuf<char> fused_ctl;              // the launch's cursors, zeroed on the stream before every launch
+        PinnedBuf<unsigned> host_ctl;           // pinned: the first 16 bytes of fused_ctl after a launch (word 2: a bounded wait ran out)
         bool stamps_clean = false;              // every record slot of hitq[0] carries stamp 0 (set when the queue is cleared, lost when it is re-allocated)
         unsigned fused_launches = 0;            // -> the launch's stamp, 1 .. 65535
     };
@@ -247,16 +245,16 @@ struct vxrt_ctx {
     unsigned rays_per_wave = 256;  // ray-queue tracer: fewest rays a trace wave takes (more = better lane refill, fewer waves)
     // longest-tile-first scheduling of the monolithic kernel: cost of every 16x16 tile in the last frame -> order
     struct TileSchedule {  // one per trace stream: costs of the frame it traced last, and the order made from them
-        uint32_t* cost = nullptr;
-        uint32_t* order = nullptr;
-        uint32_t* last_cost = nullptr;  // copy for diagnostics (vxrt_debug_tile_costs)
-        uint32_t* scratch = nullptr;    // per-block histograms of the sort (256 x 128)
+        DeviceBuf<uint32_t> cost;
+        DeviceBuf<uint32_t> order;
+        DeviceBuf<uint32_t> last_cost;  // copy for diagnostics (vxrt_debug_tile_costs)
+        DeviceBuf<uint32_t> scratch;    // per-block histograms of the sort (256 x 128)
         bool valid = false;
         int age = 0;  // frames traced since the last sort
         // VXRT_OPT_TRACE_PRIORITY: how many tiles of `order` walk (they come first: the order is plain longest-first then), read back
         // after every sort; 0 = not known (yet): the launch goes out as one grid
-        unsigned* host_heavy = nullptr;     // pinned
-        hipEvent_t heavy_ready = nullptr;
+        PinnedBuf<unsigned> host_heavy;     // pinned
+        Event heavy_ready;
         bool heavy_pending = false;
         unsigned heavy = 0;
     };
@@ -274,7 +272,7 @@ struct vxrt_ctx {
     // VXRT_OPT_SHARED_PRIMARY: a launch of >= 2 frames of ONE camera walks each pixel's primary ray once (trace.hip: first_hit_kernel).
     int shared_primary = 1;
     uint64_t shared_primary_launches = 0;   // vxrt_debug_shared_primary_launches
-    std::vector<uint4*> first_hits;         // per trace stream: one 16-byte record per pixel of the band (contexts with frames_per_launch >= 2)
+    std::vector<DeviceBuf<uint4>> first_hits;         // per trace stream: one 16-byte record per pixel of the band (contexts with frames_per_launch >= 2)
     int path_blocks = 512;  // tracer 5: blocks of path_kernel (each wave takes an equal range of the queue, >= 512 paths)
     int tail_from = 1;  // tracer 4: the hit number at which live paths move to the compacted launches
     unsigned tail_split = 0;  // ... bit k: the tail compacts again and starts a new launch at path segment k
@@ -283,19 +281,19 @@ struct vxrt_ctx {
     double ms[5] = {0, 0, 0, 0, 0};   // trace, temporal, denoise, halo pack, halo unpack
     uint64_t halo_exchanges = 0;
     std::vector<EventPair> pending, free_pairs;
+    std::vector<Event> pair_events;   // every event take_pair made: the pairs above are handles to them
 
     // vxrt_read_async (api_context.hip): a copy stream of the context's own, two slots; a slot = a device-side snapshot of the image
     // (so that later frames may overwrite the image while the snapshot travels) + "snapshot taken" / "transfer arrived" events
     struct ReadSlot {
-        float4* stage = nullptr;
+        DeviceBuf<char> stage;
         size_t stage_bytes = 0;
-        hipEvent_t snap = nullptr, arrived = nullptr;
+        Event snap, arrived;
         bool in_flight = false;
     };
-    hipStream_t copy_stream = nullptr;
     ReadSlot read_slots[2];
     // the displayed frame (vxrt_device_image / vxrt_read of VXRT_DISPLAY_*): 4 bytes per pixel, allocated on first use, freed with the images
-    uint32_t* display = nullptr;
+    DeviceBuf<uint32_t> display;
 
     // VXRT_OPT_TRACE_PRIORITY (round 6's experiment): the trace streams at the device's highest priority, the tiles that only store
     // sky as a grid of their own on a low-priority stream per trace stream
@@ -303,17 +301,16 @@ struct vxrt_ctx {
     int xcd_affinity = 0;               // VXRT_OPT_XCD_AFFINITY: 0 off, S = side of a super-tile in tiles (api_trace.hip: xcd_affine_order)
     unsigned xcd_balance_permille = 0;  // (max - min) / max of the 8 lists' summed costs at the last such sort
     uint64_t split_launches = 0;        // trace launches that went out as two grids
-    std::vector<hipStream_t> low_streams;
-    std::vector<hipEvent_t> low_fork, low_join;
+    std::vector<Event> low_fork, low_join;   // with low_streams
 
     int morph_tile_lookup = 0;    // vxrt_debug_morph_tile_lookup: vxrt_morph_voxels_device asks the block's LDS tile before the whole array
 
     // touch map (vxrt_debug_touch_map; -DVXRT_VARIANTS=1 builds): one bit per 64-byte line of the node records / the leaf words
-    uint32_t* d_touch_nodes = nullptr;
-    uint32_t* d_touch_leaves = nullptr;
+    DeviceBuf<uint32_t> d_touch_nodes;
+    DeviceBuf<uint32_t> d_touch_leaves;
     size_t touch_node_lines = 0, touch_leaf_lines = 0;
     // the DDA prototype's grid of the scene in place (vxrt_debug_dda_rays; -DVXRT_VARIANTS=1 builds): bricks, brick bits, super-brick bits, first leaf per brick
-    void* dda_grid[4] = {nullptr, nullptr, nullptr, nullptr};
+    DeviceBuf<void> dda_grid[4];
     int dda_levels = 0;
 };
 
@@ -337,12 +334,17 @@ struct TracePlan {
     TileSort sort;             // how this launch re-sorts the stream's tiles when it is over
 };
 
-// a new scene: the touch maps were sized for the old one (vxrt_debug_touch_map)
-inline void drop_touch_maps(vxrt_ctx* c) {
-    for (uint32_t** p : {&c->d_touch_nodes, &c->d_touch_leaves}) { if (*p) (void)hipFree(*p); *p = nullptr; }
-    c->touch_node_lines = c->touch_leaf_lines = 0;
-    for (void*& g : c->dda_grid) { if (g) (void)hipFree(g); g = nullptr; }   // ... and so was the DDA prototype's grid
+// the DDA prototype's grid was built from records that are about to change, or have (vxrt_debug_dda_rays builds it again)
+inline void drop_dda_grid(vxrt_ctx* c) {
+    for (DeviceBuf<void>& g : c->dda_grid) g.reset();
     c->dda_levels = 0;
+}
+// a new scene: the touch maps were sized for the old one (vxrt_debug_touch_map), and so was the DDA prototype's grid
+inline void drop_touch_maps(vxrt_ctx* c) {
+    c->d_touch_nodes.reset();
+    c->d_touch_leaves.reset();
+    c->touch_node_lines = c->touch_leaf_lines = 0;
+    drop_dda_grid(c);
 }
 // a scene was just set (api_scene.hip): none of it comes from an edit
 inline void scene_replaced(vxrt_ctx* c) {
@@ -364,8 +366,6 @@ bool valid_ctx(const vxrt_ctx* c);
 float4* image_ptr(vxrt_ctx* c, vxrt_image which);
 bool is_display(vxrt_image which);                    // VXRT_DISPLAY_BGRA8_SRGB / VXRT_DISPLAY_RGBA8_SRGB
 size_t display_bytes(const vxrt_ctx* c);              // local_rows * width * 4
-// ---- api_extract.hip
-void free_extract(vxrt_ctx* c);
 // ---- api_scene.hip
 bool use_wide(const vxrt_ctx* c);
 // the smallest box of cells of tree level min(depth, 7) that holds every voxel; recs: the first records of the tree, breadth first,
@@ -374,9 +374,14 @@ bool scene_box(const SvoRecord* recs, size_t count, uint32_t depth, const float 
 // the same box for breadth-first records in device memory (root = svo[0]): reads the prefix back.  *valid as scene_box's result
 int device_scene_box(const SvoRecord* svo, size_t nsvo, uint32_t depth, SvoRecord root, const float root_center[3], float root_size, bool* valid,
                      float box_min[3], float box_max[3]);
-// device arrays built for the context become its scene (frees the old one; sets the counts, the sky cull's box, the node order)
-int install_scene(vxrt_ctx* c, SvoRecord* svo, size_t nsvo, int32_t* lw, size_t nlw, uint32_t depth, SvoRecord root, WideRec* wide,
-                  size_t nwide, WideRec wide_root);
+// The one way the scene's arrays are replaced: takes ownership of the new ones (any may be empty), releases the old, sets the counts,
+// and drops what was sized for or built from the old records (the touch maps, the DDA grid).  The root, the box, the capacities and
+// scene_replaced stay with the caller.
+void replace_scene_arrays(vxrt_ctx* c, DeviceBuf<SvoRecord>&& svo, size_t nsvo, DeviceBuf<int32_t>&& leaves, size_t nleaves, DeviceBuf<WideRec>&& wide,
+                          size_t nwide);
+// device arrays built for the context become its scene (sets the counts, the sky cull's box, the node order)
+int install_scene(vxrt_ctx* c, DeviceBuf<SvoRecord>&& svo, size_t nsvo, DeviceBuf<int32_t>&& lw, size_t nlw, uint32_t depth, SvoRecord root,
+                  DeviceBuf<WideRec>&& wide, size_t nwide, WideRec wide_root);
 int widen_svo(const std::vector<SvoRecord>& recs, uint32_t depth, std::vector<WideRec>* out);
 // ---- api_trace.hip
 int resize_tail_queues(vxrt_ctx* c, unsigned want);
@@ -391,7 +396,7 @@ int trace_frames(vxrt_ctx* c, uint32_t g, bool timed, int* slots, Cam* cams, Cam
 int check_render(vxrt_ctx* c, uint32_t flags);
 int post_stages(vxrt_ctx* c, uint32_t flags, bool timed);
 // ---- api_halo.hip
-void free_halo(vxrt_ctx* c);
+void free_halo(vxrt_ctx* c);            // the halo store and the tile rows, with their bookkeeping
 int build_tile_rows(vxrt_ctx* c);       // after the band map changed
 uint32_t halo_rows_wanted(const vxrt_ctx* c);   // rows per band edge the next exchange carries
 }  // namespace vxrt

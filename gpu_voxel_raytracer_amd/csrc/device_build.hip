@@ -446,11 +446,11 @@ int build_levels(uint64_t* ukeys, uint64_t* spare, size_t m, uint64_t* part, uin
         cur ^= 1;
     }
     SvoRecord root;
-    HIP_TRY(hipMemcpyAsync(&root, svo.p, sizeof root, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(&root, svo.get(), sizeof root, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
 
-    out->svo = svo.as<SvoRecord>(); out->svo_count = size_t(nodes); svo.p = nullptr;
-    out->leaves = leaves->as<int32_t>(); out->leaf_count = m; leaves->p = nullptr;
+    out->svo = static_cast<SvoRecord*>(svo.release()); out->svo_count = size_t(nodes);
+    out->leaves = static_cast<int32_t*>(leaves->release()); out->leaf_count = m;
     out->depth = depth;
     out->root = root;
     return VXRT_OK;
@@ -464,11 +464,11 @@ int build_empty_tree(hipStream_t s, const char* who, DeviceTree* out) {
     const int32_t zero = 0;
     if (int rc = alloc_scratch(&svo, sizeof root, who, "the records")) return rc;
     if (int rc = alloc_scratch(&leaves, sizeof zero, who, "the leaf words")) return rc;
-    HIP_TRY(hipMemcpyAsync(svo.p, &root, sizeof root, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(leaves.p, &zero, sizeof zero, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(svo.get(), &root, sizeof root, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(leaves.get(), &zero, sizeof zero, hipMemcpyHostToDevice, s));
     HIP_TRY(hipStreamSynchronize(s));
-    out->svo = svo.as<SvoRecord>(); out->svo_count = 1; svo.p = nullptr;
-    out->leaves = leaves.as<int32_t>(); out->leaf_count = 1; leaves.p = nullptr;
+    out->svo = static_cast<SvoRecord*>(svo.release()); out->svo_count = 1;
+    out->leaves = static_cast<int32_t*>(leaves.release()); out->leaf_count = 1;
     out->root = root;
     return VXRT_OK;
 }
@@ -488,7 +488,7 @@ int alloc_list_scratch(size_t n, bool with_vals, const char* who, ListScratch* l
 int sort_unique_list(ListScratch* ls, uint32_t n, uint32_t depth, ScratchBuffer* leaves, hipStream_t s, const char* who, size_t* m_out,
                      int* cur_out) {
     const uint32_t blocks = tiles(n);
-    const bool with_vals = ls->vals[0].p != nullptr;
+    const bool with_vals = ls->vals[0].get() != nullptr;
     // stable LSD radix sort over the key's 3(depth + 1) bits
     uint64_t* kp[2] = {ls->keys[0].as<uint64_t>(), ls->keys[1].as<uint64_t>()};
     uint32_t* vp[2] = {ls->vals[0].as<uint32_t>(), ls->vals[1].as<uint32_t>()};

@@ -7,10 +7,11 @@
 
 #include "../../include/vxrt_edit.h"
 #include "kernels.h"
+#include "owned.h"
 
 namespace vxrt {
 
-struct ScratchBuffer;   // ctx.h
+using ScratchBuffer = DeviceBuf<void>;   // ctx.h
 
 // A batch as edit_kernel walks it: the entries, sorted by octree path and one per position, cut into "segments" per tree level —
 // segment = one node on the path of at least one entry.  Node levels run 0 (the root: one segment) .. depth (the leaf parents);
@@ -70,13 +71,18 @@ struct ListBounds {
 int edit_keys_device(const int16_t* pos, const uint8_t* mrgb, size_t n, uint32_t depth, uint64_t* keys, uint32_t* vals, hipStream_t stream,
                      const char* who, ListBounds* out);
 
-// The storage for `svo_need` records and `leaf_need` leaf words: fresh arrays (*new_svo / *new_leaves, at the capacities *svo_grow /
-// *leaf_grow, holding the arrays in use and zeros after them) where the current ones are too small (x 1.5), nullptr where they are not.
-// Nothing changes in the context; nothing is left allocated on failure.  VXRT_E_SCENE: 2^32 records or leaf words.
-int grow_storage(vxrt_ctx* c, size_t svo_need, size_t leaf_need, SvoRecord** new_svo, int32_t** new_leaves, size_t* svo_grow,
-                 size_t* leaf_grow);
+// The storage for `svo_need` records and `leaf_need` leaf words: fresh arrays (at the capacities svo_cap / leaf_cap, holding the
+// arrays in use and zeros after them) where the current ones are too small (x 1.5), empty where they are not.
+// Nothing changes in the context; a failure, or a GrownStorage that is never committed, leaves nothing allocated.
+// VXRT_E_SCENE: 2^32 records or leaf words.
+struct GrownStorage {
+    DeviceBuf<SvoRecord> svo;
+    DeviceBuf<int32_t> leaves;
+    size_t svo_cap = 0, leaf_cap = 0;
+};
+int grow_storage(vxrt_ctx* c, size_t svo_need, size_t leaf_need, GrownStorage* g);
 // ... and the grown storage replaces the old
-void commit_storage(vxrt_ctx* c, SvoRecord* new_svo, int32_t* new_leaves, size_t svo_grow, size_t leaf_grow);
+void commit_storage(vxrt_ctx* c, GrownStorage&& g);
 
 // Room for a set batch with `nodes` segments on node levels 0 .. depth - 1 and `parents` leaf parents: the storage grows
 // (geometrically) when it has to.  VXRT_E_SCENE: 2^32 records or leaf words; VXRT_E_DEVICE: the storage could not grow (nothing

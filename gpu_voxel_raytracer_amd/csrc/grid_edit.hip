@@ -252,7 +252,7 @@ int cut_edit_lists(const uint64_t* const* lkeys, const uint32_t* m, int count, u
     ScratchBuffer part, segs;
     if (int rc = alloc_scratch(&part, part_bytes, who, "the level counts")) return rc;
     if (int rc = alloc_scratch(&segs, size_t(count) * 32 * sizeof(uint32_t), who, "the level counts")) return rc;
-    HIP_TRY(hipMemsetAsync(segs.p, 0, size_t(count) * 32 * sizeof(uint32_t), s));
+    HIP_TRY(hipMemsetAsync(segs.get(), 0, size_t(count) * 32 * sizeof(uint32_t), s));
     for (int b = 0; b < count; b++) {
         if (m[b] == 0) continue;
         uint64_t* p = reinterpret_cast<uint64_t*>(part.as<char>() + o_part[b]);
@@ -263,7 +263,7 @@ int cut_edit_lists(const uint64_t* const* lkeys, const uint32_t* m, int count, u
         HIP_TRY(hipGetLastError());
     }
     uint32_t seg_off[kMaxLists][32];
-    HIP_TRY(hipMemcpyAsync(seg_off, segs.p, size_t(count) * 32 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(seg_off, segs.get(), size_t(count) * 32 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
 
     // child_begin | oct of every list, then the edit kernel's scratch (node | flag | out), shared by the launches

@@ -37,8 +37,8 @@ struct OwnedSet {
     ScratchBuffer keys, words;
     MorphSet view{nullptr, nullptr, 0u};
     void take(OwnedSet* from) {      // what this held goes with `from`
-        std::swap(keys.p, from->keys.p);
-        std::swap(words.p, from->words.p);
+        keys.swap(from->keys);
+        words.swap(from->words);
         view = from->view;
     }
 };

@@ -85,7 +85,7 @@ inline int upload_palette(const uint8_t (*palette)[4], hipStream_t stream, const
         words[i] = 0x80000000u | (uint32_t(palette[i][0]) & 0x7fu) << 24 | uint32_t(palette[i][1]) << 16 | uint32_t(palette[i][2]) << 8 |
                    uint32_t(palette[i][3]);
     if (int rc = alloc_scratch(out, sizeof words, who, "the palette")) return rc;
-    HIP_TRY(hipMemcpyAsync(out->p, words, sizeof words, hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(out->get(), words, sizeof words, hipMemcpyHostToDevice, stream));
     return VXRT_OK;
 }
 

@@ -263,7 +263,7 @@ int build_menger_svo_device(uint32_t level, uint32_t clip, const uint8_t mrgb[4]
     }
     ScratchBuffer d_ones;
     if (int rc = alloc_scratch(&d_ones, ones.size() * sizeof(uint16_t), "menger", "the digit table")) return rc;
-    DEV_TRY(hipMemcpyAsync(d_ones.p, ones.data(), ones.size() * sizeof(uint16_t), hipMemcpyHostToDevice, stream));
+    DEV_TRY(hipMemcpyAsync(d_ones.get(), ones.data(), ones.size() * sizeof(uint16_t), hipMemcpyHostToDevice, stream));
     const SpongeDev sp{d_ones.as<uint16_t>(), side, mrgb[0], mrgb[1], mrgb[2], mrgb[3], emissive_period};
 
     // ---- sweep 1: dense masks, bottom-up.  Tree level l (1 .. depth) has cubes of side 2^(depth+1-l) and (2^(l-1))^3 potential nodes
@@ -283,14 +283,14 @@ int build_menger_svo_device(uint32_t level, uint32_t clip, const uint8_t mrgb[4]
     // level sizes: nodes of level l = non-empty entries of dense level l; leaf words = set bits of the last level
     ScratchBuffer d_totals;
     if (int rc = alloc_scratch(&d_totals, (depth + 1) * 2 * sizeof(unsigned long long), "menger", "the level totals")) return rc;
-    DEV_TRY(hipMemsetAsync(d_totals.p, 0, (depth + 1) * 2 * sizeof(unsigned long long), stream));
+    DEV_TRY(hipMemsetAsync(d_totals.get(), 0, (depth + 1) * 2 * sizeof(unsigned long long), stream));
     for (uint32_t l = 1; l <= depth; l++) {
         const size_t n3 = size_t(dim[l]) * dim[l] * dim[l];
         const unsigned blocks = unsigned(n3 / 256 < 1 ? 1 : (n3 / 256 > 4096 ? 4096 : n3 / 256));
         hipLaunchKernelGGL(dense_count_kernel, dim3(blocks), dim3(256), 0, stream, dense[l].as<uint8_t>(), n3, d_totals.as<unsigned long long>() + 2 * l);
     }
     std::vector<unsigned long long> totals((depth + 1) * 2);
-    DEV_TRY(hipMemcpyAsync(totals.data(), d_totals.p, totals.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
+    DEV_TRY(hipMemcpyAsync(totals.data(), d_totals.get(), totals.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
     DEV_TRY(hipStreamSynchronize(stream));
     size_t nodes = 1, max_level = 1;
     for (uint32_t l = 1; l <= depth; l++) { nodes += size_t(totals[2 * l]); max_level = size_t(totals[2 * l]) > max_level ? size_t(totals[2 * l]) : max_level; }
@@ -306,13 +306,13 @@ int build_menger_svo_device(uint32_t level, uint32_t clip, const uint8_t mrgb[4]
     if (int rc = alloc_scratch(&tile_sums, ((max_level + kScanTile - 1) / kScanTile + 1) * sizeof(uint32_t), "menger", "the scan partials")) return rc;
     // root: centre 0, everything lives in its slot 7 (x, y, z >= 0); its one child is record 1
     *root = SvoRecord{any ? 0x80u : 0u, 1u};
-    DEV_TRY(hipMemcpyAsync(svo.p, root, sizeof(SvoRecord), hipMemcpyHostToDevice, stream));
-    if (nleaves == 0) DEV_TRY(hipMemsetAsync(leaves.p, 0, sizeof(int32_t), stream));
+    DEV_TRY(hipMemcpyAsync(svo.get(), root, sizeof(SvoRecord), hipMemcpyHostToDevice, stream));
+    if (nleaves == 0) DEV_TRY(hipMemsetAsync(leaves.get(), 0, sizeof(int32_t), stream));
 
     // ---- sweep 2: top-down, level by level in breadth-first order
     if (any) {
         const uint32_t zero = 0;
-        DEV_TRY(hipMemcpyAsync(coords_a.p, &zero, sizeof zero, hipMemcpyHostToDevice, stream));   // level 1: the node at (0, 0, 0)
+        DEV_TRY(hipMemcpyAsync(coords_a.get(), &zero, sizeof zero, hipMemcpyHostToDevice, stream));   // level 1: the node at (0, 0, 0)
         uint32_t* cur = coords_a.as<uint32_t>();
         uint32_t* next = coords_b.as<uint32_t>();
         size_t first = 1;
@@ -331,35 +331,34 @@ int build_menger_svo_device(uint32_t level, uint32_t clip, const uint8_t mrgb[4]
         }
     }
     DEV_TRY(hipStreamSynchronize(stream));
-    *d_svo = svo.as<SvoRecord>(); svo.p = nullptr;
-    *d_leaves = leaves.as<int32_t>(); leaves.p = nullptr;
+    *d_svo = static_cast<SvoRecord*>(svo.release());
+    *d_leaves = static_cast<int32_t*>(leaves.release());
     *svo_count = nodes;
     *leaf_count = nleaves ? nleaves : 1;
     return VXRT_OK;
 }
 
 // Reorders the last `levels` (2 or 3) node levels of a breadth-first record array into depth-first treelets (see above).
-// level_first[l]: index of the first record of node level l (0 .. depth; level 0 is the root), n: records in all.  *d_svo is replaced.
-int reorder_bottom_treelets(SvoRecord** d_svo, size_t n, const std::vector<size_t>& level_first, uint32_t depth, int levels, hipStream_t stream) {
+// level_first[l]: index of the first record of node level l (0 .. depth; level 0 is the root), n: records in all.  *ordered: the new array.
+int reorder_bottom_treelets(const SvoRecord* svo, size_t n, const std::vector<size_t>& level_first, uint32_t depth, int levels, hipStream_t stream,
+                            DeviceBuf<SvoRecord>* ordered) {
     if ((levels != 2 && levels != 3) || depth < 4 || level_first.size() < size_t(depth) + 1 || n >= (size_t(1) << 32)) {
         set_error("treelets: 2 or 3 levels of a tree at least 4 levels deep");
         return VXRT_E_INVALID;
     }
     const uint32_t fp = uint32_t(level_first[depth - 3]), fa = uint32_t(level_first[depth - 2]), fb = uint32_t(level_first[depth - 1]), fc = uint32_t(level_first[depth]);
     if (!(fp < fa && fa < fb && fb < fc && fc < n)) { set_error("treelets: level starts out of order"); return VXRT_E_INVALID; }
-    ScratchBuffer out;
-    if (int rc = alloc_scratch(&out, n * sizeof(SvoRecord), "treelets", "the records")) return rc;
+    DeviceBuf<SvoRecord> out;
+    if (hipError_t e = out.alloc(n); e != hipSuccess) return alloc_failed(e, "treelets", "the records");
     const uint32_t keep = levels == 3 ? fp : fa;        // the levels above the treelets' parents: as they are
-    DEV_TRY(hipMemcpyAsync(out.p, *d_svo, size_t(keep) * sizeof(SvoRecord), hipMemcpyDeviceToDevice, stream));
+    DEV_TRY(hipMemcpyAsync(out, svo, size_t(keep) * sizeof(SvoRecord), hipMemcpyDeviceToDevice, stream));
     if (levels == 3)
-        hipLaunchKernelGGL(treelet_kernel<3>, dim3((fa - fp + 255u) / 256u), dim3(256), 0, stream, *d_svo, out.as<SvoRecord>(), fp, fa, fb, fc);
+        hipLaunchKernelGGL(treelet_kernel<3>, dim3((fa - fp + 255u) / 256u), dim3(256), 0, stream, svo, out.get(), fp, fa, fb, fc);
     else
-        hipLaunchKernelGGL(treelet_kernel<2>, dim3((fb - fa + 255u) / 256u), dim3(256), 0, stream, *d_svo, out.as<SvoRecord>(), fa, fa, fb, fc);
+        hipLaunchKernelGGL(treelet_kernel<2>, dim3((fb - fa + 255u) / 256u), dim3(256), 0, stream, svo, out.get(), fa, fa, fb, fc);
     DEV_TRY(hipGetLastError());
     DEV_TRY(hipStreamSynchronize(stream));
-    (void)hipFree(*d_svo);
-    *d_svo = out.as<SvoRecord>();
-    out.p = nullptr;
+    *ordered = std::move(out);
     return VXRT_OK;
 }
 

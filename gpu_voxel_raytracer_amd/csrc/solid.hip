@@ -279,7 +279,7 @@ int solid_pairs(const uint64_t* keys, uint32_t crossings, SolidKeying keying, ui
     const uint32_t at = first_split != kNone ? 2u * first_split : crossings - 1u;
     hipLaunchKernelGGL(solid_open_kernel, dim3(1), dim3(64), 0, s, keys, crossings, at, keying, found.as<SolidOpen>());
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(open, found.p, sizeof *open, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(open, found.get(), sizeof *open, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     return VXRT_OK;
 }

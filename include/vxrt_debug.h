@@ -151,6 +151,15 @@ int vxrt_debug_fused_profile(vxrt_ctx* ctx, uint64_t out[8]);
 int vxrt_debug_touch_map(vxrt_ctx* ctx, uint32_t enable);
 int vxrt_debug_touch_count(vxrt_ctx* ctx, uint64_t out[6], uint32_t reset);
 
+/* A prototype (-DVXRT_VARIANTS=1 builds only; VXRT_E_INVALID otherwise): `n` rays (origins, dirs: 3 floats each, HOST arrays) through
+ * the exact walk of the scene in place and through a three-level DDA over a bit grid built on the device from that scene on first use
+ * (kept until the scene's records change; a touch map the caller enabled stays).  flags: bit 0 the certificate, bit 1 the
+ * super-brick bits staged in LDS, bit 2 skip the walk, bit 3 skip the DDA.  max_steps: the DDA gives a ray up (flags it) beyond that.
+ * out_walk / out_dda: 8 floats per ray = hit, time, bits(leaf word), normal xyz, flagged, steps.  ms[0] the walk, ms[1] the DDA,
+ * ms[2] the grid's build (0 when it was there), ms[3] its bytes. */
+int vxrt_debug_dda_rays(vxrt_ctx* ctx, const float* origins, const float* dirs, size_t n, uint32_t flags, float margin_scale, uint32_t max_steps,
+                        float* out_walk, float* out_dda, double ms[4]);
+
 /* Measurement hook of vxrt_morph.h (scripts/morph_latency.py): enable = 1 makes vxrt_morph_voxels_device look a neighbour up in the
  * block's own 2 048 keys, staged in LDS, before it asks the whole key array (morph_mask_kernel<true>); the results are the same
  * bytes.  enable = 0 (the default) is the product's lookup, which asks the whole array at once: it measured faster. */

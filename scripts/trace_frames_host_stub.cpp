@@ -17,6 +17,13 @@ hipError_t hipEventQuery(hipEvent_t) STUB
 hipError_t hipEventSynchronize(hipEvent_t) STUB
 hipError_t hipMemcpyAsync(void*, const void*, size_t, hipMemcpyKind, hipStream_t) STUB
 hipError_t hipMemsetAsync(void*, int, size_t, hipStream_t) STUB
+// what the set-up below allocates through the context's owners (not counted: trace_frames allocates nothing)
+hipError_t hipMalloc(void** p, size_t n) { *p = calloc(n, 1); return hipSuccess; }
+hipError_t hipHostMalloc(void** p, size_t n, unsigned) { *p = calloc(n, 1); return hipSuccess; }
+hipError_t hipFree(void* p) { free(p); return hipSuccess; }
+hipError_t hipHostFree(void* p) { free(p); return hipSuccess; }
+hipError_t hipEventDestroy(hipEvent_t) { return hipSuccess; }
+hipError_t hipStreamDestroy(hipStream_t) { return hipSuccess; }
 }
 namespace vxrt {
 hipError_t launch_trace(const TraceArgs& a, bool, bool, hipStream_t, unsigned, unsigned) { TraceArgs b = a; g_calls = g_calls + b.batch; return hipSuccess; }   // the real one copies the arguments too
@@ -40,11 +47,9 @@ int main(int argc, char** argv) {
     c.trace_variant = tracer == 0 ? 4 : (tracer == 1 ? 0 : tracer); c.auto_tracer = tracer == 0;
     c.trace_streams.assign(size_t(inflight), nullptr);
     c.ring.resize(size_t(inflight) * g + 2);
-    c.schedules.resize(size_t(inflight)); c.launch_events.assign(size_t(inflight) * 2, nullptr); c.launch_event_turn.assign(size_t(inflight), 0u);
-    static unsigned counts[16][3 * 64 * 16]; static unsigned hostc[16][64 * 16]; static float4 q[64];
-    if (c.trace_variant) { c.queues.resize(size_t(inflight)); for (int i = 0; i < inflight; i++) { c.queues[i].counts3 = counts[i]; c.queues[i].host_counts = hostc[i]; c.queues[i].hitq[0] = q; } }
-    static uint4 fh[4];
-    if (g >= 2) c.first_hits.assign(size_t(inflight), fh);
+    c.schedules.resize(size_t(inflight)); c.launch_events.resize(size_t(inflight) * 2); c.launch_event_turn.assign(size_t(inflight), 0u);
+    if (c.trace_variant) { c.queues.resize(size_t(inflight)); for (int i = 0; i < inflight; i++) { (void)c.queues[i].counts3.alloc(3 * 64 * 16); (void)c.queues[i].host_counts.alloc(64 * 16); (void)c.queues[i].hitq[0].alloc(64); } }
+    if (g >= 2) { c.first_hits.resize(size_t(inflight)); for (auto& fh : c.first_hits) (void)fh.alloc(4); }
     c.shard_capacity = 64; c.shard_capacity_max = 64; c.svo_count = 1000; c.leaf_count = 1000; c.depth = 5;
     c.uniforms.sun_size = 0.05f; c.uniforms.sun_strength = 1; c.box_valid = true;
     int slots[32]; Cam cams[32], olds[32];

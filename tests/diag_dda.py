@@ -18,7 +18,7 @@ from gpu_voxel_raytracer_amd import Camera, Context, host, scenes  # noqa: E402
 
 
 def run(ctx, o, d, certify=1, margin=2.0, max_steps=600, lds_top=0, skip_walk=False, skip_dda=False):
-    """vxrt_debug_dda_rays (vxrt_debug.h is silent about it: a prototype of the -DVXRT_VARIANTS=1 build): the rays through the walk of the
+    """vxrt_debug_dda_rays (vxrt_debug.h: a prototype of the -DVXRT_VARIANTS=1 build): the rays through the walk of the
     context's scene format and through the DDA over the grid the library builds on the device from the scene in place.
     -> (walk results [n, 8], DDA results [n, 8], walk ms, DDA ms, grid build ms, grid bytes)"""
     o = np.ascontiguousarray(o, np.float32); d = np.ascontiguousarray(d, np.float32)
