@@ -37,6 +37,9 @@ void free_images(vxrt_ctx* c) {
     c->queues.clear();
     c->queue_bytes = 0;
     c->first_hits.clear();
+    c->first_hit_walked.clear();
+    c->first_hit_readers.clear();
+    c->first_hit_tag = vxrt_ctx::FirstHitTag{};
 }
 
 int alloc_images(vxrt_ctx* c) {
@@ -115,10 +118,14 @@ int alloc_images(vxrt_ctx* c) {
         }
     }
     // shared primary rays (VXRT_OPT_SHARED_PRIMARY): a stream's first-hit records, 16 bytes per pixel of the band; never read before
-    // first_hit_kernel has written them in the same launch, so they start uninitialised
+    // first_hit_kernel has written them in the same API call (api_trace.hip: plan_trace), so they start uninitialised.  With each
+    // buffer the event behind its walk, and who last read it on every stream.
     if (c->batch >= 2 && c->band.local_rows > 0) {
         c->first_hits.resize(size_t(c->inflight));
         for (DeviceBuf<uint4>& p : c->first_hits) HIP_TRY(p.alloc(size_t(c->band.local_rows) * size_t(c->band.width)));
+        c->first_hit_walked.resize(size_t(c->inflight));
+        for (Event& e : c->first_hit_walked) HIP_TRY(e.create(hipEventDisableTiming));
+        c->first_hit_readers.assign(size_t(c->inflight) * size_t(c->inflight), nullptr);
     }
     const size_t tiles = trace_tile_count(c->band.width, c->band.local_rows);
     c->schedules.resize(size_t(c->inflight));
@@ -314,7 +321,7 @@ int apply_option(vxrt_ctx* c, uint32_t option, uint32_t value, bool at_create) {
             c->frame_lanes = int(value);
             return VXRT_OK;
         case VXRT_OPT_SHARED_PRIMARY:
-            if (value > 1) { set_error("shared primary must be 0 or 1"); return VXRT_E_INVALID; }
+            if (value > 2) { set_error("shared primary must be 0 (off), 1 (one walk per launch) or 2 (one walk per call)"); return VXRT_E_INVALID; }
             c->shared_primary = int(value);
             return VXRT_OK;
         case VXRT_OPT_HALO_ROWS:
@@ -817,6 +824,7 @@ int vxrt_reset_stats(vxrt_ctx* c) try {
     c->halo_exchanges = 0;
     c->frame_lane_launches = 0;
     c->shared_primary_launches = 0;
+    c->first_hit_walks = 0;
     c->split_launches = 0;
     return VXRT_OK;
 } VXRT_CATCH

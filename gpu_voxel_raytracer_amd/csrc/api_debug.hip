@@ -169,7 +169,7 @@ int vxrt_debug_culled_pixels(vxrt_ctx* c, uint64_t* count) try {
     frame_constants(c, a);
     a.cam = c->cam;
     a.batch = 1;
-    set_cull(c, a, &a.cam, 1);
+    set_cull(a, cull_box(c, &a.cam, 1));
     c->cam = keep_cam; c->old_cam = keep_old; c->uniforms = keep_u;
     ScratchBuffer b;
     HIP_TRY(b.alloc(sizeof(unsigned long long)));
@@ -185,6 +185,12 @@ int vxrt_debug_culled_pixels(vxrt_ctx* c, uint64_t* count) try {
 int vxrt_debug_shared_primary_launches(vxrt_ctx* c, uint64_t* count) try {
     if (!valid_ctx(c) || !count) { set_error("null argument"); return VXRT_E_INVALID; }
     *count = c->shared_primary_launches;
+    return VXRT_OK;
+} VXRT_CATCH
+
+int vxrt_debug_first_hit_walks(vxrt_ctx* c, uint64_t* count) try {
+    if (!valid_ctx(c) || !count) { set_error("null argument"); return VXRT_E_INVALID; }
+    *count = c->first_hit_walks;
     return VXRT_OK;
 } VXRT_CATCH
 

@@ -149,6 +149,7 @@ extern "C" {
 int vxrt_render(vxrt_ctx* c, uint32_t flags) try {
     if (int rc = check_render(c, flags)) return rc;
     HIP_TRY(hipSetDevice(c->cfg.device));
+    c->call_id++;   // a new call scope: first-hit records of earlier calls are nobody's (ctx.h: first_hit_tag)
     const bool timed = (flags & VXRT_TIMED) != 0;
     if (flags & VXRT_TRACE) {
         int slot = 0;
@@ -196,6 +197,7 @@ static int render_sequence(vxrt_ctx* c, uint32_t flags, uint32_t count, const fl
 int vxrt_render_frames(vxrt_ctx* c, uint32_t flags, uint32_t count) try {
     if (int rc = check_render(c, flags)) return rc;
     HIP_TRY(hipSetDevice(c->cfg.device));
+    c->call_id++;
     return render_sequence(c, flags, count, nullptr, nullptr);
 } VXRT_CATCH
 
@@ -205,6 +207,7 @@ int vxrt_render_path(vxrt_ctx* c, uint32_t flags, uint32_t count, const float (*
     if (int rc = check_render(c, flags)) return rc;
     if (!positions || !directions) { set_error("null argument"); return VXRT_E_INVALID; }
     HIP_TRY(hipSetDevice(c->cfg.device));
+    c->call_id++;
     c->cam_fov = fov;
     return render_sequence(c, flags, count, positions, directions);
 } VXRT_CATCH
@@ -216,6 +219,7 @@ int vxrt_render_spp(vxrt_ctx* c, uint32_t flags, uint32_t spp) try {
     if (int rc = check_render(c, flags)) return rc;
     if (!(flags & VXRT_TRACE) || spp == 0 || spp > 4096) { set_error("vxrt_render_spp needs VXRT_TRACE and 1 <= spp <= 4096"); return VXRT_E_INVALID; }
     HIP_TRY(hipSetDevice(c->cfg.device));
+    c->call_id++;
     const bool timed = (flags & VXRT_TIMED) != 0;
     const size_t pixels = size_t(c->band.local_rows) * c->band.width;
     if (spp > 1 && c->spp_sum == nullptr && pixels > 0) HIP_TRY(c->spp_sum.alloc(pixels));

@@ -116,8 +116,8 @@ void frame_constants(const vxrt_ctx* c, TraceArgs& a) {
 // Sky cull: the scene's box grown by a margin m that dwarfs every rounding error of the walk and of the test itself.  The walk
 // visits a cell only if the ray passes within ~2^-21 (|origin| + root_size) of it (its plane times are fl(fl(p - o) * inv): two
 // roundings of quantities no larger than that); m = 0.01 + 2^-16 (max |origin| + 2 root_size) is at least 32 times as much.
-void set_cull(const vxrt_ctx* c, TraceArgs& a, const Cam* cams, uint32_t g) {
-    a.cull = 0;
+CullBox cull_box(const vxrt_ctx* c, const Cam* cams, uint32_t g) {
+    CullBox b;
     if (c->sky_cull && c->box_valid) {
         float far = 0.0f;
         bool sane = true;
@@ -129,10 +129,16 @@ void set_cull(const vxrt_ctx* c, TraceArgs& a, const Cam* cams, uint32_t g) {
             }
         if (sane) {
             const float m = 0.01f + ldexpf(far + 2.0f * c->root_size, -16);
-            for (int i = 0; i < 3; i++) { a.cull_min[i] = c->box_min[i] - m; a.cull_max[i] = c->box_max[i] + m; }
-            a.cull = 1;
+            for (int i = 0; i < 3; i++) { b.lo[i] = c->box_min[i] - m; b.hi[i] = c->box_max[i] + m; }
+            b.on = 1;
         }
     }
+    return b;
+}
+
+void set_cull(TraceArgs& a, const CullBox& b) {
+    a.cull = b.on;
+    for (int i = 0; i < 3; i++) { a.cull_min[i] = b.lo[i]; a.cull_max[i] = b.hi[i]; }
 }
 
 // VXRT_OPT_XCD_AFFINITY (round 6's experiment for scenes that live in HBM, BASELINE config 5): a launch order in which the tiles that
@@ -217,9 +223,10 @@ struct CountSets {
     unsigned* cleared() const { return sets[(J + 2) % 3]; }
 };
 
-// one launch: what its steps share.  plan, a and counts are filled by the steps named after them, in that order
+// one launch: what its steps share.  cull, plan, a and counts are filled by the steps named after them, in that order
 struct TraceLaunch {
     vxrt_ctx* c; hipStream_t ts; size_t lane; uint32_t g; const int* slots;
+    CullBox cull{};     // the launch's sky cull (cull_box), as the plan compared it and the kernels get it
     TracePlan plan{};
     TraceArgs a;
     CountSets counts;   // the stream's counter sets as this launch finds them (tracers with queues)
@@ -252,7 +259,8 @@ static float path_motion_px(const vxrt_ctx* c, uint32_t g, uint32_t F, const flo
 
 // Everything a launch of g frames on stream `lane` will do, decided here and nowhere else, into p (all zero on entry).  Calls no HIP API and changes nothing: it
 // reads the context as absorb_feedback left it (tail capacity, walking-tile count), the launch's cameras and the optional path poses.
-static void plan_trace(TracePlan& p, const vxrt_ctx* c, uint32_t g, const Cam* cams, const float (*path_pos)[3], const float (*path_dir)[3], size_t lane) {
+static void plan_trace(TracePlan& p, const vxrt_ctx* c, uint32_t g, const Cam* cams, const CullBox& cull, const float (*path_pos)[3], const float (*path_dir)[3],
+                       size_t lane) {
     const bool wide = use_wide(c);
     const vxrt_ctx::TileSchedule& sched = c->schedules[lane];
     const bool ordered = c->use_tile_order && sched.valid;
@@ -283,11 +291,23 @@ static void plan_trace(TracePlan& p, const vxrt_ctx* c, uint32_t g, const Cam* c
     if (p.frame_lanes && path_pos != nullptr && !(path_motion_px(c, g, uint32_t(p.frame_lanes), path_pos, path_dir) <= 16.0f)) p.frame_lanes = 0;
     // Shared primary rays (VXRT_OPT_SHARED_PRIMARY): when every frame of the launch has the camera of the first — decided by
     // comparing the cameras, not by who called — first_hit_kernel walks the band's primary rays once, ahead of trace_kernel on
-    // this stream and inside the timed region, and trace_kernel's lanes load their pixel's record instead of casting.  The
-    // records belong to this launch alone: the next launch on the stream writes them again before it reads them.  Not for the
+    // this stream and inside the timed region, and trace_kernel's lanes load their pixel's record instead of casting.  Not for the
     // wide records, nor for a scene beyond the Infinity Cache (its kernel stays as measured: DESIGN.md section 5).
     p.share = trace_kernel_head && c->shared_primary && g >= 2 && lane < c->first_hits.size() && c->first_hits[lane] != nullptr && !wide && !p.hbm;
     for (uint32_t k = 1; p.share && k < g; k++) p.share = memcmp(&cams[k], &cams[0], sizeof(Cam)) == 0;
+    // Option 1: the records belong to this launch alone.  Option 2: to the API call — a launch that shares walks only when no
+    // earlier launch of this call has walked the same rays.  The records are a function of the camera, the cull state (a culled
+    // lane writes no record, and trace_block reads one exactly when its own cull test fails: walker and reader must cull alike),
+    // the band and the scene.  The first two are compared here; band and scene cannot change inside an API call, and the tag's call
+    // id says the walk was this call's — nothing is kept from one call to the next, so no setter has to invalidate anything.
+    p.walk = p.share;
+    p.hits = lane;
+    const vxrt_ctx::FirstHitTag& tag = c->first_hit_tag;
+    if (p.share && c->shared_primary == 2 && tag.call != 0 && tag.call == c->call_id && tag.buffer < c->first_hits.size() &&
+        memcmp(&tag.cam, &cams[0], sizeof(Cam)) == 0 && tag.cull == cull) {
+        p.walk = false;
+        p.hits = tag.buffer;
+    }
     // (-DVXRT_VARIANTS=1 only: measured slower — the rest of the tiles are as chain-bound as the longest.)  The longest tiles apart
     // (VXRT_OPT_LONG_TILES, per mille of the tiles): the first tiles of the launch order — the longest chains of the last frames — run
     // as an all-in-one grid of their own on a second stream (fork_long_tiles), beside the head + tail pair of all other tiles.
@@ -364,7 +384,7 @@ static void fill_trace_args(TraceLaunch& L, const Cam* cams, uint32_t gbuf_frame
     a.batch = int(g);
     a.gbuf_frames = gbuf_frames;
     a.frame_lanes = L.plan.frame_lanes;
-    set_cull(c, a, cams, g);
+    set_cull(a, L.cull);
     a.ray_counter = c->d_rays;
     a.tile_order = (c->use_tile_order && sched.valid) ? sched.order : nullptr;
     a.tile_cost = c->use_tile_order ? sched.cost : nullptr;
@@ -440,12 +460,38 @@ static int fork_long_tiles(TraceLaunch& L) {
 }
 
 // The all-in-one launch, and the head of a head + tail pair: the long tiles' grid (its arguments are copied before the first hits are
-// set: it casts its own), first_hit_kernel when the launch shares its primary rays, trace_kernel.
+// set: it casts its own), the first hits when the launch shares its primary rays — its own walk or an earlier one's — trace_kernel.
 static int issue_head(TraceLaunch& L) {
+    vxrt_ctx* c = L.c;
     if (L.plan.long_blocks != 0u) { if (int rc = fork_long_tiles(L)) return rc; }
     if (L.plan.share) {
-        L.a.first_hit = L.c->first_hits[L.lane];
-        HIP_TRY(launch_first_hit(L.a, L.ts));
+        const size_t b = L.plan.hits, streams = c->trace_streams.size();
+        vxrt_ctx::FirstHitTag& tag = c->first_hit_tag;
+        L.a.first_hit = c->first_hits[b];
+        if (L.plan.walk) {
+            // The walk overwrites buffer b (b == this stream).  Who may still be reading it?  Launches of this stream are over
+            // before the walk starts: the stream's order.  A launch of another stream s that read b noted its event in
+            // first_hit_readers (finish_launch), and launches of s are ordered among themselves, so waiting for the LAST reader on
+            // each s covers all of them.  Those events were recorded before this call to hipStreamWaitEvent, by this thread: the
+            // wait cannot refer to work not yet issued, and it costs the host nothing.  (A launch_events entry is recorded again two
+            // launches later on its stream; the wait then covers that later launch as well — more than needed, never less.)
+            for (size_t s = 0; s < streams; s++) {
+                hipEvent_t& reader = c->first_hit_readers[b * streams + s];
+                if (reader != nullptr && s != L.lane) HIP_TRY(hipStreamWaitEvent(L.ts, reader, 0));
+                reader = nullptr;
+            }
+            tag.call = 0;   // the tagged records are overwritten now, or are superseded below, or were another call's
+            HIP_TRY(launch_first_hit(L.a, L.ts));
+            if (c->shared_primary == 2) {
+                HIP_TRY(hipEventRecord(c->first_hit_walked[b], L.ts));
+                tag.call = c->call_id;
+                tag.buffer = b;
+                tag.cam = L.a.cams[0];
+                tag.cull = L.cull;
+            }
+        } else if (b != L.lane) {
+            HIP_TRY(hipStreamWaitEvent(L.ts, c->first_hit_walked[b], 0));   // the walker's own stream needs no wait
+        }
     }
     return issue_trace_kernel(L);
 }
@@ -591,7 +637,11 @@ static int finish_launch(TraceLaunch& L, bool timed) {
     c->accum_is_sampled = true;
     c->halo_valid = false;
     if (L.plan.frame_lanes) c->frame_lane_launches++;
-    if (L.plan.share) c->shared_primary_launches++;
+    if (L.plan.share) {
+        c->shared_primary_launches++;
+        c->first_hit_readers[L.plan.hits * c->trace_streams.size() + lane] = done;   // issue_head: the next walk into that buffer waits for it
+    }
+    if (L.plan.walk) c->first_hit_walks++;
     if (L.plan.split_heavy) c->split_launches++;
     return VXRT_OK;
 }
@@ -612,7 +662,8 @@ int trace_frames(vxrt_ctx* c, uint32_t g, bool timed, int* slots, Cam* cams, Cam
     TraceLaunch L(c, ts, lane, g, slots);
     if (c->band.local_rows > 0) {
         if (int rc = absorb_feedback(c, lane)) return rc;
-        plan_trace(L.plan, c, g, cams, path_pos, path_dir, lane);
+        L.cull = cull_box(c, cams, g);
+        plan_trace(L.plan, c, g, cams, L.cull, path_pos, path_dir, lane);
         fill_trace_args(L, cams, gbuf_frames, first_frame_number);
         EventPair p;
         if (timed) { p = take_pair(c, 0); HIP_TRY(hipEventRecord(p.a, ts)); }

@@ -96,6 +96,13 @@ struct EventPair {   // handles, not owned: the events live in vxrt_ctx::pair_ev
     hipEvent_t a = nullptr, b = nullptr;
     int stage = 0;  // 0 trace, 1 temporal, 2 denoise, 3 halo pack, 4 halo unpack
 };
+
+// the sky cull of a launch as the kernels get it (TraceArgs::cull, cull_min, cull_max; api_trace.hip: cull_box)
+struct CullBox {
+    int on = 0;
+    float lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
+    bool operator==(const CullBox& o) const { return on == o.on && (on == 0 || (memcmp(lo, o.lo, sizeof lo) == 0 && memcmp(hi, o.hi, sizeof hi) == 0)); }
+};
 }  // namespace vxrt
 
 using namespace vxrt;
@@ -269,10 +276,29 @@ struct vxrt_ctx {
     unsigned wave_slots = 5120;   // waves of trace_kernel the device holds at once: CUs x 4 SIMDs x 5 (vxrt_create)
     int frame_lanes = 1;   // trace_kernel may put 8 frames of a pixel row into a wave (TraceArgs::frame_lanes; VXRT_OPT_FRAME_LANES)
     uint32_t frame_lane_launches = 0;
-    // VXRT_OPT_SHARED_PRIMARY: a launch of >= 2 frames of ONE camera walks each pixel's primary ray once (trace.hip: first_hit_kernel).
-    int shared_primary = 1;
-    uint64_t shared_primary_launches = 0;   // vxrt_debug_shared_primary_launches
+    // VXRT_OPT_SHARED_PRIMARY: a launch of >= 2 frames of ONE camera takes each pixel's first hit from a record (trace.hip:
+    // first_hit_kernel).  1: every such launch walks the primary rays itself; 2: one walk per API call serves all its launches that
+    // have the walk's camera and cull state (first_hit_tag)
+    int shared_primary = 2;
+    uint64_t shared_primary_launches = 0;   // vxrt_debug_shared_primary_launches: launches that took their first hits from records
+    uint64_t first_hit_walks = 0;           // vxrt_debug_first_hit_walks: launches of first_hit_kernel
     std::vector<DeviceBuf<uint4>> first_hits;         // per trace stream: one 16-byte record per pixel of the band (contexts with frames_per_launch >= 2)
+    std::vector<Event> first_hit_walked;              // per buffer of first_hits: recorded behind the walk that filled it (option 2)
+    // [buffer * inflight + stream]: the event (a handle to one of launch_events, or null) of the last launch on `stream` that read
+    // `buffer` and that no later walk into the buffer has waited for yet
+    std::vector<hipEvent_t> first_hit_readers;
+    // The API call in progress: bumped on entry by vxrt_render, vxrt_render_frames, vxrt_render_path and vxrt_render_spp.  Neither the
+    // scene nor the band nor an option can change inside one, so what a launch of the call computed from them holds for the call's rest.
+    uint64_t call_id = 0;
+    // What the records of the last walk under option 2 were made from.  They are valid for the call that made them only: no mutator
+    // of the scene, the camera or an option has to know of them.
+    struct FirstHitTag {
+        uint64_t call = 0;      // call_id of the walk (0: no records)
+        size_t buffer = 0;      // index into first_hits = the trace stream that walked
+        Cam cam{};              // the camera the rays were made from
+        CullBox cull{};         // the sky cull the walk used: a culled lane wrote no record
+    };
+    FirstHitTag first_hit_tag;
     int path_blocks = 512;  // tracer 5: blocks of path_kernel (each wave takes an equal range of the queue, >= 512 paths)
     int tail_from = 1;  // tracer 4: the hit number at which live paths move to the compacted launches
     unsigned tail_split = 0;  // ... bit k: the tail compacts again and starts a new launch at path segment k
@@ -327,7 +353,9 @@ struct TracePlan {
     int tracer;                // the tracer that really runs: 0 where auto falls back to the all-in-one kernel, else vxrt_ctx::trace_variant
     TracePath path;
     int frame_lanes;           // frames a wave of the head holds, as the kernel really uses it (TraceArgs::frame_lanes): 8, 4 or 0
-    bool share;                // first_hit_kernel walks the primary rays once for all frames
+    bool share;                // the frames take their first hits from records (vxrt_ctx::first_hits[hits]) ...
+    bool walk;                 // ... which this launch's own first_hit_kernel writes; false: an earlier launch of the call has
+    size_t hits;               // the buffer of the records: this launch's stream when it walks, else the stream that did
     unsigned long_blocks;      // blocks of the longest tiles that go out as a grid of their own (0: none); the head starts behind them
     bool single_tail_launch;   // the tail is exactly one launch: the counter copy-back goes behind it
     unsigned split_heavy;      // priority split: the first split_heavy tiles of the order on the trace stream, the rest on the low-priority one (0: one grid)
@@ -386,7 +414,8 @@ int widen_svo(const std::vector<SvoRecord>& recs, uint32_t depth, std::vector<Wi
 // ---- api_trace.hip
 int resize_tail_queues(vxrt_ctx* c, unsigned want);
 int apply_option(vxrt_ctx* c, uint32_t option, uint32_t value, bool at_create);   // api_context.hip
-void set_cull(const vxrt_ctx* c, TraceArgs& a, const Cam* cams, uint32_t g);       // api_trace.hip
+CullBox cull_box(const vxrt_ctx* c, const Cam* cams, uint32_t g);                  // api_trace.hip
+void set_cull(TraceArgs& a, const CullBox& b);
 int grow_tail_queues(vxrt_ctx* c, size_t lane);
 void update_bindings(vxrt_ctx* c);
 void frame_constants(const vxrt_ctx* c, TraceArgs& a);

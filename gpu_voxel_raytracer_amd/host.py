@@ -1622,6 +1622,12 @@ class Context:
         self._chk(self._L.vxrt_debug_shared_primary_launches(self._h, C.byref(n)), "vxrt_debug_shared_primary_launches")
         return int(n.value)
 
+    def first_hit_walks(self):
+        """vxrt_debug_first_hit_walks: launches of the first-hit kernel (OPT_SHARED_PRIMARY 1: one per sharing launch; 2: one per call and camera)."""
+        n = C.c_uint64(0)
+        self._chk(self._L.vxrt_debug_first_hit_walks(self._h, C.byref(n)), "vxrt_debug_first_hit_walks")
+        return int(n.value)
+
     def set_option(self, option, value):
         """vxrt_set_option: OPT_DENOISE_MODE (0 exact, 1 tolerant), OPT_TAIL_CAPACITY (records per queue shard; 0 = automatic)."""
         self._chk(self._L.vxrt_set_option(self._h, C.c_int(option), C.c_uint32(value)), "vxrt_set_option")

@@ -239,14 +239,18 @@ typedef struct vxrt_stats {
  *                          instead of an 8 x 8 tile of one frame — the same per-pixel operations, more coherent waves (a pixel's primary
  *                          ray is the same in every frame).  0: always one frame per wave.  vxrt_stats.frame_lane_launches counts the
  *                          former.  Not used for scenes beyond the Infinity Cache (measured slower there).
- *   VXRT_OPT_SHARED_PRIMARY 1 (default): a trace launch of 2 or more frames that all have the SAME camera (vxrt_render_frames /
+ *   VXRT_OPT_SHARED_PRIMARY 1: a trace launch of 2 or more frames that all have the SAME camera (vxrt_render_frames /
  *                          vxrt_render_spp, or a vxrt_render_path whose poses give bytewise equal cameras) walks each pixel's primary
  *                          ray once: a first-hit kernel, one wave per 8 x 8 pixel tile, runs ahead of the trace kernel on the same
  *                          stream, and every frame of the launch takes its pixel's first hit from that kernel's record instead of
  *                          casting the ray again (the same ray through the same walk: the same hit, bit for bit; vxrt_stats.rays
- *                          counts the primary ray per frame as before).  Nothing is kept between launches.  0: every frame casts
- *                          its own primary rays — exactly the launches of earlier versions.  Not used for scenes beyond the
- *                          Infinity Cache.  vxrt_debug.h: vxrt_debug_shared_primary_launches counts the launches that shared.
+ *                          counts the primary ray per frame as before).  Nothing is kept between launches.
+ *                          2 (default): as 1, and the walk is made once per API CALL: a later launch of the same vxrt_render_frames /
+ *                          vxrt_render_spp / vxrt_render_path call with the same camera reads the records of the call's first walk
+ *                          (on another stream: behind an event).  Nothing is kept between calls.
+ *                          0: every frame casts its own primary rays — exactly the launches of earlier versions.  Not used for scenes
+ *                          beyond the Infinity Cache.  vxrt_debug.h: vxrt_debug_shared_primary_launches counts the launches that took
+ *                          their first hits from records, vxrt_debug_first_hit_walks the walks.
  *
  */
 typedef enum vxrt_option { VXRT_OPT_DENOISE_MODE = 1, VXRT_OPT_TAIL_CAPACITY = 2, VXRT_OPT_SCENE_FORMAT = 3, VXRT_OPT_HALO_ROWS = 4,

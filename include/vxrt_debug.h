@@ -138,6 +138,10 @@ int vxrt_debug_culled_pixels(vxrt_ctx* ctx, uint64_t* count);
  * (vxrt.h: VXRT_OPT_SHARED_PRIMARY).  In the frames of such a launch after the first, a pixel that is not culled has its primary
  * ray counted in vxrt_stats.rays without a walk of its own. */
 int vxrt_debug_shared_primary_launches(vxrt_ctx* ctx, uint64_t* count);
+/* Diagnostics: launches of the first-hit kernel since create / vxrt_reset_stats — the walks of the primary rays that really went out.
+ * VXRT_OPT_SHARED_PRIMARY 1: one per launch that shared; 2: one per API call (vxrt_render_frames, vxrt_render_spp, vxrt_render_path)
+ * and camera, however many of the call's launches shared it; 0: none. */
+int vxrt_debug_first_hit_walks(vxrt_ctx* ctx, uint64_t* count);
 /* Diagnostics of trace stream 0's last fused launch (VXRT_OPT_FUSED_TAIL): shader clocks to "every head block finished" and to the last
  * wave's end, chunks taken before / after that moment, idle sleeps, stamp polls, head claims, 0. */
 int vxrt_debug_fused_profile(vxrt_ctx* ctx, uint64_t out[8]);

@@ -49,7 +49,7 @@ int main(int argc, char** argv) {
     c.ring.resize(size_t(inflight) * g + 2);
     c.schedules.resize(size_t(inflight)); c.launch_events.resize(size_t(inflight) * 2); c.launch_event_turn.assign(size_t(inflight), 0u);
     if (c.trace_variant) { c.queues.resize(size_t(inflight)); for (int i = 0; i < inflight; i++) { (void)c.queues[i].counts3.alloc(3 * 64 * 16); (void)c.queues[i].host_counts.alloc(64 * 16); (void)c.queues[i].hitq[0].alloc(64); } }
-    if (g >= 2) { c.first_hits.resize(size_t(inflight)); for (auto& fh : c.first_hits) (void)fh.alloc(4); }
+    if (g >= 2) { c.first_hits.resize(size_t(inflight)); for (auto& fh : c.first_hits) (void)fh.alloc(4); c.first_hit_walked.resize(size_t(inflight)); c.first_hit_readers.assign(size_t(inflight) * size_t(inflight), nullptr); }
     c.shard_capacity = 64; c.shard_capacity_max = 64; c.svo_count = 1000; c.leaf_count = 1000; c.depth = 5;
     c.uniforms.sun_size = 0.05f; c.uniforms.sun_strength = 1; c.box_valid = true;
     int slots[32]; Cam cams[32], olds[32];
