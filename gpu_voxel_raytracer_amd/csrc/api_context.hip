@@ -40,6 +40,9 @@ void free_images(vxrt_ctx* c) {
     c->first_hit_walked.clear();
     c->first_hit_readers.clear();
     c->first_hit_tag = vxrt_ctx::FirstHitTag{};
+    c->tile_sky.clear();
+    c->walk_lists.clear();
+    c->sky_count = vxrt_ctx::SkyCount{};
 }
 
 int alloc_images(vxrt_ctx* c) {
@@ -126,7 +129,23 @@ int alloc_images(vxrt_ctx* c) {
         c->first_hit_walked.resize(size_t(c->inflight));
         for (Event& e : c->first_hit_walked) HIP_TRY(e.create(hipEventDisableTiming));
         c->first_hit_readers.assign(size_t(c->inflight) * size_t(c->inflight), nullptr);
+        // sky once (VXRT_OPT_SKY_ONCE): beside each buffer of records the walk's flag per 8 x 8 tile, and per stream the list of the tiles
+        // that walk; one pinned pair for the walk's numbers.  Never read before a walk of the same API call has written them.
+        const size_t tiles8 = size_t(c->band.width + 7) / 8 * (size_t(c->band.local_rows + 7) / 8);
+        c->tile_sky.resize(size_t(c->inflight));
+        for (DeviceBuf<uint32_t>& p : c->tile_sky) HIP_TRY(p.alloc(tiles8));
+        c->walk_lists.resize(size_t(c->inflight));
+        for (vxrt_ctx::WalkList& wl : c->walk_lists) {
+            HIP_TRY(wl.order.alloc(tiles8 + 1));
+            HIP_TRY(wl.partial.alloc(2 * kSortBlocks + 2));
+        }
+        HIP_TRY(c->sky_count.host.alloc(64 / sizeof(unsigned)));
+        c->sky_count.host[0] = c->sky_count.host[1] = 0u;
+        HIP_TRY(c->sky_count.ready.create(hipEventDisableTiming));
     }
+    int tile_w = 0, tile_h = 0;
+    trace_tile_dims(&tile_w, &tile_h);
+    c->sky_tiles = tile_w == 8 && tile_h == 8;
     const size_t tiles = trace_tile_count(c->band.width, c->band.local_rows);
     c->schedules.resize(size_t(c->inflight));
     for (vxrt_ctx::TileSchedule& t : c->schedules) {
@@ -323,6 +342,10 @@ int apply_option(vxrt_ctx* c, uint32_t option, uint32_t value, bool at_create) {
         case VXRT_OPT_SHARED_PRIMARY:
             if (value > 2) { set_error("shared primary must be 0 (off), 1 (one walk per launch) or 2 (one walk per call)"); return VXRT_E_INVALID; }
             c->shared_primary = int(value);
+            return VXRT_OK;
+        case VXRT_OPT_SKY_ONCE:
+            if (value > 1) { set_error("sky once must be 0 or 1"); return VXRT_E_INVALID; }
+            c->sky_once = int(value);
             return VXRT_OK;
         case VXRT_OPT_HALO_ROWS:
             if (value > 4096) { set_error("halo rows must be 0..4096"); return VXRT_E_INVALID; }
@@ -781,7 +804,7 @@ int vxrt_get_stats(vxrt_ctx* c, vxrt_stats* out) try {
     for (size_t i = 0; i < slots.size(); i += 8) rays += slots[i];
     memset(out, 0, sizeof *out);
     out->frames = c->frames;
-    out->rays = rays;
+    out->rays = rays + c->sky_rays;   // the primary rays of pixels that thin launches left out are on the host's books (VXRT_OPT_SKY_ONCE)
     out->pixels = c->pixels;
     out->trace_ms = c->ms[0];
     out->temporal_ms = c->ms[1];
@@ -826,6 +849,9 @@ int vxrt_reset_stats(vxrt_ctx* c) try {
     c->shared_primary_launches = 0;
     c->first_hit_walks = 0;
     c->split_launches = 0;
+    c->sky_rays = 0;
+    c->thin_launches = 0;
+    c->trace_kernel_blocks = 0;
     return VXRT_OK;
 } VXRT_CATCH
 

@@ -194,6 +194,18 @@ int vxrt_debug_first_hit_walks(vxrt_ctx* c, uint64_t* count) try {
     return VXRT_OK;
 } VXRT_CATCH
 
+int vxrt_debug_thin_launches(vxrt_ctx* c, uint64_t* count) try {
+    if (!valid_ctx(c) || !count) { set_error("null argument"); return VXRT_E_INVALID; }
+    *count = c->thin_launches;
+    return VXRT_OK;
+} VXRT_CATCH
+
+int vxrt_debug_trace_blocks(vxrt_ctx* c, uint64_t* count) try {
+    if (!valid_ctx(c) || !count) { set_error("null argument"); return VXRT_E_INVALID; }
+    *count = c->trace_kernel_blocks;
+    return VXRT_OK;
+} VXRT_CATCH
+
 // PROTOTYPE (csrc/trace_dda.hip; -DVXRT_VARIANTS=1 builds only): the same rays through the exact walk (cast_probe_kernel over the
 // context's scene format) and through the three-level DDA over a bit grid that is built on the device from the scene in place (first
 // call; kept until the scene changes), both timed with HIP events (the second of two launches each).  flags: bit 0 = the certificate,

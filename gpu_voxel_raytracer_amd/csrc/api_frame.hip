@@ -150,6 +150,7 @@ int vxrt_render(vxrt_ctx* c, uint32_t flags) try {
     if (int rc = check_render(c, flags)) return rc;
     HIP_TRY(hipSetDevice(c->cfg.device));
     c->call_id++;   // a new call scope: first-hit records of earlier calls are nobody's (ctx.h: first_hit_tag)
+    c->call_frames = 1;
     const bool timed = (flags & VXRT_TIMED) != 0;
     if (flags & VXRT_TRACE) {
         int slot = 0;
@@ -198,6 +199,7 @@ int vxrt_render_frames(vxrt_ctx* c, uint32_t flags, uint32_t count) try {
     if (int rc = check_render(c, flags)) return rc;
     HIP_TRY(hipSetDevice(c->cfg.device));
     c->call_id++;
+    c->call_frames = count;
     return render_sequence(c, flags, count, nullptr, nullptr);
 } VXRT_CATCH
 
@@ -208,6 +210,7 @@ int vxrt_render_path(vxrt_ctx* c, uint32_t flags, uint32_t count, const float (*
     if (!positions || !directions) { set_error("null argument"); return VXRT_E_INVALID; }
     HIP_TRY(hipSetDevice(c->cfg.device));
     c->call_id++;
+    c->call_frames = count;
     c->cam_fov = fov;
     return render_sequence(c, flags, count, positions, directions);
 } VXRT_CATCH
@@ -220,6 +223,7 @@ int vxrt_render_spp(vxrt_ctx* c, uint32_t flags, uint32_t spp) try {
     if (!(flags & VXRT_TRACE) || spp == 0 || spp > 4096) { set_error("vxrt_render_spp needs VXRT_TRACE and 1 <= spp <= 4096"); return VXRT_E_INVALID; }
     HIP_TRY(hipSetDevice(c->cfg.device));
     c->call_id++;
+    c->call_frames = spp;
     const bool timed = (flags & VXRT_TIMED) != 0;
     const size_t pixels = size_t(c->band.local_rows) * c->band.width;
     if (spp > 1 && c->spp_sum == nullptr && pixels > 0) HIP_TRY(c->spp_sum.alloc(pixels));
@@ -246,6 +250,7 @@ int vxrt_render_spp(vxrt_ctx* c, uint32_t flags, uint32_t spp) try {
             a.pixels = pixels;
             a.count = int(g); a.first = done == 0; a.last = done + g == spp; a.total = int(spp);
             HIP_TRY(launch_spp_accumulate(a, c->stream));
+            if (a.last) c->ring[size_t(slots[g - 1])].sky.call = 0;   // the average went over that slot's colour: its sky tiles are no frame's any more
             for (uint32_t k = 0; k < g; k++) {  // the slots may be traced into again only after this pass has read them
                 vxrt_ctx::Slot& sl = c->ring[size_t(slots[k])];
                 if (k == 0) HIP_TRY(hipEventRecord(sl.own, c->stream));   // one event for the pass; the batch's slots share it

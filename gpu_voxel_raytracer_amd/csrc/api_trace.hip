@@ -91,6 +91,7 @@ void frame_constants(const vxrt_ctx* c, TraceArgs& a) {
     a.block_first = 0;
     a.cull = 0;
     a.first_hit = nullptr;
+    a.tile_sky = nullptr;
     a.stack_levels = c->depth < 1 ? 1 : int(c->depth);
 #if VXRT_VARIANTS
     a.touch_nodes = c->d_touch_nodes;
@@ -257,10 +258,20 @@ static float path_motion_px(const vxrt_ctx* c, uint32_t g, uint32_t F, const flo
     return worst;
 }
 
+// Sky once can work at all: the option, the flags and lists (contexts with frames_per_launch >= 2), tiles of first_hit_kernel's size,
+// the list's kernels in this program (kernels.h: launch_walk_list), and a call that goes at least TWICE round the ring.  The first
+// ring's worth of frames and the launch that straddles the wrap go out full whatever happens, so in a shorter call the full frames
+// outnumber the thin ones: it keeps the parent's launches throughout, and with them the bytes per frame that bench.py's model of the
+// stage counts (48 B stored per pixel and frame; its counter passes over a short block are held against that model by
+// test_bench_contract_line).  What that gives up is measured: HISTORY §17 (two thin launches of a 48-frame call's six, 2.7 %).
+static bool sky_once_ready(const vxrt_ctx* c) {
+    return c->sky_once != 0 && c->sky_tiles && !c->tile_sky.empty() && launch_walk_list != nullptr && c->call_frames >= 2u * c->ring.size();
+}
+
 // Everything a launch of g frames on stream `lane` will do, decided here and nowhere else, into p (all zero on entry).  Calls no HIP API and changes nothing: it
 // reads the context as absorb_feedback left it (tail capacity, walking-tile count), the launch's cameras and the optional path poses.
 static void plan_trace(TracePlan& p, const vxrt_ctx* c, uint32_t g, const Cam* cams, const CullBox& cull, const float (*path_pos)[3], const float (*path_dir)[3],
-                       size_t lane) {
+                       size_t lane, const int* slots, uint32_t gbuf_frames) {
     const bool wide = use_wide(c);
     const vxrt_ctx::TileSchedule& sched = c->schedules[lane];
     const bool ordered = c->use_tile_order && sched.valid;
@@ -317,6 +328,22 @@ static void plan_trace(TracePlan& p, const vxrt_ctx* c, uint32_t g, const Cam* c
     }
     // the priority split (issue_trace_kernel) needs the walking tiles first in the order and their number on the host
     if (trace_kernel_head && c->trace_priority && ordered && !sched.heavy_pending && p.long_blocks == 0u && sched.heavy < tiles) p.split_heavy = sched.heavy;
+    // Sky once (VXRT_OPT_SKY_ONCE).  A tile none of whose pixels walks (first_hit_kernel: tile_sky) gets, from every block of
+    // trace_kernel, values that depend on the camera, the cull box and the uniforms alone.  A full launch that shares under option 2
+    // — the tag is this call's once it is issued, its frames have the tag's camera — leaves them in its slots (finish_launch: Slot::sky).
+    // A later launch of the SAME call that reads the same records finds them there when every one of its slots says so, for its own
+    // camera and cull box and with the G-buffer images where this launch wants them; it then goes out over the stream's list of the
+    // tiles that walk alone (refresh_walk_list), when that list was cut from the tagged walk — and is not empty, which settle_thin
+    // looks at.  The uniforms, the scene and the band cannot change inside a call, and a tag of another call matches nothing.
+    // A walk notes the all-sky tiles when the pinned pair their numbers travel in is free (nearly always: see settle_thin).
+    p.stamps_sky = sky_once_ready(c) && p.share && c->shared_primary == 2 && (p.walk ? !c->sky_count.pending : tag.sky);
+    if (p.stamps_sky && !p.walk && p.long_blocks == 0u && p.split_heavy == 0u && lane < c->walk_lists.size()) {
+        p.thin = c->walk_lists[lane].order_walk == tag.walk;
+        for (uint32_t k = 0; p.thin && k < g; k++) {
+            const vxrt_ctx::Slot::SkyTag& sky = c->ring[size_t(slots[k])].sky;
+            p.thin = sky.call == c->call_id && memcmp(&sky.cam, &cams[0], sizeof(Cam)) == 0 && sky.cull == cull && (sky.gbuf || ((gbuf_frames >> k) & 1u) == 0u);
+        }
+    }
     // Re-sort the tiles for this stream's coming frames from the costs just measured: after its first
     // frame, then every 8th (costs keep accumulating as a running maximum in between; ~7 us per sort).
     if (batches_frames(p.tracer) && c->use_tile_order && (!sched.valid || sched.age >= 8))
@@ -356,6 +383,14 @@ static int wait_for_slots(vxrt_ctx* c, uint32_t g, const int* slots, hipStream_t
     return VXRT_OK;
 }
 
+// the pinned pair has arrived (its event has been seen)
+static void take_sky_count(vxrt_ctx::SkyCount& sc) {
+    sc.n_walk = sc.host[0];
+    sc.skipped_pixels = sc.host[1];
+    sc.walk = sc.pending_walk;
+    sc.pending = false;
+}
+
 // step 3: what earlier launches of this stream reported, polled BEFORE the launch's timed region starts and before it is planned: the
 // room its tail wanted (the queues grow: host wait + reallocation) and the number of walking tiles its last sort found
 static int absorb_feedback(vxrt_ctx* c, size_t lane) {
@@ -365,6 +400,25 @@ static int absorb_feedback(vxrt_ctx* c, size_t lane) {
         sched.heavy = sched.host_heavy[0];
         sched.heavy_pending = false;
     }
+    vxrt_ctx::SkyCount& sc = c->sky_count;   // the numbers of the last walk's all-sky tiles (issue_head)
+    if (sc.pending && hipEventQuery(sc.ready) == hipSuccess) take_sky_count(sc);
+    return VXRT_OK;
+}
+
+// step 4b (sky once): a launch that plan_trace found thin needs the walk's numbers.  They left right behind first_hit_kernel in the
+// call's first launch, and no launch can be thin before the call has been once around the ring: they are here, unless the host has
+// run that far ahead of the GPU — then it waits for them, with at least the ring's worth of launches queued behind that event.  An
+// all-sky view keeps the full launch: block 0 of trace_kernel rotates the tail's counters (zero_counts), so there must be one.
+static int settle_thin(TraceLaunch& L) {
+    vxrt_ctx* c = L.c;
+    vxrt_ctx::SkyCount& sc = c->sky_count;
+    const uint64_t walk = c->first_hit_tag.walk;
+    if (sc.pending && sc.pending_walk == walk) {
+        HIP_TRY(hipEventSynchronize(sc.ready));
+        take_sky_count(sc);
+    }
+    L.plan.thin = sc.walk == walk && sc.n_walk > 0u && sc.n_walk <= trace_tile_count(c->band.width, c->band.local_rows);
+    if (L.plan.thin) { L.plan.n_walk = sc.n_walk; L.plan.skipped_pixels = sc.skipped_pixels; }
     return VXRT_OK;
 }
 
@@ -423,6 +477,14 @@ static int copy_counts(vxrt_ctx* c, vxrt_ctx::StreamQueues& sq, const unsigned* 
 static int issue_trace_kernel(TraceLaunch& L) {
     vxrt_ctx* c = L.c;
     const TracePlan& p = L.plan;
+    if (p.thin) {   // the tiles that walk alone, in the launch order's sequence; the others hold their sky (plan_trace)
+        const uint32_t* whole = L.a.tile_order;
+        L.a.tile_order = c->walk_lists[L.lane].order;
+        const hipError_t e = launch_trace(L.a, p.wide_head, p.hbm, L.ts, 0u, p.n_walk * L.g);
+        L.a.tile_order = whole;
+        HIP_TRY(e);
+        return VXRT_OK;
+    }
     if (p.split_heavy == 0u) {
         HIP_TRY(launch_trace(L.a, p.wide_head, p.hbm, L.ts, p.long_blocks, 0u));
         return VXRT_OK;
@@ -459,6 +521,18 @@ static int fork_long_tiles(TraceLaunch& L) {
     return VXRT_OK;
 }
 
+// Sky once: the launch's stream gets its order (as the stream's next launch will take it) without the all-sky tiles of the tagged walk
+static int cut_walk_list(TraceLaunch& L) {
+    vxrt_ctx* c = L.c;
+    const vxrt_ctx::FirstHitTag& tag = c->first_hit_tag;
+    vxrt_ctx::WalkList& wl = c->walk_lists[L.lane];
+    const vxrt_ctx::TileSchedule& sched = c->schedules[L.lane];
+    HIP_TRY(launch_walk_list((c->use_tile_order && sched.valid) ? sched.order.get() : nullptr, c->tile_sky[tag.buffer], c->use_tile_order ? sched.cost.get() : nullptr,
+                             wl.order, wl.partial, trace_tile_count(c->band.width, c->band.local_rows), L.ts));
+    wl.order_walk = tag.walk;
+    return VXRT_OK;
+}
+
 // The all-in-one launch, and the head of a head + tail pair: the long tiles' grid (its arguments are copied before the first hits are
 // set: it casts its own), the first hits when the launch shares its primary rays — its own walk or an earlier one's — trace_kernel.
 static int issue_head(TraceLaunch& L) {
@@ -469,6 +543,8 @@ static int issue_head(TraceLaunch& L) {
         vxrt_ctx::FirstHitTag& tag = c->first_hit_tag;
         L.a.first_hit = c->first_hits[b];
         if (L.plan.walk) {
+            if (L.plan.stamps_sky && c->shared_primary == 2 && b < c->tile_sky.size() && L.lane < c->walk_lists.size())
+                L.a.tile_sky = c->tile_sky[b];   // the walk notes the all-sky tiles as well
             // The walk overwrites buffer b (b == this stream).  Who may still be reading it?  Launches of this stream are over
             // before the walk starts: the stream's order.  A launch of another stream s that read b noted its event in
             // first_hit_readers (finish_launch), and launches of s are ordered among themselves, so waiting for the LAST reader on
@@ -488,6 +564,18 @@ static int issue_head(TraceLaunch& L) {
                 tag.buffer = b;
                 tag.cam = L.a.cams[0];
                 tag.cull = L.cull;
+                tag.walk = ++c->walk_serial;
+                tag.sky = L.a.tile_sky != nullptr;
+                // Sky once: this stream's list right away — a few microseconds ahead of trace_kernel, once per call — because its
+                // numbers are the walk's, and the host wants them when the call comes back to its first ring slot (settle_thin)
+                if (tag.sky) {
+                    vxrt_ctx::SkyCount& sc = c->sky_count;
+                    if (int rc = cut_walk_list(L)) return rc;
+                    HIP_TRY(hipMemcpyAsync(sc.host, c->walk_lists[L.lane].partial + 2 * kSortBlocks, 2 * sizeof(unsigned), hipMemcpyDeviceToHost, L.ts));
+                    HIP_TRY(hipEventRecord(sc.ready, L.ts));
+                    sc.pending = true;
+                    sc.pending_walk = tag.walk;
+                }
             }
         } else if (b != L.lane) {
             HIP_TRY(hipStreamWaitEvent(L.ts, c->first_hit_walked[b], 0));   // the walker's own stream needs no wait
@@ -614,6 +702,20 @@ static int resort_tiles(TraceLaunch& L) {
     return VXRT_OK;
 }
 
+// step 7b (sky once): the stream's launch order without the all-sky tiles, cut again whenever the tagged walk or the order is new —
+// behind the timed region, on the launch's stream: the next launch of the stream finds it by the stream's order.  The flags are read
+// from the tagged buffer, which this launch's kernels read as well: the next walk into that buffer waits for this launch's event
+// (finish_launch: first_hit_readers), recorded behind the list.  A re-sort changes the order, not the numbers: nothing travels.
+static int refresh_walk_list(TraceLaunch& L) {
+    vxrt_ctx* c = L.c;
+    if (L.lane >= c->walk_lists.size()) return VXRT_OK;
+    vxrt_ctx::WalkList& wl = c->walk_lists[L.lane];
+    if (L.plan.sort != TileSort::none) wl.order_walk = 0;   // the order it was cut from is gone
+    const vxrt_ctx::FirstHitTag& tag = c->first_hit_tag;
+    if (!L.plan.stamps_sky || tag.call != c->call_id || !tag.sky || wl.order_walk == tag.walk) return VXRT_OK;
+    return cut_walk_list(L);
+}
+
 // step 8: one event for the whole launch, the slots' and the context's books, and the three counters of what went out
 static int finish_launch(TraceLaunch& L, bool timed) {
     vxrt_ctx* c = L.c;
@@ -626,6 +728,15 @@ static int finish_launch(TraceLaunch& L, bool timed) {
         sl.trace_done = done;
         sl.last_use = done;              // until a later stage reads the slot, the trace is its last use
         sl.last_use_recorded = true;
+        // what the slot's all-sky tiles hold now: a thin launch left them alone; a full one stored this call's sky, or something else
+        if (L.plan.thin) continue;
+        sl.sky.call = 0;
+        if (L.plan.stamps_sky) {
+            sl.sky.call = c->call_id;
+            sl.sky.cam = L.a.cams[0];
+            sl.sky.cull = L.cull;
+            sl.sky.gbuf = ((L.a.gbuf_frames >> k) & 1u) != 0u;
+        }
     }
     c->slot = L.slots[g - 1];
     c->last_schedule = int(lane);
@@ -643,6 +754,12 @@ static int finish_launch(TraceLaunch& L, bool timed) {
     }
     if (L.plan.walk) c->first_hit_walks++;
     if (L.plan.split_heavy) c->split_launches++;
+    if (c->band.local_rows > 0 && (L.plan.path == TracePath::all_in_one || L.plan.path == TracePath::head_bounces || L.plan.path == TracePath::head_paths))
+        c->trace_kernel_blocks += uint64_t(L.plan.thin ? L.plan.n_walk : trace_tile_count(c->band.width, c->band.local_rows)) * g;
+    if (L.plan.thin) {
+        c->thin_launches++;
+        c->sky_rays += uint64_t(g) * L.plan.skipped_pixels;   // one cast_bounded_ray per pixel and frame, as a culled lane counts it (trace_block)
+    }
     return VXRT_OK;
 }
 
@@ -663,7 +780,8 @@ int trace_frames(vxrt_ctx* c, uint32_t g, bool timed, int* slots, Cam* cams, Cam
     if (c->band.local_rows > 0) {
         if (int rc = absorb_feedback(c, lane)) return rc;
         L.cull = cull_box(c, cams, g);
-        plan_trace(L.plan, c, g, cams, L.cull, path_pos, path_dir, lane);
+        plan_trace(L.plan, c, g, cams, L.cull, path_pos, path_dir, lane, slots, gbuf_frames);
+        if (L.plan.thin) { if (int rc = settle_thin(L)) return rc; }
         fill_trace_args(L, cams, gbuf_frames, first_frame_number);
         EventPair p;
         if (timed) { p = take_pair(c, 0); HIP_TRY(hipEventRecord(p.a, ts)); }
@@ -672,6 +790,7 @@ int trace_frames(vxrt_ctx* c, uint32_t g, bool timed, int* slots, Cam* cams, Cam
         if (c->trace_priority && batches_frames(L.plan.tracer)) HIP_TRY(hipStreamWaitEvent(ts, c->low_join[lane], 0));
         if (timed) HIP_TRY(hipEventRecord(p.b, ts));
         if (int rc = resort_tiles(L)) return rc;
+        if (int rc = refresh_walk_list(L)) return rc;
         if (timed) c->pending.push_back(p);
     }
     return finish_launch(L, timed);

@@ -167,6 +167,17 @@ struct vxrt_ctx {
         hipEvent_t trace_done = nullptr;  // handle, not owned: the event of the launch that traced the slot
         hipEvent_t last_use = nullptr;    // handle: what must have finished before the slot is traced into again (`own` or a launch's event)
         bool last_use_recorded = false;
+        // VXRT_OPT_SKY_ONCE: what the slot's all-sky tiles (first_hit_kernel: tile_sky) hold.  Set by a FULL trace launch that took its
+        // first hits from the call's tagged records (finish_launch): those tiles then hold the sky of `cam` under this call's uniforms.
+        // Whatever else writes one of the slot's three images inside a call clears it (vxrt_render_spp's average).  A tag of another
+        // call is never honoured — the uniforms, the scene and the band cannot change inside one — so no setter has to know of it.
+        struct SkyTag {
+            uint64_t call = 0;    // call_id of the launch that stored the tiles (0: nothing known)
+            Cam cam{};
+            CullBox cull{};
+            bool gbuf = false;    // normal/depth and albedo/node were stored with the colour
+        };
+        SkyTag sky;
     };
     std::vector<Slot> ring;
     int inflight = 1;
@@ -297,8 +308,38 @@ struct vxrt_ctx {
         size_t buffer = 0;      // index into first_hits = the trace stream that walked
         Cam cam{};              // the camera the rays were made from
         CullBox cull{};         // the sky cull the walk used: a culled lane wrote no record
+        uint64_t walk = 0;      // which walk of the context it was (walk_serial): a WalkList made from an earlier one is stale
+        bool sky = false;       // the walk noted the all-sky tiles (tile_sky[buffer]) and sent their numbers off (sky_count): VXRT_OPT_SKY_ONCE
     };
     FirstHitTag first_hit_tag;
+    uint64_t walk_serial = 0;   // walks of the primary rays issued so far (never reset)
+    // VXRT_OPT_SKY_ONCE (default 1): inside one API call, a launch whose slots all hold this call's sky already (Slot::sky) goes out
+    // over the tiles that walk alone — same kernel, same blocks for those tiles — and the rays of the pixels left out are counted on
+    // the host (sky_rays).  0: every launch covers every tile, as before the option existed.
+    int sky_once = 1;
+    bool sky_tiles = false;             // trace_kernel's tiles are first_hit_kernel's 8 x 8 pixels (alloc_images)
+    uint64_t call_frames = 0;           // frames the API call in progress traces: one that goes less than twice round the ring asks for no flags and no list
+    std::vector<DeviceBuf<uint32_t>> tile_sky;        // per buffer of first_hits, written by the same walk and valid under the same tag
+    struct WalkList {   // per trace stream: the stream's launch order without the all-sky tiles (trace.hip: walk_list_kernel)
+        DeviceBuf<uint32_t> order;      // the first SkyCount::n_walk entries
+        DeviceBuf<uint32_t> partial;    // the kernels' scratch; its last two words are the list's numbers
+        uint64_t order_walk = 0;        // FirstHitTag::walk the list in `order` was made from (0: none, or the stream's order has changed since)
+    };
+    std::vector<WalkList> walk_lists;
+    // How many tiles walk, and how many pixels the others have: numbers of the WALK, the same on every stream.  They leave with the
+    // walking launch's own list, right behind first_hit_kernel, and are on the host long before the call comes back to a ring slot.
+    struct SkyCount {
+        PinnedBuf<unsigned> host;       // pinned: {tiles that walk, pixels of the tiles that do not}
+        Event ready;                    // behind the copy into host
+        bool pending = false;
+        uint64_t pending_walk = 0;      // FirstHitTag::walk the numbers under way belong to
+        uint64_t walk = 0;              // ... n_walk and skipped_pixels belong to (0: none)
+        unsigned n_walk = 0, skipped_pixels = 0;
+    };
+    SkyCount sky_count;
+    uint64_t sky_rays = 0;              // primary rays of pixels that thin launches left out (vxrt_stats.rays adds them to the device's count)
+    uint64_t thin_launches = 0;         // vxrt_debug_thin_launches
+    uint64_t trace_kernel_blocks = 0;   // vxrt_debug_trace_blocks: blocks of trace_kernel issued, summed over the launches
     int path_blocks = 512;  // tracer 5: blocks of path_kernel (each wave takes an equal range of the queue, >= 512 paths)
     int tail_from = 1;  // tracer 4: the hit number at which live paths move to the compacted launches
     unsigned tail_split = 0;  // ... bit k: the tail compacts again and starts a new launch at path segment k
@@ -359,6 +400,10 @@ struct TracePlan {
     unsigned long_blocks;      // blocks of the longest tiles that go out as a grid of their own (0: none); the head starts behind them
     bool single_tail_launch;   // the tail is exactly one launch: the counter copy-back goes behind it
     unsigned split_heavy;      // priority split: the first split_heavy tiles of the order on the trace stream, the rest on the low-priority one (0: one grid)
+    bool thin;                 // sky once: trace_kernel goes out over the stream's WalkList alone, n_walk tiles (every slot holds its sky already)
+    unsigned n_walk;           // ... their number, and the pixels per frame that are left out and counted on the host
+    unsigned skipped_pixels;
+    bool stamps_sky;           // a full launch that leaves this call's sky in its slots' all-sky tiles: finish_launch tags the slots
     TileSort sort;             // how this launch re-sorts the stream's tiles when it is over
 };
 

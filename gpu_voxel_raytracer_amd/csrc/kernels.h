@@ -153,6 +153,9 @@ struct TraceArgs {
     // one record per pixel of the band — what cast_bounded_ray returns for that pixel's primary ray — written by first_hit_kernel ahead
     // of trace_kernel on the same stream, and loaded by trace_block in place of a walking lane's first cast.  null: every frame casts.
     uint4* first_hit;         // [local_rows * width]  (bits(hit.time), hit.node, normal as pack_axis x | y << 2 | z << 4, hit ? 1 : 0)
+    // Sky once (VXRT_OPT_SKY_ONCE): first_hit_kernel alone writes, per 8 x 8 tile, 0 when a pixel of the tile walks, else the number of
+    // the tile's pixels inside the frame — all answered by the sky cull.  null: not wanted.  trace_kernel never looks at it.
+    uint32_t* tile_sky;       // [tiles]
 #if VXRT_VARIANTS
     // Touch map (vxrt_debug_touch_map; -DVXRT_VARIANTS=1 only): when set, every scene load of the walk marks the 64-byte line it reads —
     // bit (index * record bytes) >> 6 of touch_nodes for a node record (8-byte or wide), of touch_leaves for a leaf word — so that the
@@ -242,6 +245,13 @@ hipError_t launch_fused(const TraceArgs& a, void* ctl, unsigned waves, const uin
 hipError_t launch_trace(const TraceArgs& a, bool wide, bool hbm_scene, hipStream_t s, unsigned block_first = 0, unsigned block_count = 0);
 // the primary rays of camera a.cams[0], one wave per 8 x 8 pixel tile of the band -> a.first_hit (TraceArgs::first_hit); 8-byte records only
 hipError_t launch_first_hit(const TraceArgs& a, hipStream_t s);
+// Sky once (VXRT_OPT_SKY_ONCE): walk_order = the tiles of `order` (null: raster order) whose tile_sky entry is 0, in the same sequence
+// (stable: longest-first survives); result[0] = their number, result[1] = the summed tile_sky of the others (the pixels a launch over
+// walk_order alone leaves out); cost (may be null): the tiles left out get the cost-map entry they would have recorded themselves.
+// partial: 2 x 64 + 2 words of scratch (result = partial + 128).  Weak: a host-only program that links the scheduling code against
+// stubs of the launchers may leave it out (api_trace.hip then never asks for a list, and no launch is thin).
+hipError_t launch_walk_list(const uint32_t* order, const uint32_t* tile_sky, uint32_t* cost, uint32_t* walk_order, uint32_t* partial, unsigned tiles,
+                            hipStream_t s) __attribute__((weak));
 // test hook: the walk (cast_ray) for caller-given rays; out = 8 floats per ray (hit, time, bits(leaf word), normal, 0, 0)
 hipError_t launch_path_log(const TraceArgs& a, bool wide, int x, int y, float* log, hipStream_t s);
 hipError_t launch_count_culled(const TraceArgs& a, unsigned long long* count, hipStream_t s);   // diagnostics: pixels the sky cull decides

@@ -21,6 +21,7 @@
 //
 // Arithmetic follows include/vxrt_detmath.h: every float operation that can change a result is the
 // shader's operation, in the shader's order, never contracted.
+#include "block_scan.h"
 #include "trace_block.h"
 
 namespace vxrt {
@@ -49,11 +50,18 @@ __global__ __launch_bounds__(64) void first_hit_kernel(const TraceArgs a) {
     const int x = int(tile % tiles_x) * 8 + (lane & 7);
     const int lrow = int(tile / tiles_x) * 8 + (lane >> 3);
     const int y = frame_row(a.band, lrow);
-    if (!(x < a.band.width && lrow < a.band.local_rows && y < a.band.height)) return;
+    const bool active = x < a.band.width && lrow < a.band.local_rows && y < a.band.height;
     const Cam& cam = a.cams[0];
     const f3 o = ld3(cam.o);
     const f3 d = norm3((float(x) * ld3(cam.r) - float(y) * ld3(cam.u)) + ld3(cam.f));  // voxels.comp:299-303
-    if (primary_miss_is_certain(a, o, d)) return;
+    const bool walk = active && !primary_miss_is_certain(a, o, d);
+    // Sky once (TraceArgs::tile_sky): does anybody in the tile walk?  If not, every block of trace_kernel for this tile would only store
+    // the sky and count one ray per pixel inside the frame — the number noted here (>= 1: a tile has a pixel inside the frame).
+    if (a.tile_sky != nullptr) {
+        const unsigned long long walkers = __ballot(walk), inside = __ballot(active);
+        if (lane == 0) a.tile_sky[tile] = walkers != 0ull ? 0u : unsigned(__popcll(inside));
+    }
+    if (!walk) return;
     const Caster<false> caster(a, lds_stack, lane);
     RayHit hit;
     hit.time = 0.0f; hit.node = 0; hit.normal = splat3(0.0f);
@@ -61,6 +69,63 @@ __global__ __launch_bounds__(64) void first_hit_kernel(const TraceArgs a) {
     const f3 n = hit.normal;
     a.first_hit[size_t(lrow) * a.band.width + x] =
         make_uint4(vx_f2u(hit.time), uint32_t(hit.node), pack_axis(n.x) | pack_axis(n.y) << 2 | pack_axis(n.z) << 4, is_hit ? 1u : 0u);
+}
+
+// Sky once (VXRT_OPT_SKY_ONCE): a stream's launch order without the tiles that only store sky (first_hit_kernel: tile_sky != 0), in
+// two small launches over contiguous ranges of the order, as the sort below: each block counts its range's walking tiles and sums the
+// pixels of the others -> partial[2 b], partial[2 b + 1]; then each block writes its range's walking tiles behind those of the blocks
+// before it, in order (block_exclusive is in thread order: the compaction is stable), and block 0 writes the totals.
+constexpr unsigned kListThreads = 256;
+
+__device__ __forceinline__ unsigned listed_tile(const uint32_t* order, unsigned i) { return order ? order[i] : i; }
+
+__global__ __launch_bounds__(kListThreads) void walk_count_kernel(const uint32_t* order, const uint32_t* tile_sky, uint32_t* partial, unsigned tiles,
+                                                                  unsigned per_block) {
+    __shared__ unsigned sums[2];
+    if (threadIdx.x < 2u) sums[threadIdx.x] = 0u;
+    __syncthreads();
+    const unsigned i0 = blockIdx.x * per_block, i1 = i0 + per_block < tiles ? i0 + per_block : tiles;
+    unsigned walking = 0, pixels = 0;
+    for (unsigned i = i0 + threadIdx.x; i < i1; i += kListThreads) {
+        const unsigned sky = tile_sky[listed_tile(order, i)];
+        walking += sky == 0u ? 1u : 0u;
+        pixels += sky;
+    }
+    walking = wave_sum(walking);
+    pixels = wave_sum(pixels);
+    if ((threadIdx.x & 63u) == 0u) { atomicAdd(&sums[0], walking); atomicAdd(&sums[1], pixels); }
+    __syncthreads();
+    if (threadIdx.x < 2u) partial[2u * blockIdx.x + threadIdx.x] = sums[threadIdx.x];
+}
+
+__global__ __launch_bounds__(kListThreads) void walk_list_kernel(const uint32_t* order, const uint32_t* tile_sky, uint32_t* cost, uint32_t* walk_order,
+                                                                 uint32_t* partial, unsigned tiles, unsigned per_block) {
+    __shared__ unsigned scan_lds[kListThreads / 64];
+    __shared__ unsigned before_lds[2];
+    if (threadIdx.x < 64u) {   // blocks <= kSortBlocks = 64: one lane per block
+        const unsigned b = threadIdx.x;
+        const unsigned n = b < gridDim.x ? partial[2u * b] : 0u, px = b < gridDim.x ? partial[2u * b + 1u] : 0u;
+        const unsigned before = wave_sum(b < blockIdx.x ? n : 0u), all = wave_sum(n), all_px = wave_sum(px);
+        if (b == 0u) {
+            before_lds[0] = before;
+            if (blockIdx.x == 0u) { partial[2u * kSortBlocks] = all; partial[2u * kSortBlocks + 1u] = all_px; }
+        }
+    }
+    __syncthreads();
+    unsigned at = before_lds[0];
+    const unsigned i0 = blockIdx.x * per_block, i1 = i0 + per_block < tiles ? i0 + per_block : tiles;
+    for (unsigned base = i0; base < i1; base += kListThreads) {   // uniform trip count: block_exclusive has barriers
+        const unsigned i = base + threadIdx.x;
+        const unsigned tile = i < i1 ? listed_tile(order, i) : 0u;
+        const bool walks = i < i1 && tile_sky[tile] == 0u;
+        unsigned total = 0;
+        const unsigned rank = block_exclusive<unsigned, kListThreads / 64>(walks ? 1u : 0u, scan_lds, &total);
+        if (walks) walk_order[at + rank] = tile;
+        // a tile that is left out of a launch records no cost: what it would have recorded (trace_block: kLightCost), so that the next
+        // sort of this stream sees the cost map it always saw
+        else if (i < i1 && cost != nullptr && cost[tile] < kLightCost) cost[tile] = kLightCost;
+        at += total;
+    }
 }
 
 
@@ -327,6 +392,16 @@ hipError_t launch_first_hit(const TraceArgs& a, hipStream_t s) {
     if (a.band.local_rows <= 0 || a.first_hit == nullptr) return hipSuccess;
     const unsigned tiles = unsigned(a.band.width + 7) / 8u * (unsigned(a.band.local_rows + 7) / 8u);
     hipLaunchKernelGGL(first_hit_kernel, dim3(tiles), dim3(64), caster_lds_bytes(a, false, kTB), s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_walk_list(const uint32_t* order, const uint32_t* tile_sky, uint32_t* cost, uint32_t* walk_order, uint32_t* partial, unsigned tiles,
+                            hipStream_t s) {
+    if (tiles == 0u) return hipSuccess;
+    const unsigned blocks = (tiles + kListThreads - 1u) / kListThreads < kSortBlocks ? (tiles + kListThreads - 1u) / kListThreads : kSortBlocks;
+    const unsigned per_block = (tiles + blocks - 1u) / blocks;
+    hipLaunchKernelGGL(walk_count_kernel, dim3(blocks), dim3(kListThreads), 0, s, order, tile_sky, partial, tiles, per_block);
+    hipLaunchKernelGGL(walk_list_kernel, dim3(blocks), dim3(kListThreads), 0, s, order, tile_sky, cost, walk_order, partial, tiles, per_block);
     return hipGetLastError();
 }
 

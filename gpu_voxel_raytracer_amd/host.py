@@ -126,6 +126,7 @@ OPT_DENOISE_MODE, OPT_TAIL_CAPACITY, OPT_SCENE_FORMAT, OPT_HALO_ROWS, OPT_SKY_CU
  OPT_TRACE_SPLIT, OPT_PATH_BLOCKS, OPT_SHADE_BLOCKS, OPT_RAYS_PER_WAVE, OPT_NODE_ORDER, OPT_HEAD_STAGGER, OPT_LONG_TILES, OPT_FUSED_TAIL,
  OPT_TRACE_PRIORITY, OPT_XCD_AFFINITY) = range(7, 24)      # include/vxrt_debug.h (the options of experiments)
 OPT_SHARED_PRIMARY = 24                                    # include/vxrt.h (a product option: the next free id)
+OPT_SKY_ONCE = 25                                          # include/vxrt.h
 TILE_SPREAD_AUTO = 0xffffffff
 
 
@@ -144,7 +145,7 @@ ENV_KNOBS = {"VXRT_SKY_CULL": OPT_SKY_CULL, "VXRT_HALO_ROWS": OPT_HALO_ROWS, "VX
              "VXRT_SPREAD": OPT_TILE_SPREAD, "VXRT_TILE_ORDER": OPT_TILE_ORDER, "VXRT_TRACE_SPLIT": OPT_TRACE_SPLIT,
              "VXRT_HOST_BUILD": OPT_HOST_SCENE_BUILD, "VXRT_NODE_ORDER": OPT_NODE_ORDER, "VXRT_HEAD_STAGGER": OPT_HEAD_STAGGER, "VXRT_LONG_TILES": OPT_LONG_TILES, "VXRT_FUSED_TAIL": OPT_FUSED_TAIL,
              "VXRT_TRACE_PRIORITY": OPT_TRACE_PRIORITY, "VXRT_XCD_AFFINITY": OPT_XCD_AFFINITY,
-             "VXRT_SHARED_PRIMARY": OPT_SHARED_PRIMARY}
+             "VXRT_SHARED_PRIMARY": OPT_SHARED_PRIMARY, "VXRT_SKY_ONCE": OPT_SKY_ONCE}
 _env_knobs_enabled = os.environ.get("VXRT_ENV_KNOBS") == "1"      # the explicit opt-in of the A/B scripts (scripts/*.sh)
 
 
@@ -1626,6 +1627,18 @@ class Context:
         """vxrt_debug_first_hit_walks: launches of the first-hit kernel (OPT_SHARED_PRIMARY 1: one per sharing launch; 2: one per call and camera)."""
         n = C.c_uint64(0)
         self._chk(self._L.vxrt_debug_first_hit_walks(self._h, C.byref(n)), "vxrt_debug_first_hit_walks")
+        return int(n.value)
+
+    def thin_launches(self):
+        """vxrt_debug_thin_launches: trace launches that went out over the tiles that walk alone (OPT_SKY_ONCE)."""
+        n = C.c_uint64(0)
+        self._chk(self._L.vxrt_debug_thin_launches(self._h, C.byref(n)), "vxrt_debug_thin_launches")
+        return int(n.value)
+
+    def trace_blocks(self):
+        """vxrt_debug_trace_blocks: blocks of the trace kernel issued, summed over the launches."""
+        n = C.c_uint64(0)
+        self._chk(self._L.vxrt_debug_trace_blocks(self._h, C.byref(n)), "vxrt_debug_trace_blocks")
         return int(n.value)
 
     def set_option(self, option, value):

@@ -251,12 +251,23 @@ typedef struct vxrt_stats {
  *                          0: every frame casts its own primary rays — exactly the launches of earlier versions.  Not used for scenes
  *                          beyond the Infinity Cache.  vxrt_debug.h: vxrt_debug_shared_primary_launches counts the launches that took
  *                          their first hits from records, vxrt_debug_first_hit_walks the walks.
+ *   VXRT_OPT_SKY_ONCE      1 (default): inside ONE vxrt_render_frames / vxrt_render_spp / vxrt_render_path call that traces at least twice as
+ *                          many frames as the context has frame slots (frames_in_flight x frames_per_launch + 2), with VXRT_OPT_SHARED_PRIMARY 2
+ *                          and the camera at rest, an 8 x 8 pixel tile whose every pixel the sky cull answers is stored once per frame
+ *                          slot: the call's walk of the primary rays notes those tiles, the first launch into a slot stores them, and
+ *                          a later launch of the call into slots that all hold them already runs the trace kernel over the other tiles
+ *                          alone — the same blocks, the same arithmetic for those.  The tiles left out depend on the camera, the cull
+ *                          box and the sky parameters only, none of which can change inside a call; nothing is kept between calls.
+ *                          Same frames, bit for bit; vxrt_stats.rays counts the pixels left out as before (one primary ray each).
+ *                          0: every launch covers every tile — exactly the launches of earlier versions.  vxrt_debug.h:
+ *                          vxrt_debug_thin_launches counts the launches that left tiles out, vxrt_debug_trace_blocks the blocks issued.
  *
  */
 typedef enum vxrt_option { VXRT_OPT_DENOISE_MODE = 1, VXRT_OPT_TAIL_CAPACITY = 2, VXRT_OPT_SCENE_FORMAT = 3, VXRT_OPT_HALO_ROWS = 4,
                            VXRT_OPT_SKY_CULL = 5, VXRT_OPT_FRAME_LANES = 6,
                            VXRT_OPT_LAST_ = 0x7fffffff /* vxrt_debug.h continues the list from 7 on (scheduling options of experiments) */ } vxrt_option;
 #define VXRT_OPT_SHARED_PRIMARY ((vxrt_option)24)   /* the next free id after vxrt_debug.h's 7 .. 23 */
+#define VXRT_OPT_SKY_ONCE ((vxrt_option)25)
 int vxrt_set_option(vxrt_ctx* ctx, vxrt_option option, uint32_t value);
 
 /* ---- context: replaces Context::new / create_bindings / resize (src/context.rs:595-660, 936-1016,

@@ -142,6 +142,11 @@ int vxrt_debug_shared_primary_launches(vxrt_ctx* ctx, uint64_t* count);
  * VXRT_OPT_SHARED_PRIMARY 1: one per launch that shared; 2: one per API call (vxrt_render_frames, vxrt_render_spp, vxrt_render_path)
  * and camera, however many of the call's launches shared it; 0: none. */
 int vxrt_debug_first_hit_walks(vxrt_ctx* ctx, uint64_t* count);
+/* Diagnostics: trace launches since create / vxrt_reset_stats that went out over the tiles that walk alone (vxrt.h: VXRT_OPT_SKY_ONCE). */
+int vxrt_debug_thin_launches(vxrt_ctx* ctx, uint64_t* count);
+/* Diagnostics: blocks of the trace kernel issued since create / vxrt_reset_stats, summed over the launches: tiles x frames for a launch
+ * that covers every tile, walking tiles x frames for a thin one. */
+int vxrt_debug_trace_blocks(vxrt_ctx* ctx, uint64_t* count);
 /* Diagnostics of trace stream 0's last fused launch (VXRT_OPT_FUSED_TAIL): shader clocks to "every head block finished" and to the last
  * wave's end, chunks taken before / after that moment, idle sleeps, stamp polls, head claims, 0. */
 int vxrt_debug_fused_profile(vxrt_ctx* ctx, uint64_t out[8]);

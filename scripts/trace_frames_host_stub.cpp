@@ -29,6 +29,7 @@ namespace vxrt {
 hipError_t launch_trace(const TraceArgs& a, bool, bool, hipStream_t, unsigned, unsigned) { TraceArgs b = a; g_calls = g_calls + b.batch; return hipSuccess; }   // the real one copies the arguments too
 hipError_t launch_bounces(const TraceArgs&, bool, const PathQueue*, unsigned**, unsigned* l, int, unsigned, int, hipStream_t) { *l += 1; STUB }
 hipError_t launch_first_hit(const TraceArgs&, hipStream_t) STUB
+hipError_t launch_walk_list(const uint32_t*, const uint32_t*, uint32_t*, uint32_t*, uint32_t*, unsigned, hipStream_t) STUB
 hipError_t launch_tile_order(uint32_t*, uint32_t*, uint32_t*, uint32_t*, unsigned, unsigned, unsigned, int, hipStream_t) STUB
 unsigned trace_tile_count(int w, int h) { return unsigned((w + 7) / 8) * unsigned((h + 7) / 8); }
 void trace_tile_dims(int* w, int* h) { *w = 8; *h = 8; }
