@@ -17,7 +17,8 @@
 //   api_setops.hip   two device voxel lists combined: union, intersection, difference, delta (vxrt_setops.h)
 //   api_morph.hip    a device voxel list dilated, eroded, or cut to its surface layer or margin ring (vxrt_morph.h)
 //   api_mesh.hip     a device voxel list's exposed faces as an indexed triangle mesh (vxrt_mesh.h)
-//   list_ops.hip     no entry point: the host pipeline those four share (list_ops.h)
+//   api_shape.hip    a box, ball, cylinder or capsule rasterised into a device voxel list (vxrt_shape.h)
+//   list_ops.hip     no entry point: the host pipeline those five share (list_ops.h)
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -233,6 +233,132 @@ def rigid_box(src_min, src_max, rotation, pivot=(0, 0, 0), translation=(0, 0, 0)
     return tuple(int(v) for v in box_min), tuple(int(v) for v in box_max)
 
 
+class Shape(C.Structure):
+    """vxrt_shape (include/vxrt_shape.h): a box, ball, cylinder or capsule in shape space, in Q16 cells, 32 bytes."""
+    _fields_ = [("kind", C.c_uint32), ("r", C.c_uint32), ("h", C.c_uint32 * 3), ("reserved", C.c_uint32 * 3)]
+
+
+# vxrt_shape_kind (include/vxrt_shape.h)
+SHAPE_BOX, SHAPE_BALL, SHAPE_CYLINDER, SHAPE_CAPSULE = 0, 1, 2, 3
+SHAPE_LIMIT = 1 << 29          # r and h, Q16: 8192 cells
+
+
+def _vec3(v, name):
+    try:
+        a = np.asarray(v, np.float64).reshape(-1)
+    except (TypeError, ValueError):
+        raise ValueError(f"{name} must be three numbers") from None
+    if a.shape != (3,) or not np.isfinite(a).all():
+        raise ValueError(f"{name} must be three finite numbers")
+    return a
+
+
+def _length(v, name):
+    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v) or v < 0:
+        raise ValueError(f"{name} must be a finite number, not negative")
+    return float(v)
+
+
+def _rotation3(rotation):
+    r = np.eye(3) if rotation is None else np.asarray(rotation, np.float64)
+    if r.shape != (3, 3) or not np.isfinite(r).all():
+        raise ValueError("rotation must be a finite 3x3 matrix")
+    return r
+
+
+def _shape_of(kind, r, h, centre, rotation, gain, extent):
+    """(Shape, Affine, box_min, box_max) of a shape with shape-space radius r and half extents h (cells), centre and orientation
+    `rotation` (its columns are the shape's axes in the destination) and per-axis gain (shape-space cells per destination cell, >= 1);
+    extent: the shape's half width per destination axis about the centre.  m = rint(65536 g_i R[j][i]), t = rint(-65536 g_i (R^T
+    centre)_i) in float64; the box is [floor(centre - extent) - 2, ceil(centre + extent) + 2), clipped to [-32768, 32768]: the
+    rounding of m and t moves a pulled centre by under 1.3 shape-space cells, which with no gain below 1 is no longer in the
+    destination, so a cell of the result lies within 1.8 cells of the shape's bounding box (include/vxrt_shape.h)."""
+    m = np.rint(65536.0 * gain[:, None] * rotation.T)
+    t = np.rint(-65536.0 * gain * (rotation.T @ centre))
+    q = np.rint(65536.0 * np.array([r, *h]))
+    if (np.abs(m) > AFFINE_M_LIMIT).any() or (np.abs(t) > AFFINE_T_LIMIT).any():
+        raise ValueError("the pull map is beyond vxrt_affine's limits (|m| <= 2^24, |t| <= 2^40)")
+    if (q > SHAPE_LIMIT).any():
+        raise ValueError("the shape is beyond vxrt_shape's limits (r, h <= 8192 cells)")
+    s, a = Shape(), Affine()
+    s.kind, s.r = kind, int(q[0])
+    for i in range(3):
+        s.h[i] = int(q[1 + i])
+        for j in range(3):
+            a.m[i][j] = int(m[i, j])
+        a.t[i] = int(t[i])
+    box_min = np.clip(np.floor(centre - extent) - 2, -32768, 32768)
+    box_max = np.clip(np.ceil(centre + extent) + 2, -32768, 32768)
+    return s, a, tuple(int(v) for v in box_min), tuple(int(v) for v in box_max)
+
+
+def ball_shape(center, radius):
+    """The ball about `center` (three numbers, in the coordinates in which cell c is the cube [c, c + 1)^3) of `radius` cells ->
+    (Shape, Affine, box_min, box_max) for Context.shape_voxels: the cells whose centres lie within radius of center, up to the Q16
+    rounding of both."""
+    c, r = _vec3(center, "center"), _length(radius, "radius")
+    return _shape_of(SHAPE_BALL, r, (0, 0, 0), c, np.eye(3), np.ones(3), np.full(3, r))
+
+
+def ellipsoid_shape(center, radii, rotation=None):
+    """The ellipsoid about `center` with semi-axes `radii` (three positive numbers) along the columns of `rotation` (3x3, None: the
+    identity) -> (Shape, Affine, box_min, box_max): a SHAPE_BALL of radius rho under the pull that scales axis i by rho / radii[i].
+    rho is the largest power of two that keeps the pull within its limits — rho / min(radii) <= 256 (|m| <= 2^24) and rho <= 8192
+    (r <= 2^29) — so that m's rounding step of 2^-16 is as small a part of rho / radii[i] as the format allows; it must not be
+    below max(radii) (no axis is shrunk, see _shape_of), which refuses radii above 8192 and aspect ratios above 256."""
+    c, a, rot = _vec3(center, "center"), _vec3(radii, "radii"), _rotation3(rotation)
+    if not (a > 0).all():
+        raise ValueError("radii must be positive")
+    rho = 2.0 ** np.floor(np.log2(min(8192.0, 256.0 * a.min())))
+    if rho < a.max():
+        raise ValueError("radii beyond 8192 cells or an aspect ratio beyond 256")
+    extent = np.sqrt(((rot * a[None, :]) ** 2).sum(axis=1))
+    return _shape_of(SHAPE_BALL, rho, (0, 0, 0), c, rot, rho / a, extent)
+
+
+def box_shape(center, half, rotation=None):
+    """The box about `center` with half extents `half` along the columns of `rotation` (3x3, None: the identity) -> (Shape, Affine,
+    box_min, box_max).  Half-open in shape space: with the identity, an integer centre and integer half extents it is exactly the
+    cells [center - half, center + half)."""
+    c, h, rot = _vec3(center, "center"), _vec3(half, "half"), _rotation3(rotation)
+    if (h < 0).any():
+        raise ValueError("half must not be negative")
+    return _shape_of(SHAPE_BOX, 0.0, h, c, rot, np.ones(3), np.abs(rot) @ h)
+
+
+def _axis_frame(a, b):
+    """The centre, half length and an orientation whose third column runs from a to b (the first is the destination axis least
+    along it, made orthogonal; a == b: the identity)."""
+    a, b = _vec3(a, "a"), _vec3(b, "b")
+    v = b - a
+    length = float(np.linalg.norm(v))
+    if length == 0.0:
+        return a, 0.0, np.eye(3)
+    w = v / length
+    e = np.zeros(3)
+    e[int(np.argmin(np.abs(w)))] = 1.0
+    u = e - (e @ w) * w
+    u /= np.linalg.norm(u)
+    return (a + b) / 2, length / 2, np.stack([u, np.cross(w, u), w], axis=1)
+
+
+def cylinder_shape(a, b, radius):
+    """The cylinder of `radius` cells whose axis runs from point a to point b, with flat ends there -> (Shape, Affine, box_min,
+    box_max)."""
+    r = _length(radius, "radius")
+    c, h, rot = _axis_frame(a, b)
+    w = rot[:, 2]
+    return _shape_of(SHAPE_CYLINDER, r, (0, 0, h), c, rot, np.ones(3), h * np.abs(w) + r * np.sqrt(np.maximum(0.0, 1.0 - w * w)))
+
+
+def capsule_shape(a, b, radius):
+    """The capsule of `radius` cells about the segment from point a to point b: the cells whose centres lie within radius of it ->
+    (Shape, Affine, box_min, box_max)."""
+    r = _length(radius, "radius")
+    c, h, rot = _axis_frame(a, b)
+    return _shape_of(SHAPE_CAPSULE, r, (0, 0, h), c, rot, np.ones(3), h * np.abs(rot[:, 2]) + r)
+
+
 # vxrt_pick_hit (include/vxrt_edit.h)
 PICK_HIT_DTYPE = np.dtype([("status", np.uint32), ("time", np.float32), ("normal", np.float32, (3,)), ("voxel", np.int32, (3,)),
                            ("leaf", np.int32)])
@@ -1313,6 +1439,57 @@ class Context:
             return self.transform_voxels(pos, mrgb, pull, (0, 0, 0), (0, 0, 0))
         lo, hi = pos.amin(dim=0).cpu().numpy(), pos.amax(dim=0).cpu().numpy()
         return self.transform_voxels(pos, mrgb, pull, *rigid_box(lo, hi, rotation, pivot, translation))
+
+    def shape_voxels(self, shape, pull, box_min, box_max, mrgb=None, cap=None):
+        """vxrt_shape_voxels_device (include/vxrt_shape.h): the cells of the half-open box [box_min, box_max) whose centres the pull
+        map (an Affine) takes into the shape (a Shape; ball_shape, ellipsoid_shape, box_shape, cylinder_shape and capsule_shape make
+        all four arguments) -> (pos int16 [k,3], mrgb uint8 [k,4]) as torch tensors on the context's device, in path order.  mrgb:
+        four integers of [0, 255] that every voxel carries (the material's top bit dropped), or None: positions only, and the second
+        value is None.  cap as transform_voxels'.  Ordered on both sides against torch's current stream.  No scene is needed or
+        touched."""
+        if not isinstance(shape, Shape):
+            raise TypeError("shape must be a Shape (ball_shape and its kin make one)")
+        if not isinstance(pull, Affine):
+            raise TypeError("pull must be an Affine (ball_shape and its kin make one)")
+        lo, hi = self._cell3(box_min, "box_min", -32768, 32768), self._cell3(box_max, "box_max", -32768, 32768)
+        word = None
+        if mrgb is not None:
+            try:
+                b = [int(v) for v in np.asarray(mrgb).reshape(-1).tolist()]
+                exact = [float(v) for v in np.asarray(mrgb, np.float64).reshape(-1).tolist()] == [float(v) for v in b]
+            except (TypeError, ValueError):
+                raise ValueError("mrgb must be four integers of [0, 255]") from None
+            if len(b) != 4 or not exact or not all(0 <= v <= 255 for v in b):
+                raise ValueError("mrgb must be four integers of [0, 255]")
+            word = (C.c_uint8 * 4)(*b)
+        self._cap(cap)
+        got = C.c_size_t(0)
+
+        def run(out_pos, out_mrgb, room):
+            self._chk(self._L.vxrt_shape_voxels_device(self._h, C.byref(shape), C.byref(pull), lo, hi, word, _dptr(out_pos), _dptr(out_mrgb),
+                                                       C.c_size_t(room), C.byref(got)), "vxrt_shape_voxels_device")
+            return int(got.value)
+        return self._list_result(run, word is not None, False, cap)
+
+    def ball_voxels(self, center, radius, mrgb=None, cap=None):
+        """shape_voxels of ball_shape(center, radius)."""
+        return self.shape_voxels(*ball_shape(center, radius), mrgb, cap)
+
+    def ellipsoid_voxels(self, center, radii, rotation=None, mrgb=None, cap=None):
+        """shape_voxels of ellipsoid_shape(center, radii, rotation)."""
+        return self.shape_voxels(*ellipsoid_shape(center, radii, rotation), mrgb, cap)
+
+    def box_voxels(self, center, half, rotation=None, mrgb=None, cap=None):
+        """shape_voxels of box_shape(center, half, rotation)."""
+        return self.shape_voxels(*box_shape(center, half, rotation), mrgb, cap)
+
+    def cylinder_voxels(self, a, b, radius, mrgb=None, cap=None):
+        """shape_voxels of cylinder_shape(a, b, radius)."""
+        return self.shape_voxels(*cylinder_shape(a, b, radius), mrgb, cap)
+
+    def capsule_voxels(self, a, b, radius, mrgb=None, cap=None):
+        """shape_voxels of capsule_shape(a, b, radius)."""
+        return self.shape_voxels(*capsule_shape(a, b, radius), mrgb, cap)
 
     def combine_voxels(self, a_pos, a_mrgb, b_pos, b_mrgb, op, cap=None):
         """vxrt_combine_voxels_device (include/vxrt_setops.h): the lists A and B combined under op (LIST_UNION: in either, B's bytes

@@ -29,6 +29,7 @@
 #include "vxrt_query.h"
 #include "vxrt_scene_depth.h"
 #include "vxrt_setops.h"
+#include "vxrt_shape.h"
 #include "vxrt_mesh.h"
 #include "vxrt_morph.h"
 #include "vxrt_solid.h"
@@ -288,6 +289,24 @@ class Context {
         size_t count = 0;
         check(vxrt_transform_voxels_device(ctx_, pos, mrgb, n, &pull, box_min.data(), box_max.data(), out_pos, out_mrgb, cap, &count),
               "vxrt_transform_voxels_device");
+        return count;
+    }
+    // vxrt_shape.h: the cells of the half-open box whose centres the pull map takes into the shape, as a list in device memory in
+    // path order; mrgb (host memory, 4 bytes) == nullptr: positions only.  This form counts only.  Returns the number of voxels.
+    size_t shape_voxels_device(const vxrt_shape& shape, const vxrt_affine& pull, const std::array<int32_t, 3>& box_min,
+                               const std::array<int32_t, 3>& box_max) {
+        size_t count = 0;
+        check(vxrt_shape_voxels_device(ctx_, &shape, &pull, box_min.data(), box_max.data(), nullptr, nullptr, nullptr, 0, &count),
+              "vxrt_shape_voxels_device");
+        return count;
+    }
+    // ... and this one writes out_pos and, with mrgb, out_mrgb, which have room for cap voxels.
+    size_t shape_voxels_device(const vxrt_shape& shape, const vxrt_affine& pull, const std::array<int32_t, 3>& box_min,
+                               const std::array<int32_t, 3>& box_max, const uint8_t* mrgb, int16_t (*out_pos)[3], uint8_t (*out_mrgb)[4],
+                               size_t cap) {
+        size_t count = 0;
+        check(vxrt_shape_voxels_device(ctx_, &shape, &pull, box_min.data(), box_max.data(), mrgb, out_pos, out_mrgb, cap, &count),
+              "vxrt_shape_voxels_device");
         return count;
     }
     // vxrt_setops.h: the lists A and B (device memory; a_mrgb == nullptr: positions only) combined under op, in path order.
