@@ -18,7 +18,8 @@
 //   api_morph.hip    a device voxel list dilated, eroded, or cut to its surface layer or margin ring (vxrt_morph.h)
 //   api_mesh.hip     a device voxel list's exposed faces as an indexed triangle mesh (vxrt_mesh.h)
 //   api_shape.hip    a box, ball, cylinder or capsule rasterised into a device voxel list (vxrt_shape.h)
-//   list_ops.hip     no entry point: the host pipeline those five share (list_ops.h)
+//   api_distance.hip a device voxel list's exact squared Euclidean distance transform; ball dilate and erode (vxrt_distance.h)
+//   list_ops.hip     no entry point: the host pipeline those six share (list_ops.h)
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -368,6 +368,9 @@ PICK_MISS, PICK_HIT, PICK_CAP = 0, 1, 2
 LIST_UNION, LIST_INTERSECT, LIST_DIFFERENCE, LIST_XOR, LIST_CHANGED = 0, 1, 2, 3, 4
 # vxrt_morph_op (include/vxrt_morph.h)
 MORPH_DILATE, MORPH_ERODE, MORPH_SURFACE, MORPH_MARGIN = 0, 1, 2, 3
+# vxrt_distance_mode (include/vxrt_distance.h); a d2 of DISTANCE_FAR: no cell within max_d2; max_d2 is at most DISTANCE_MAX_D2
+DISTANCE_DEPTH, DISTANCE_FIELD, DISTANCE_ERODE, DISTANCE_DILATE = 0, 1, 2, 3
+DISTANCE_FAR, DISTANCE_MAX_D2 = 0xFFFF, 256
 # vxrt_mesh_mode (include/vxrt_mesh.h)
 MESH_FACES, MESH_RUNS = 0, 1
 
@@ -1639,6 +1642,75 @@ class Context:
         """morph_voxels MORPH_ERODE, then MORPH_DILATE of the result: specks and spurs up to 2 * steps cells wide are removed."""
         self._morph_check(pos, mrgb, connectivity, steps)
         return self.morph_voxels(*self.morph_voxels(pos, mrgb, MORPH_ERODE, connectivity, steps), MORPH_DILATE, connectivity, steps)
+
+    def _distance_check(self, pos, mrgb, max_d2):
+        self._list_check(pos, mrgb)
+        self._int_of(max_d2, range(1, DISTANCE_MAX_D2 + 1), "max_d2 must be an integer of 1 .. 256 (a squared radius in cells)")
+
+    def distance_voxels(self, pos, mrgb, mode, max_d2, cap=None):
+        """vxrt_distance_voxels_device (include/vxrt_distance.h): the exact squared Euclidean distance transform of the list pos /
+        mrgb, bounded by the squared radius max_d2 (1 .. 256), under mode (DISTANCE_DEPTH: every voxel with the d2 to its nearest
+        empty cell, or DISTANCE_FAR; DISTANCE_FIELD: every empty cell within max_d2 of a voxel, with that d2 and the nearest voxel's
+        bytes; DISTANCE_ERODE: the voxels deeper than max_d2; DISTANCE_DILATE: the list and DISTANCE_FIELD's cells) -> (pos int16
+        [k,3], mrgb uint8 [k,4], d2 uint16 [k]) as torch tensors on the context's device, in path order, each position once.
+        mrgb=None: positions only, and the second value is None.  pos (int16 [n,3]) and mrgb (uint8 [n,4]) are contiguous torch
+        tensors on the context's device, or numpy arrays, which are uploaded with torch once every check has passed.  cap as
+        transform_voxels'.  Ordered on both sides against torch's current stream.  No scene is needed or touched."""
+        import torch
+        self._distance_check(pos, mrgb, max_d2)
+        self._int_of(mode, range(DISTANCE_DEPTH, DISTANCE_DILATE + 1), "mode must be one of DISTANCE_DEPTH .. DISTANCE_DILATE")
+        self._cap(cap)
+        dev = torch.device("cuda", self.device)
+        pos = self._query_tensor(pos)
+        mrgb = None if mrgb is None else self._query_tensor(mrgb)
+        got = C.c_size_t(0)
+
+        def run(out_pos, out_mrgb, out_d2, room):
+            self._chk(self._L.vxrt_distance_voxels_device(
+                self._h, _dptr(pos), _dptr(mrgb), C.c_size_t(len(pos)), C.c_uint32(int(mode)), C.c_uint32(int(max_d2)), _dptr(out_pos),
+                _dptr(out_mrgb), _dptr(out_d2), C.c_size_t(room), C.byref(got)), "vxrt_distance_voxels_device")
+            return int(got.value)
+        # an empty tensor has no address to tell "no mrgb" from "no entries" by: the result is empty either way
+        if len(pos) == 0:
+            cap = 0
+        if cap is None:
+            with self._ordered():
+                cap = run(None, None, None, 0)
+        cap = int(cap)
+        out_pos = torch.empty((cap, 3), dtype=torch.int16, device=dev)
+        out_mrgb = torch.empty((cap, 4), dtype=torch.uint8, device=dev) if mrgb is not None else None
+        out_d2 = torch.empty(cap, dtype=torch.uint16, device=dev)
+        k = 0
+        if cap:
+            with self._ordered():
+                k = run(out_pos, out_mrgb, out_d2, cap)
+        return out_pos[:k], (None if out_mrgb is None else out_mrgb[:k]), out_d2[:k]
+
+    def depth_voxels(self, pos, mrgb, max_d2):
+        """distance_voxels DISTANCE_DEPTH: how deep inside the list each of its voxels lies -> (pos, mrgb, d2)."""
+        return self.distance_voxels(pos, mrgb, DISTANCE_DEPTH, max_d2)
+
+    def dilate_ball(self, pos, mrgb, max_d2):
+        """distance_voxels DISTANCE_DILATE without the distances: the list dilated by the ball of squared radius max_d2 -> (pos, mrgb)."""
+        return self.distance_voxels(pos, mrgb, DISTANCE_DILATE, max_d2)[:2]
+
+    def erode_ball(self, pos, mrgb, max_d2):
+        """distance_voxels DISTANCE_ERODE without the distances: the list eroded by the ball of squared radius max_d2 -> (pos, mrgb)."""
+        return self.distance_voxels(pos, mrgb, DISTANCE_ERODE, max_d2)[:2]
+
+    def margin_ball(self, pos, mrgb, max_d2):
+        """distance_voxels DISTANCE_FIELD without the distances: the round margin of squared radius max_d2 outside the list -> (pos, mrgb)."""
+        return self.distance_voxels(pos, mrgb, DISTANCE_FIELD, max_d2)[:2]
+
+    def close_ball(self, pos, mrgb, max_d2):
+        """dilate_ball, then erode_ball of the result: pinholes and gaps are filled, with the bytes dilation gave them."""
+        self._distance_check(pos, mrgb, max_d2)
+        return self.erode_ball(*self.dilate_ball(pos, mrgb, max_d2), max_d2)
+
+    def open_ball(self, pos, mrgb, max_d2):
+        """erode_ball, then dilate_ball of the result: specks and spurs are removed, and what is left is rounded."""
+        self._distance_check(pos, mrgb, max_d2)
+        return self.dilate_ball(*self.erode_ball(pos, mrgb, max_d2), max_d2)
 
     def _box(self, box_min, box_max):
         if (box_min is None) != (box_max is None):

@@ -20,6 +20,7 @@
 #include "vxrt_components.h"
 #include "vxrt_device_edit.h"
 #include "vxrt_device_scene.h"
+#include "vxrt_distance.h"
 #include "vxrt_edit.h"
 #include "vxrt_extract.h"
 #include "vxrt_grid.h"
@@ -327,6 +328,17 @@ class Context {
         size_t count = 0;
         check(vxrt_morph_voxels_device(ctx_, pos, mrgb, n, uint32_t(op), connectivity, steps, out_pos, out_mrgb, cap, &count),
               "vxrt_morph_voxels_device");
+        return count;
+    }
+    // vxrt_distance.h: the list's exact squared Euclidean distance transform (device memory; mrgb == nullptr: positions only): every
+    // voxel's d2 to the nearest empty cell (VXRT_DISTANCE_DEPTH), every empty cell within max_d2 of a voxel (VXRT_DISTANCE_FIELD), or
+    // the list eroded / dilated by the ball of squared radius max_d2, in path order.  out_pos == nullptr counts only.  Returns the
+    // number of voxels of the result.
+    size_t distance_voxels_device(const int16_t (*pos)[3], const uint8_t (*mrgb)[4], size_t n, vxrt_distance_mode mode, uint32_t max_d2,
+                                  int16_t (*out_pos)[3] = nullptr, uint8_t (*out_mrgb)[4] = nullptr, uint16_t* out_d2 = nullptr, size_t cap = 0) {
+        size_t count = 0;
+        check(vxrt_distance_voxels_device(ctx_, pos, mrgb, n, uint32_t(mode), max_d2, out_pos, out_mrgb, out_d2, cap, &count),
+              "vxrt_distance_voxels_device");
         return count;
     }
     // vxrt_mesh.h: the list's exposed faces (device memory; mrgb == nullptr: positions only) as an indexed triangle mesh, one quad
