@@ -8,12 +8,12 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libvxrt.so")
 # the default library: tracers 1 (all-in-one kernel) and 4 (head + compacted tail) over the 8-byte scene records
 SOURCES = ["api_context.hip", "api_scene.hip", "api_trace.hip", "api_frame.hip", "api_halo.hip", "api_host.cpp", "api_debug.hip", "api_edit.hip", "api_extract.hip", "api_device_scene.hip", "api_grid.hip", "api_grid_edit.hip", "api_scene_depth.hip", "api_device_edit.hip", "api_compact.hip", "api_voxelize.hip", "api_solid.hip", "api_components.hip", "api_pieces.hip", "api_query.hip", "api_transform.hip", "api_setops.hip", "api_morph.hip", "api_mesh.hip", "api_shape.hip", "api_distance.hip", "list_ops.hip",
-           "trace.hip", "trace_tail.hip", "edit.hip", "extract.hip", "device_build.hip", "grid_build.hip", "grid_edit.hip", "scene_depth.hip", "device_edit.hip", "compact.hip", "voxelize.hip", "solid.hip", "components.hip", "pieces.hip", "query.hip", "transform.hip", "setops.hip", "morph.hip", "mesh.hip", "shape.hip", "distance.hip", "post.hip", "display.hip", "halo.hip", "noise.hip", "scene_device.hip", "scene_host.cpp", "scene_procedural.cpp",
+           "trace.hip", "trace_tail.hip", "edit.hip", "extract.hip", "device_build.hip", "grid_build.hip", "grid_edit.hip", "scene_depth.hip", "device_edit.hip", "compact.hip", "voxelize.hip", "solid.hip", "components.hip", "pieces.hip", "query.hip", "transform.hip", "setops.hip", "morph.hip", "run_heads.hip", "mesh.hip", "shape.hip", "distance.hip", "post.hip", "display.hip", "halo.hip", "noise.hip", "scene_device.hip", "scene_host.cpp", "scene_procedural.cpp",
            "noise_zip.cpp", "vox_scene.cpp"]
 # -DVXRT_VARIANTS=1 (scripts/test_variants.sh): the schedules and the scene format that measured slower and are kept for comparison —
 # tracers 2 (wavefront), 3 (ray queues), 5 (per-lane path refill) and the wide records (two tree levels per 16-byte record)
 VARIANT_SOURCES = ["trace_wavefront.hip", "trace_paths.hip", "trace_pool.hip", "trace_dda.hip", "trace_fused.hip"]
-HEADERS = ["block_scan.h", "compact.h", "ctx.h", "device_build.h", "edit.h", "extract.h", "grid.h", "grid_edit.h", "halo_view.h", "kernels.h", "list_ops.h", "owned.h", "trace_common.h", "trace_block.h", "trace_tail_body.h", "ray_queue.h", "walk_wide.h", "scene_host.h", "vx_vec.h", "voxelize.h", "solid.h", "components.h", "pieces.h", "query.h", "transform.h", "transform_rule.h", "setops.h", "setops_rule.h", "morph.h", "morph_rule.h", "mesh.h", "mesh_rule.h", "shape.h", "shape_rule.h", "distance.h", "distance_rule.h", os.path.join("..", "..", "include", "vxrt.h"),
+HEADERS = ["block_scan.h", "compact.h", "ctx.h", "device_build.h", "edit.h", "extract.h", "grid.h", "grid_edit.h", "halo_view.h", "kernels.h", "list_ops.h", "owned.h", "trace_common.h", "trace_block.h", "trace_tail_body.h", "ray_queue.h", "walk_wide.h", "scene_host.h", "vx_vec.h", "voxelize.h", "solid.h", "components.h", "pieces.h", "query.h", "transform.h", "transform_rule.h", "setops.h", "setops_rule.h", "morph.h", "morph_rule.h", "run_heads.h", "mesh.h", "mesh_rule.h", "shape.h", "shape_rule.h", "distance.h", "distance_rule.h", os.path.join("..", "..", "include", "vxrt.h"),
            os.path.join("..", "..", "include", "vxrt_host.h"), os.path.join("..", "..", "include", "vxrt_debug.h"), os.path.join("..", "..", "include", "vxrt_edit.h"), os.path.join("..", "..", "include", "vxrt_extract.h"),
            os.path.join("..", "..", "include", "vxrt_device_scene.h"), os.path.join("..", "..", "include", "vxrt_grid.h"),
            os.path.join("..", "..", "include", "vxrt_grid_edit.h"), os.path.join("..", "..", "include", "vxrt_scene_depth.h"),

@@ -9,7 +9,7 @@ namespace vxrt {
 
 // About 40 bytes per entry, all of it allocated before the first launch.
 int alloc_labelling(size_t n, const char* who, Labelling* l) {
-    if (int rc = alloc_list_scratch(n, true, who, &l->ls)) return rc;
+    if (int rc = l->ls.alloc(n, true, who)) return rc;
     for (ScratchBuffer* b : {&l->uhead, &l->parent, &l->comp, &l->acc})
         if (int rc = alloc_scratch(b, n * sizeof(uint32_t), who, "the union-find")) return rc;
     return alloc_scratch(&l->part, (size_t(comp_blocks(n)) + 1) * sizeof(uint64_t), who, "the scan partials");
@@ -17,20 +17,18 @@ int alloc_labelling(size_t n, const char* who, Labelling* l) {
 
 // pos[0 .. n), 0 < n < 2^32, read on s -> *l.  axes: 1, 2 or 3.  Waits for the two counts.
 int label_list(const int16_t* pos, uint32_t n, uint32_t axes, const CompBox& box, hipStream_t s, Labelling* l) {
-    uint64_t* kp[2] = {l->ls.keys[0].as<uint64_t>(), l->ls.keys[1].as<uint64_t>()};
-    uint32_t* vp[2] = {l->ls.vals[0].as<uint32_t>(), l->ls.vals[1].as<uint32_t>()};
+    KeySort& ls = l->ls;
     uint64_t* part = l->part.as<uint64_t>();
-    HIP_TRY(components_keys(pos, n, kp[0], vp[0], s));
-    int cur = 0;
-    HIP_TRY(radix_sort_pairs(kp, vp, n, kCompKeyBits, l->ls.hist.as<uint32_t>(), l->ls.totals.as<uint32_t>(), s, &cur));
+    HIP_TRY(components_keys(pos, n, ls.keys(), ls.vals(), s));
+    HIP_TRY(ls.sort(n, kCompKeyBits, s));
     // the sort's other buffers are free from here on: they take the unique keys and the entries' ranks
-    uint64_t* ukeys = kp[cur ^ 1];
-    uint32_t* rank = vp[cur ^ 1];
-    HIP_TRY(components_heads_count(kp[cur], n, part, s));
+    uint64_t* ukeys = ls.spare_keys();
+    uint32_t* rank = ls.spare_vals();
+    HIP_TRY(components_heads_count(ls.keys(), n, part, s));
     HIP_TRY(launch_exclusive_scan(part, comp_blocks(n), s));
     uint64_t m = 0;
     HIP_TRY(hipMemcpyAsync(&m, part + comp_blocks(n), sizeof m, hipMemcpyDeviceToHost, s));
-    HIP_TRY(components_heads_write(kp[cur], vp[cur], n, part, ukeys, l->uhead.as<uint32_t>(), rank, l->parent.as<uint32_t>(), l->acc.as<uint32_t>(), s));
+    HIP_TRY(components_heads_write(ls.keys(), ls.vals(), n, part, ukeys, l->uhead.as<uint32_t>(), rank, l->parent.as<uint32_t>(), l->acc.as<uint32_t>(), s));
     HIP_TRY(hipStreamSynchronize(s));      // m; the partials are rewritten below
     const uint32_t mm = uint32_t(m);       // 0 < m <= n
     HIP_TRY(components_union(ukeys, mm, axes, l->parent.as<uint32_t>(), s));
@@ -39,7 +37,7 @@ int label_list(const int16_t* pos, uint32_t n, uint32_t axes, const CompBox& box
     HIP_TRY(hipMemcpyAsync(&l->components, part + comp_blocks(mm), sizeof l->components, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     l->ukeys = ukeys;
-    l->sorted = vp[cur];
+    l->sorted = ls.vals();
     l->rank = rank;
     l->unique = mm;
     return VXRT_OK;

@@ -1,6 +1,8 @@
 // api_debug.hip — test hooks and diagnostics of libvxrt (include/vxrt.h "Test hook" entries) and the blue-noise generator's entry point.
 #include "../../include/vxrt_bluenoise.h"
 #include "ctx.h"
+#include "list_ops.h"
+#include "scene_args.h"
 
 extern "C" {
 
@@ -402,6 +404,49 @@ int vxrt_detmath_probe(int32_t device, int32_t fn, const float* x, const float* 
     HIP_TRY(launch_detmath_probe(fn, dx, dy, dout, n, nullptr));
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(out, dout, n * 4, hipMemcpyDeviceToHost));
+    return VXRT_OK;
+} VXRT_CATCH
+
+// vxrt_debug.h: list_ops.h's run heads over the caller's device arrays
+int vxrt_debug_run_heads(vxrt_ctx* c, const uint64_t* keys, const uint32_t* words, size_t n, uint32_t shift, uint64_t* out_keys,
+                         uint32_t* out_words, size_t cap, size_t* n_out) try {
+    using namespace vxrt;
+    const char* who = "vxrt_debug_run_heads";
+    const std::string w = who;
+    if (!valid_ctx(c)) { set_error("null context"); return VXRT_E_INVALID; }
+    if (uint64_t(n) >= (uint64_t(1) << 32)) { set_error(w + ": 2^32 keys or more"); return VXRT_E_INVALID; }
+    if (!n_out) { set_error(w + ": null n_out"); return VXRT_E_INVALID; }
+    if (shift > 63u) { set_error(w + ": shift must lie in 0 .. 63"); return VXRT_E_INVALID; }
+    if (out_words && (!words || !out_keys)) { set_error(w + (words ? ": out_words without out_keys" : ": out_words without words")); return VXRT_E_INVALID; }
+    if (n != 0 && !keys) { set_error(w + ": null keys"); return VXRT_E_INVALID; }
+    if ((reinterpret_cast<uintptr_t>(keys) | reinterpret_cast<uintptr_t>(out_keys)) & 7u || (reinterpret_cast<uintptr_t>(words) | reinterpret_cast<uintptr_t>(out_words)) & 3u) {
+        set_error(w + ": an array is not aligned to its entries");
+        return VXRT_E_INVALID;
+    }
+    if (n == 0) { *n_out = 0; return VXRT_OK; }
+
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    if (int rc = check_device_array(c, keys, n * sizeof(uint64_t), who, "keys")) return rc;
+    if (words)
+        if (int rc = check_device_array(c, words, n * sizeof(uint32_t), who, "words")) return rc;
+    if (out_keys)
+        if (int rc = check_device_array(c, out_keys, cap * sizeof(uint64_t), who, "out_keys")) return rc;
+    if (out_words)
+        if (int rc = check_device_array(c, out_words, cap * sizeof(uint32_t), who, "out_words")) return rc;
+
+    // the heads go into a set of their own first: the inputs are read before the first output byte is written
+    hipStream_t s = c->stream;
+    RunHeads rh;
+    OwnedSet heads;
+    if (int rc = out_keys ? run_heads(keys, words, uint32_t(n), shift, out_words != nullptr, s, who, "the heads'", &rh, &heads)
+                          : run_heads_count(keys, uint32_t(n), shift, s, who, &rh))
+        return rc;
+    HIP_TRY(hipStreamSynchronize(s));      // rh.part and the set are freed on return
+    if (int rc = list_room(rh.count, out_keys, cap, who, n_out)) return rc;
+    if (!out_keys) return VXRT_OK;
+    HIP_TRY(hipMemcpyAsync(out_keys, heads.view.keys, size_t(rh.count) * sizeof(uint64_t), hipMemcpyDeviceToDevice, s));
+    if (out_words) HIP_TRY(hipMemcpyAsync(out_words, heads.view.words, size_t(rh.count) * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipStreamSynchronize(s));
     return VXRT_OK;
 } VXRT_CATCH
 

@@ -36,7 +36,7 @@ int vxrt_edit_voxels_device(vxrt_ctx* c, const int16_t (*pos)[3], const uint8_t 
     if (int rc = alloc_list_scratch(n, !clear, who, &ls)) return rc;
     ListBounds lb;
     if (int rc = edit_keys_device(reinterpret_cast<const int16_t*>(pos), reinterpret_cast<const uint8_t*>(mrgb), n, L,
-                                  ls.keys[0].as<uint64_t>(), ls.vals[0].as<uint32_t>(), s, who, &lb))
+                                  ls.keys(), ls.vals(), s, who, &lb))
         return rc;
     if (lb.outside) {
         const std::string half = std::to_string(int32_t(1) << L);
@@ -47,11 +47,10 @@ int vxrt_edit_voxels_device(vxrt_ctx* c, const int16_t (*pos)[3], const uint8_t 
     }
     ScratchBuffer words, segments;
     size_t m = 0;
-    int cur = 0;
-    if (int rc = sort_unique_list(&ls, nn, L, &words, s, who, &m, &cur)) return rc;
+    if (int rc = sort_unique_list(&ls, nn, L, &words, s, who, &m)) return rc;
 
     EditBatch b;
-    const uint64_t* keys[1] = {ls.keys[cur].as<uint64_t>()};
+    const uint64_t* keys[1] = {ls.keys()};
     const uint32_t count[1] = {uint32_t(m)};
     EditBatch* out[1] = {&b};
     if (int rc = cut_edit_lists(keys, count, 1, L, s, who, &segments, out)) return rc;

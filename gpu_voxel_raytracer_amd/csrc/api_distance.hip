@@ -1,10 +1,11 @@
 // api_distance.hip — host side of vxrt_distance.h: the exact squared Euclidean distance transform of a voxel list in device memory
 // and the ball dilation and erosion a threshold on it gives.  The list is keyed, sorted and deduplicated by list_ops.h's key_list;
-// distance.hip's run heads give the tiles of the list; for FIELD and DILATE their 3 x 3 x 3 windows are sorted by the list builder's
-// radix sort (device_build.h) over the key bits in which they can differ, and the heads of that are the candidate tiles; distance.hip
-// then counts per candidate tile, scan_total turns the counts into offsets, and the same kernel writes the caller's arrays at them:
-// no keys, no sort and no decode of the result (api_shape.hip's scheme).  The output checks are list_ops.h's.  Nothing but counts
-// crosses to the host.  DESIGN.md §30.
+// distance.hip's run heads give the tiles of the list; for FIELD and DILATE their 3 x 3 x 3 windows are sorted by a KeySort
+// (device_build.h) over the key bits in which they can differ (tile_sort_bits), and the heads of that are the candidate tiles;
+// distance.hip then counts per candidate tile, scan_total turns the counts into offsets, and the same kernel writes the caller's
+// arrays at them: no keys, no sort and no decode of the result (api_shape.hip's scheme).  The output checks are list_ops.h's.
+// Nothing but counts crosses to the host.  The heads are distance.hip's own kernel, one entry a thread, and not run_heads.hip's:
+// with that one FIELD and DILATE measured slower than before.  DESIGN.md §30.
 #include <algorithm>
 #include <string>
 
@@ -12,16 +13,6 @@
 #include "list_ops.h"
 #include "scene_args.h"
 #include "../../include/vxrt_distance.h"
-
-namespace {
-
-uint32_t bit_length(uint32_t v) {
-    uint32_t bits = 0;
-    while (v >> bits) bits++;
-    return bits;
-}
-
-}  // namespace
 
 extern "C" {
 
@@ -67,41 +58,36 @@ int vxrt_distance_voxels_device(vxrt_ctx* c, const int16_t (*pos)[3], const uint
     if (spread >= (uint64_t(1) << 32)) { set_error(w + ": 2^32 candidate tiles or more"); return VXRT_E_INVALID; }
 
     // two buffers of spread + 1 words: the sort's ping-pong; then the candidate tiles and their counts
-    ScratchBuffer tiles[2];
-    for (int b = 0; b < 2; b++)
-        if (int rc = alloc_scratch(&tiles[b], (size_t(spread) + 1) * sizeof(uint64_t), who, "the tiles' keys and counts")) return rc;
-    uint64_t* kp[2] = {tiles[0].as<uint64_t>(), tiles[1].as<uint64_t>()};
-    HIP_TRY(launch_distance_heads(list.view.keys, m, 12u, grow, heads.as<uint64_t>(), kp[0], s));
+    KeySort tiles;
+    if (int rc = tiles.alloc_keys(size_t(spread) + 1, who, "the tiles' keys and counts")) return rc;
+    HIP_TRY(launch_distance_heads(list.view.keys, m, 12u, grow, heads.as<uint64_t>(), tiles.keys(), s));
 
     DistanceArgs a{};
-    ScratchBuffer hist, totals, firsts;      // outlive the launches that use them: every path below waits before it returns
+    ScratchBuffer firsts;      // outlives the launches that use it: every path below waits before it returns
     if (!grow) {
-        a.tiles = kp[0];
-        a.part = kp[1];
         a.ntiles = uint32_t(own);
     } else {
-        // the windows' tiles agree above the bits in which the list's box, one tile wider, differs (Morton keys: api_shape.hip)
-        uint32_t sort_bits = 0;
+        // the windows' tiles differ in the bits in which the list's box, one tile wider, does
+        uint32_t first[3], last[3];
         for (int ax = 0; ax < 3; ax++) {
             const uint32_t lo = uint32_t(box.lo[ax] + 32768) >> 4, hi = uint32_t(box.hi[ax] + 32768) >> 4;
-            const uint32_t first = lo != 0u ? lo - 1u : 0u, last = std::min(hi + 1u, 4095u);
-            sort_bits = std::max(sort_bits, 3u * bit_length(first ^ last));
+            first[ax] = lo != 0u ? lo - 1u : 0u;
+            last[ax] = std::min(hi + 1u, 4095u);
         }
         const uint32_t blocks = distance_head_blocks(spread);
-        if (int rc = alloc_scratch(&hist, radix_hist_entries(size_t(spread)) * sizeof(uint32_t), who, "the digit counts")) return rc;
-        if (int rc = alloc_scratch(&totals, 256 * sizeof(uint32_t), who, "the digit counts")) return rc;
+        if (int rc = tiles.alloc_counts(size_t(spread), who)) return rc;
         if (int rc = alloc_scratch(&firsts, (size_t(blocks) + 1) * sizeof(uint64_t), who, "the block counts")) return rc;
-        uint32_t* vp[2] = {nullptr, nullptr};
-        int at = 0;
-        HIP_TRY(radix_sort_pairs(kp, vp, uint32_t(spread), sort_bits, hist.as<uint32_t>(), totals.as<uint32_t>(), s, &at));
-        HIP_TRY(launch_distance_heads(kp[at], uint32_t(spread), 0u, false, firsts.as<uint64_t>(), nullptr, s));
+        HIP_TRY(tiles.sort(uint32_t(spread), tile_sort_bits(first, last), s));
+        // the candidate tiles: the distinct ones, written over the sort's free side
+        HIP_TRY(launch_distance_heads(tiles.keys(), uint32_t(spread), 0u, false, firsts.as<uint64_t>(), nullptr, s));
         uint64_t unique = 0;
         if (int rc = scan_total(firsts.as<uint64_t>(), blocks, s, &unique)) return rc;
-        HIP_TRY(launch_distance_heads(kp[at], uint32_t(spread), 0u, false, firsts.as<uint64_t>(), kp[at ^ 1], s));
-        a.tiles = kp[at ^ 1];
-        a.part = kp[at];      // read no more once the heads are written, in stream order
+        HIP_TRY(launch_distance_heads(tiles.keys(), uint32_t(spread), 0u, false, firsts.as<uint64_t>(), tiles.spare_keys(), s));
+        tiles.flip();      // the sorted side is read no more once the heads are written, in stream order
         a.ntiles = uint32_t(unique);
     }
+    a.tiles = tiles.keys();
+    a.part = tiles.spare_keys();
     if (a.ntiles >= (uint32_t(1) << 31)) { set_error(w + ": 2^31 candidate tiles or more"); return VXRT_E_INVALID; }
 
     a.keys = list.view.keys;

@@ -2,7 +2,7 @@
 // list is keyed, sorted and deduplicated by list_ops.h's key_list; morph.hip gives each voxel its 6-neighbour mask; mesh.hip counts
 // and writes the faces as sortable keys; the list builder's radix sort puts them in face-key order, where a run is a stretch of
 // consecutive keys; the run heads are counted and written, each quad's four corner keys written and sorted (keys only), the
-// distinct corners counted and written; the last two kernels look each quad's corners up and write the caller's arrays.  Nothing
+// distinct corners counted and written (list_ops.h's run heads at shift 0); the last two kernels look each quad's corners up and write the caller's arrays.  Nothing
 // but counts crosses to the host.  DESIGN.md §27.
 #include <string>
 
@@ -13,11 +13,6 @@
 
 namespace vxrt {
 namespace {
-
-// part[0 .. blocks] for a counting kernel over `count` entries and the scan behind it.
-int alloc_part(ScratchBuffer* part, uint64_t count, const char* who) {
-    return alloc_scratch(part, (size_t(morph_blocks(count)) + 1) * sizeof(uint64_t), who, "the block counts");
-}
 
 // An output array of `cap` entries of `each` bytes, 4-byte aligned where `aligned`.
 int check_mesh_output(const vxrt_ctx* c, const void* p, size_t cap, size_t each, bool aligned, const char* who, const char* what) {
@@ -75,10 +70,7 @@ int vxrt_mesh_voxels_device(vxrt_ctx* c, const int16_t (*pos)[3], const uint8_t 
 
     // the faces: a voxel has one wherever its 6-neighbour mask has no bit
     uint64_t faces = 0;
-    ListScratch fs;      // the faces, double-buffered for the sort
-    uint64_t* fk[2];
-    uint32_t* fw[2];
-    int fat = 0;
+    KeySort fs;      // the faces, double-buffered for the sort
     {
         ScratchBuffer masks, part;
         if (int rc = alloc_scratch(&masks, size_t(set.m) * sizeof(uint32_t), who, "the neighbour masks")) return rc;
@@ -88,17 +80,13 @@ int vxrt_mesh_voxels_device(vxrt_ctx* c, const int16_t (*pos)[3], const uint8_t 
         if (int rc = scan_total(part.as<uint64_t>(), morph_blocks(set.m), s, &faces)) return rc;
         if (faces >= (uint64_t(1) << 32)) { set_error(w + ": 2^32 faces or more"); return VXRT_E_INVALID; }
         if (faces == 0) { set_error(w + ": internal error: a set without a face"); return VXRT_E_INVALID; }
-        if (int rc = alloc_list_scratch(size_t(faces), words, who, &fs)) return rc;
-        for (int b = 0; b < 2; b++) {
-            fk[b] = fs.keys[b].as<uint64_t>();
-            fw[b] = fs.vals[b].as<uint32_t>();      // null without words: the sort then moves keys only
-        }
-        HIP_TRY(launch_mesh_face_emit(set, masks.as<uint32_t>(), part.as<uint64_t>(), fk[0], fw[0], s));
-        HIP_TRY(radix_sort_pairs(fk, fw, uint32_t(faces), kMeshFaceBits, fs.hist.as<uint32_t>(), fs.totals.as<uint32_t>(), s, &fat));
+        if (int rc = fs.alloc(size_t(faces), words, who)) return rc;
+        HIP_TRY(launch_mesh_face_emit(set, masks.as<uint32_t>(), part.as<uint64_t>(), fs.keys(), fs.vals(), s));
+        HIP_TRY(fs.sort(uint32_t(faces), kMeshFaceBits, s));
         HIP_TRY(hipStreamSynchronize(s));      // masks and part are freed here
     }
-    const uint64_t* sorted_faces = fk[fat];
-    const uint32_t* sorted_words = fw[fat];
+    const uint64_t* sorted_faces = fs.keys();
+    const uint32_t* sorted_words = fs.vals();      // null without words
 
     // the quads: one per run head
     uint64_t quads = 0;
@@ -113,18 +101,14 @@ int vxrt_mesh_voxels_device(vxrt_ctx* c, const int16_t (*pos)[3], const uint8_t 
 
     // the vertices: the distinct corners of all quads, ascending by (x, y, z)
     const uint32_t corners = uint32_t(4 * quads);
-    ListScratch cs;
-    ScratchBuffer cpart, verts;
-    if (int rc = alloc_list_scratch(size_t(corners), false, who, &cs)) return rc;
-    if (int rc = alloc_part(&cpart, corners, who)) return rc;
-    uint64_t* ck[2] = {cs.keys[0].as<uint64_t>(), cs.keys[1].as<uint64_t>()};
-    uint32_t* none[2] = {nullptr, nullptr};
-    int cat = 0;
-    HIP_TRY(launch_mesh_quad_corners(sorted_faces, uint32_t(faces), heads.as<uint32_t>(), uint32_t(quads), ck[0], s));
-    HIP_TRY(radix_sort_pairs(ck, none, corners, kMeshCornerBits, cs.hist.as<uint32_t>(), cs.totals.as<uint32_t>(), s, &cat));
-    HIP_TRY(launch_mesh_unique(ck[cat], corners, cpart.as<uint64_t>(), nullptr, s));
-    uint64_t distinct = 0;
-    if (int rc = scan_total(cpart.as<uint64_t>(), morph_blocks(corners), s, &distinct)) return rc;
+    KeySort cs;
+    ScratchBuffer verts;
+    if (int rc = cs.alloc(size_t(corners), false, who)) return rc;
+    HIP_TRY(launch_mesh_quad_corners(sorted_faces, uint32_t(faces), heads.as<uint32_t>(), uint32_t(quads), cs.keys(), s));
+    HIP_TRY(cs.sort(corners, kMeshCornerBits, s));
+    RunHeads firsts;
+    if (int rc = run_heads_count(cs.keys(), corners, 0u, s, who, &firsts)) return rc;
+    const uint64_t distinct = firsts.count;
 
     // the caps
     *n_verts = size_t(distinct);
@@ -136,7 +120,7 @@ int vxrt_mesh_voxels_device(vxrt_ctx* c, const int16_t (*pos)[3], const uint8_t 
         return VXRT_E_INVALID;
     }
     if (int rc = alloc_scratch(&verts, size_t(distinct) * sizeof(uint64_t), who, "the vertices")) return rc;
-    HIP_TRY(launch_mesh_unique(ck[cat], corners, cpart.as<uint64_t>(), verts.as<uint64_t>(), s));
+    if (int rc = run_heads_emit(firsts, nullptr, verts.as<uint64_t>(), nullptr, s)) return rc;
 
     // the only kernels that write an output byte
     HIP_TRY(launch_mesh_triangles(sorted_faces, sorted_words, uint32_t(faces), heads.as<uint32_t>(), uint32_t(quads), verts.as<uint64_t>(),

@@ -1,8 +1,8 @@
 // api_morph.hip — host side of vxrt_morph.h: a voxel list in device memory dilated, eroded, or cut down to its surface layer or its
 // margin ring.  The list is keyed, sorted and deduplicated by list_ops.h's key_list, once per call; every step then works on unique
 // ascending keys and their leaf words.  morph.hip gives each voxel its neighbour mask; ERODE compacts by it, DILATE lets the voxels
-// beside empty cells offer themselves, sorts the offers (the list builder's radix sort), keeps each cell's first and merges the new
-// cells in (list_ops.h's merge); SURFACE and MARGIN end in that merge's DIFFERENCE against the original set; the totals, the output
+// beside empty cells offer themselves, sorts the offers (a KeySort), keeps each cell's first (list_ops.h's run heads) and merges
+// the new cells in (list_ops.h's merge); SURFACE and MARGIN end in that merge's DIFFERENCE against the original set; the totals, the output
 // checks and the decode are list_ops.h's too.  What is here are the two steps and the loop over them.  Nothing but counts crosses
 // to the host.  DESIGN.md §25.
 #include <string>
@@ -36,7 +36,7 @@ int erode_step(const MorphSet& in, uint32_t c, bool tile, bool with_vals, hipStr
     const uint32_t blocks = morph_blocks(in.m);
     ScratchBuffer masks, part;
     if (int rc = alloc_scratch(&masks, size_t(in.m) * sizeof(uint32_t), who, "the neighbour masks")) return rc;
-    if (int rc = alloc_scratch(&part, (size_t(blocks) + 1) * sizeof(uint64_t), who, "the block counts")) return rc;
+    if (int rc = alloc_part(&part, in.m, who)) return rc;
     HIP_TRY(launch_morph_mask(in, c, kMorphErode, tile, masks.as<uint32_t>(), part.as<uint64_t>(), s));
     uint64_t count = 0;
     if (int rc = scan_total(part.as<uint64_t>(), blocks, s, &count)) return rc;
@@ -56,7 +56,7 @@ int dilate_step(const MorphSet& in, uint32_t c, bool tile, bool with_vals, hipSt
     const uint32_t blocks = morph_blocks(in.m);
     ScratchBuffer masks, part;
     if (int rc = alloc_scratch(&masks, size_t(in.m) * sizeof(uint32_t), who, "the neighbour masks")) return rc;
-    if (int rc = alloc_scratch(&part, (size_t(blocks) + 1) * sizeof(uint64_t), who, "the block counts")) return rc;
+    if (int rc = alloc_part(&part, in.m, who)) return rc;
     HIP_TRY(launch_morph_mask(in, c, kMorphDilate, tile, masks.as<uint32_t>(), part.as<uint64_t>(), s));
     uint64_t offers = 0;
     if (int rc = scan_total(part.as<uint64_t>(), blocks, s, &offers)) return rc;
@@ -64,23 +64,13 @@ int dilate_step(const MorphSet& in, uint32_t c, bool tile, bool with_vals, hipSt
     if (offers == 0) { set_error(w + ": internal error: a set without an empty cell beside it"); return VXRT_E_INVALID; }
 
     // the offers, sorted by (cell, row as the cell sees the source): the first of each cell is its first source
-    ListScratch ls;
-    ScratchBuffer firsts;
-    const uint32_t oblocks = morph_blocks(offers);
-    if (int rc = alloc_list_scratch(size_t(offers), with_vals, who, &ls)) return rc;
-    if (int rc = alloc_scratch(&firsts, (size_t(oblocks) + 1) * sizeof(uint64_t), who, "the block counts")) return rc;
-    uint64_t* kp[2] = {ls.keys[0].as<uint64_t>(), ls.keys[1].as<uint64_t>()};
-    uint32_t* vp[2] = {ls.vals[0].as<uint32_t>(), ls.vals[1].as<uint32_t>()};
-    HIP_TRY(launch_morph_offer(in, c, masks.as<uint32_t>(), part.as<uint64_t>(), kp[0], vp[0], s));
-    int at = 0;
-    HIP_TRY(radix_sort_pairs(kp, vp, uint32_t(offers), 53u, ls.hist.as<uint32_t>(), ls.totals.as<uint32_t>(), s, &at));
-    HIP_TRY(launch_morph_first(kp[at], vp[at], uint32_t(offers), firsts.as<uint64_t>(), nullptr, nullptr, s));
-    uint64_t fresh = 0;
-    if (int rc = scan_total(firsts.as<uint64_t>(), oblocks, s, &fresh)) return rc;
+    KeySort sort;
+    if (int rc = sort.alloc(size_t(offers), with_vals, who)) return rc;
+    HIP_TRY(launch_morph_offer(in, c, masks.as<uint32_t>(), part.as<uint64_t>(), sort.keys(), sort.vals(), s));
+    HIP_TRY(sort.sort(uint32_t(offers), 53u, s));
+    RunHeads firsts;      // freed on return, behind merge_sets' wait
     OwnedSet cells;
-    if (int rc = alloc_set(&cells, fresh, with_vals, who, "a step's")) return rc;
-    HIP_TRY(launch_morph_first(kp[at], vp[at], uint32_t(offers), firsts.as<uint64_t>(), cells.keys.as<uint64_t>(),
-                               with_vals ? cells.words.as<uint32_t>() : nullptr, s));
+    if (int rc = run_heads(sort.keys(), sort.vals(), uint32_t(offers), kMorphOfferShift, with_vals, s, who, "a step's", &firsts, &cells)) return rc;
     // the new cells and the set are disjoint: UNION interleaves them
     return merge_sets(in, cells.view, kListUnion, s, who, out);
 }

@@ -1,6 +1,6 @@
 // api_shape.hip — host side of vxrt_shape.h: a box, ball, cylinder or capsule rasterised into a voxel list in device memory under
-// a fixed-point affine pull.  The tiles that meet the box are keyed by shape.hip and sorted by the list builder's radix sort
-// (device_build.h) over the key bits in which they differ; shape.hip then counts per tile, scan_total turns the counts into offsets,
+// a fixed-point affine pull.  The tiles that meet the box are keyed by shape.hip and sorted by a KeySort (device_build.h) over the
+// key bits in which they differ (list_ops.h's tile_sort_bits); shape.hip then counts per tile, scan_total turns the counts into offsets,
 // and the same kernel writes the caller's arrays at them: no keys, no sort and no decode of the result.  The output checks are
 // list_ops.h's.  Nothing but the count crosses to the host.  DESIGN.md §29.
 #include <algorithm>
@@ -11,16 +11,6 @@
 #include "shape.h"
 #include "shape_rule.h"
 #include "../../include/vxrt_shape.h"
-
-namespace {
-
-uint32_t bit_length(uint32_t v) {
-    uint32_t bits = 0;
-    while (v >> bits) bits++;
-    return bits;
-}
-
-}  // namespace
 
 extern "C" {
 
@@ -78,19 +68,20 @@ int vxrt_shape_voxels_device(vxrt_ctx* c, const vxrt_shape* shape, const vxrt_af
 
     ShapeArgs a{};
     uint64_t tiles = 1;
-    uint32_t sort_bits = 0;
+    uint32_t first[3], last[3];
     for (int i = 0; i < 3; i++) {
         for (int j = 0; j < 3; j++) a.m[i][j] = pull->m[i][j];
         a.t[i] = pull->t[i];
         a.h2[i] = 2 * int64_t(shape->h[i]);
         a.lo[i] = box_min[i];
         a.hi[i] = box_max[i];
-        const uint32_t first = uint32_t(box_min[i] + 32768) >> 4, last = uint32_t(box_max[i] - 1 + 32768) >> 4;
-        a.tlo[i] = first;
-        a.text[i] = last - first + 1u;
+        first[i] = uint32_t(box_min[i] + 32768) >> 4;
+        last[i] = uint32_t(box_max[i] - 1 + 32768) >> 4;
+        a.tlo[i] = first[i];
+        a.text[i] = last[i] - first[i] + 1u;
         tiles *= a.text[i];                                       // each at most 4096, and a box below 2^32 cells has about 2^24 at the most
-        sort_bits = std::max(sort_bits, 3u * bit_length(first ^ last));     // Morton keys: the tiles' keys agree above these bits
     }
+    const uint32_t sort_bits = tile_sort_bits(first, last);
     if (tiles >= (uint64_t(1) << 31)) { set_error(w + ": too many tiles"); return VXRT_E_INVALID; }
     a.kind = shape->kind;
     a.r2 = 2 * int64_t(shape->r);
@@ -108,22 +99,19 @@ int vxrt_shape_voxels_device(vxrt_ctx* c, const vxrt_shape* shape, const vxrt_af
         for (int i = 0; i < 3; i++) a.ext[i] = uint32_t(box_max[i] - box_min[i]);
         const uint32_t blocks = shape_blocks(cells);
         ScratchBuffer part;
-        if (int rc = alloc_scratch(&part, (size_t(blocks) + 1) * sizeof(uint64_t), who, "the block counts")) return rc;
+        if (int rc = alloc_scratch(&part, (size_t(blocks) + 1) * sizeof(uint64_t), who, "the block counts")) return rc;      // shape_blocks' span
         a.part = part.as<uint64_t>();
         HIP_TRY(launch_shape_linear(a, s));
         uint64_t count = 0;
         if (int rc = scan_total(a.part, blocks, s, &count)) return rc;
         if (int rc = list_room(count, out_pos, cap, who, n_out)) return rc;
         if (!out_pos || count == 0) return VXRT_OK;
-        ListScratch out;
-        if (int rc = alloc_list_scratch(size_t(count), false, who, &out)) return rc;
-        uint64_t* kp[2] = {out.keys[0].as<uint64_t>(), out.keys[1].as<uint64_t>()};
-        uint32_t* vp[2] = {nullptr, nullptr};
-        a.out_keys = kp[0];
+        KeySort out;
+        if (int rc = out.alloc(size_t(count), false, who)) return rc;
+        a.out_keys = out.keys();
         HIP_TRY(launch_shape_linear(a, s));
-        int at = 0;
-        HIP_TRY(radix_sort_pairs(kp, vp, uint32_t(count), 12u + sort_bits, out.hist.as<uint32_t>(), out.totals.as<uint32_t>(), s, &at));
-        HIP_TRY(launch_shape_decode(kp[at], uint32_t(count), a.word, reinterpret_cast<uint8_t*>(out_pos), reinterpret_cast<uint8_t*>(out_mrgb), s));
+        HIP_TRY(out.sort(uint32_t(count), 12u + sort_bits, s));
+        HIP_TRY(launch_shape_decode(out.keys(), uint32_t(count), a.word, reinterpret_cast<uint8_t*>(out_pos), reinterpret_cast<uint8_t*>(out_mrgb), s));
         HIP_TRY(hipStreamSynchronize(s));
         return VXRT_OK;
     }
@@ -131,20 +119,14 @@ int vxrt_shape_voxels_device(vxrt_ctx* c, const vxrt_shape* shape, const vxrt_af
     // the scratch, all of it: two buffers of tiles + 1 words (the sort's ping-pong; then the sorted keys and the counts) and the
     // sort's digit counts
     hipStream_t s = c->stream;     // behind everything enqueued there, vxrt_context_wait_stream's events included
-    ScratchBuffer keys[2], hist, totals;
-    for (int b = 0; b < 2; b++)
-        if (int rc = alloc_scratch(&keys[b], (size_t(a.tiles) + 1) * sizeof(uint64_t), who, "the tiles' keys and counts")) return rc;
-    if (int rc = alloc_scratch(&hist, radix_hist_entries(a.tiles) * sizeof(uint32_t), who, "the digit counts")) return rc;
-    if (int rc = alloc_scratch(&totals, 256 * sizeof(uint32_t), who, "the digit counts")) return rc;
-
-    uint64_t* kp[2] = {keys[0].as<uint64_t>(), keys[1].as<uint64_t>()};
-    uint32_t* vp[2] = {nullptr, nullptr};
-    a.keys = kp[0];
+    KeySort keys;
+    if (int rc = keys.alloc_keys(size_t(a.tiles) + 1, who, "the tiles' keys and counts")) return rc;
+    if (int rc = keys.alloc_counts(a.tiles, who)) return rc;
+    a.keys = keys.keys();
     HIP_TRY(launch_shape_tiles(a, s));
-    int at = 0;
-    HIP_TRY(radix_sort_pairs(kp, vp, a.tiles, sort_bits, hist.as<uint32_t>(), totals.as<uint32_t>(), s, &at));
-    a.keys = kp[at];
-    a.part = kp[at ^ 1];
+    HIP_TRY(keys.sort(a.tiles, sort_bits, s));
+    a.keys = keys.keys();
+    a.part = keys.spare_keys();
     HIP_TRY(launch_shape(a, s));
     uint64_t count = 0;
     if (int rc = scan_total(a.part, a.tiles, s, &count)) return rc;

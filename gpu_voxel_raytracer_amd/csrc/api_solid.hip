@@ -53,8 +53,7 @@ int vxrt_voxelize_solid_device(vxrt_ctx* c, const float (*verts)[3], size_t n_ve
         return VXRT_E_SCENE;
     }
     ScratchBuffer cpart;
-    ListScratch xs;      // the crossings' keys, double-buffered, and the sort's counts
-    int xcur = 0;
+    KeySort xs;      // the crossings' keys, double-buffered, and the sort's counts
     if (zcolumns != 0) {
         if (int rc = alloc_scratch(&cpart, (size_t(vox_blocks(zcolumns)) + 1) * sizeof(uint64_t), who, "the scan partials")) return rc;
         if (int rc = solid_count(f.tq.as<VoxTri>(), zoff.as<uint64_t>(), nt, uint32_t(zcolumns), cpart.as<uint64_t>(), s, &crossings)) return rc;
@@ -65,18 +64,16 @@ int vxrt_voxelize_solid_device(vxrt_ctx* c, const float (*verts)[3], size_t n_ve
     }
     const uint32_t pairs = uint32_t(crossings / 2);
     if (crossings != 0) {
-        if (int rc = alloc_list_scratch(size_t(crossings), false, who, &xs)) return rc;
-        HIP_TRY(solid_emit(f.tq.as<VoxTri>(), zoff.as<uint64_t>(), nt, uint32_t(zcolumns), cpart.as<uint64_t>(), keying, xs.keys[0].as<uint64_t>(), s));
-        uint64_t* kp[2] = {xs.keys[0].as<uint64_t>(), xs.keys[1].as<uint64_t>()};
-        uint32_t* vp[2] = {nullptr, nullptr};
-        HIP_TRY(radix_sort_pairs(kp, vp, uint32_t(crossings), keying.bits, xs.hist.as<uint32_t>(), xs.totals.as<uint32_t>(), s, &xcur));
+        if (int rc = xs.alloc(size_t(crossings), false, who)) return rc;
+        HIP_TRY(solid_emit(f.tq.as<VoxTri>(), zoff.as<uint64_t>(), nt, uint32_t(zcolumns), cpart.as<uint64_t>(), keying, xs.keys(), s));
+        HIP_TRY(xs.sort(uint32_t(crossings), keying.bits, s));
         // the pairs: closedness and the interior lengths.  Their offsets go into the sort's other buffer, which is free from here on
         // and holds crossings >= crossings / 2 + 1 words
         ScratchBuffer ppart;
         if (int rc = alloc_scratch(&ppart, (size_t(vox_blocks(pairs)) + 1) * sizeof(uint64_t), who, "the scan partials")) return rc;
         bool closed = false;
         SolidOpen open{};
-        if (int rc = solid_pairs(kp[xcur], uint32_t(crossings), keying, kp[xcur ^ 1], ppart.as<uint64_t>(), who, s, &closed, &open, &cells)) return rc;
+        if (int rc = solid_pairs(xs.keys(), uint32_t(crossings), keying, xs.spare_keys(), ppart.as<uint64_t>(), who, s, &closed, &open, &cells)) return rc;
         if (!closed) {
             set_error(std::string(who) + ": the mesh is not closed: column (" + std::to_string(open.x) + ", " + std::to_string(open.y) + ") is crossed " +
                       std::to_string(open.crossings) + " times, the first column in x, then y order with an odd count (" + std::to_string(crossings) +
@@ -107,21 +104,20 @@ int vxrt_voxelize_solid_device(vxrt_ctx* c, const float (*verts)[3], size_t n_ve
     // one list: the interior first, the surface behind it
     ListScratch ls;
     if (int rc = alloc_list_scratch(size_t(entries), !count_only, who, &ls)) return rc;
-    uint64_t* keys = ls.keys[0].as<uint64_t>();
-    uint32_t* vals = ls.vals[0].as<uint32_t>();      // null when counting
+    uint64_t* keys = ls.keys();
+    uint32_t* vals = ls.vals();      // null when counting
     if (cells != 0) {
         const uint32_t word = count_only ? 0u : 0x80000000u | (uint32_t(fill_mrgb[0]) & 0x7fu) << 24 | uint32_t(fill_mrgb[1]) << 16 |
                                                     uint32_t(fill_mrgb[2]) << 8 | uint32_t(fill_mrgb[3]);
-        HIP_TRY(solid_fill(xs.keys[xcur].as<uint64_t>(), xs.keys[xcur ^ 1].as<uint64_t>(), pairs, uint32_t(cells), keying, depth, word, keys, vals, s));
+        HIP_TRY(solid_fill(xs.keys(), xs.spare_keys(), pairs, uint32_t(cells), keying, depth, word, keys, vals, s));
     }
     if (hits != 0)
         HIP_TRY(voxelize_emit(f.tq.as<VoxTri>(), f.off.as<uint64_t>(), nt, uint32_t(f.columns), spart.as<uint64_t>(), depth,
                               reinterpret_cast<const uint8_t*>(tri_mrgb), keys + cells, vals ? vals + cells : nullptr, s));
     ScratchBuffer words;
     size_t m = 0;
-    int cur = 0;
-    if (int rc = sort_unique_list(&ls, uint32_t(entries), depth, &words, s, who, &m, &cur)) return rc;
-    return voxelize_output(who, ls.keys[cur].as<uint64_t>(), words.as<int32_t>(), m, depth, pos, mrgb, cap, s, n);
+    if (int rc = sort_unique_list(&ls, uint32_t(entries), depth, &words, s, who, &m)) return rc;
+    return voxelize_output(who, ls.keys(), words.as<int32_t>(), m, depth, pos, mrgb, cap, s, n);
 } VXRT_CATCH
 
 }  // extern "C"

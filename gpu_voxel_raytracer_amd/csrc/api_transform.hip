@@ -1,7 +1,7 @@
 // api_transform.hip — host side of vxrt_transform.h: a voxel list in device memory resampled under a fixed-point affine map, by
 // pulling every cell of a destination box through the map into the list.  The source is keyed, sorted and deduplicated by
 // list_ops.h's key_list, which also gives its bounds; the pull is transform.hip's; the blocks' counts are summed by scan_total and
-// the result is sorted by the list builder's radix sort (device_build.h); the output checks and the decode are list_ops.h's.
+// the result is sorted by a KeySort (device_build.h); the output checks and the decode are list_ops.h's.
 // Nothing but two counts and the source's bounds crosses to the host.  DESIGN.md §23.
 #include <string>
 
@@ -84,16 +84,13 @@ int vxrt_transform_voxels_device(vxrt_ctx* c, const int16_t (*pos)[3], const uin
     if (!out_pos || count == 0) return VXRT_OK;
 
     // the result: (key of d, leaf word of s) per voxel at the scanned offsets, sorted by key (unique by construction), decoded
-    ListScratch out;
-    if (int rc = alloc_list_scratch(size_t(count), with_vals, who, &out)) return rc;
-    uint64_t* kp[2] = {out.keys[0].as<uint64_t>(), out.keys[1].as<uint64_t>()};
-    uint32_t* vp[2] = {out.vals[0].as<uint32_t>(), out.vals[1].as<uint32_t>()};
-    a.out_keys = kp[0];
-    a.out_words = vp[0];
+    KeySort out;
+    if (int rc = out.alloc(size_t(count), with_vals, who)) return rc;
+    a.out_keys = out.keys();
+    a.out_words = out.vals();
     HIP_TRY(launch_transform_pull(a, s));
-    int at = 0;
-    HIP_TRY(radix_sort_pairs(kp, vp, uint32_t(count), 48u, out.hist.as<uint32_t>(), out.totals.as<uint32_t>(), s, &at));
-    return decode_list(kp[at], vp[at], count, out_pos, out_mrgb, s);
+    HIP_TRY(out.sort(uint32_t(count), 48u, s));
+    return decode_list(out.keys(), out.vals(), count, out_pos, out_mrgb, s);
 } VXRT_CATCH
 
 }  // extern "C"

@@ -133,12 +133,11 @@ int vxrt_voxelize_mesh_device(vxrt_ctx* c, const float (*verts)[3], size_t n_ver
     ListScratch ls;
     if (int rc = alloc_list_scratch(size_t(hits), !count_only, who, &ls)) return rc;
     HIP_TRY(voxelize_emit(f.tq.as<VoxTri>(), f.off.as<uint64_t>(), nt, uint32_t(columns), cpart.as<uint64_t>(), depth,
-                          reinterpret_cast<const uint8_t*>(tri_mrgb), ls.keys[0].as<uint64_t>(), ls.vals[0].as<uint32_t>(), s));
+                          reinterpret_cast<const uint8_t*>(tri_mrgb), ls.keys(), ls.vals(), s));
     ScratchBuffer words;
     size_t m = 0;
-    int cur = 0;
-    if (int rc = sort_unique_list(&ls, uint32_t(hits), depth, &words, s, who, &m, &cur)) return rc;
-    return voxelize_output(who, ls.keys[cur].as<uint64_t>(), words.as<int32_t>(), m, depth, pos, mrgb, cap, s, n);
+    if (int rc = sort_unique_list(&ls, uint32_t(hits), depth, &words, s, who, &m)) return rc;
+    return voxelize_output(who, ls.keys(), words.as<int32_t>(), m, depth, pos, mrgb, cap, s, n);
 } VXRT_CATCH
 
 }  // extern "C"

@@ -1,5 +1,6 @@
 // block_scan.h — wave and workgroup reductions and prefix sums (wave64) shared by the level-synchronous kernels (extract.hip,
-// device_build.hip, edit.hip, device_edit.hip, voxelize.hip, components.hip, pieces.hip, query.hip).  Everything is in thread order
+// device_build.hip, edit.hip, device_edit.hip, voxelize.hip, components.hip, pieces.hip, query.hip) and the list operators'
+// (run_heads.hip, morph.hip, mesh.hip, distance.hip).  Everything is in thread order
 // and integer, so the results never depend on scheduling.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -65,6 +66,29 @@ template <uint32_t W, typename Out> __device__ __forceinline__ void block_sum_to
         uint32_t all = 0;
         for (uint32_t w = 0; w < W; w++) all += lds[w];
         *out = all;
+    }
+}
+
+// The two halves of a compaction over a block of W waves, kItems <= 32 items per thread side by side: bit k of `kept` says that
+// the thread keeps its item k.  Counting (kEmit == false): the block's kept items -> part[blockIdx.x] (block_sum_to: once per
+// kernel).  Emitting (part scanned): write(k, to) for every kept item in item order, `to` counting up from part[blockIdx.x] plus
+// what the threads before this one keep, so that a block's output stands in the order of its input.
+template <uint32_t W, uint32_t kItems, bool kEmit, typename Part, typename Write>
+__device__ __forceinline__ void block_compact(uint32_t kept, Part* part, Write write) {
+    const uint32_t mine = uint32_t(__builtin_popcount(kept));
+    if constexpr (!kEmit) {
+        block_sum_to<W>(mine, part + blockIdx.x);
+    } else {
+        __shared__ uint32_t scan[W];
+        uint32_t all;
+        uint64_t to = part[blockIdx.x] + block_exclusive<uint32_t, W>(mine, scan, &all);
+#pragma unroll
+        for (uint32_t k = 0; k < kItems; k++) {
+            if (kept >> k & 1u) {
+                write(k, to);
+                to++;
+            }
+        }
     }
 }
 

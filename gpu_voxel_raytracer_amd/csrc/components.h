@@ -79,7 +79,7 @@ hipError_t components_select_write(const uint32_t* flag, uint32_t n, const uint6
 // acc[comp[x]] the component's value (components_flatten); part holds the flatten's root counts, scanned: part[b] = the roots before
 // block b, part[comp_blocks(unique)] = components.
 struct Labelling {
-    ListScratch ls;      // keys and input indices, double-buffered, and the sort's counts
+    KeySort ls;          // keys and input indices, double-buffered, and the sort's counts
     ScratchBuffer uhead, parent, comp, acc, part;
     const uint64_t* ukeys = nullptr;
     const uint32_t* sorted = nullptr;

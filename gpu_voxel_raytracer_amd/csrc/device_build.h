@@ -1,9 +1,10 @@
 // device_build.h — what api_device_scene.hip (host side of vxrt_device_scene.h), device_build.hip (the list builder), grid_build.hip
 // (the dense-grid builder), grid_edit.hip (the grid editor), api_grid.hip (host side of vxrt_grid.h) and api_device_edit.hip /
 // device_edit.hip (vxrt_device_edit.h) share, and the device primitives they and api_extract.hip use: the path key and leaf word,
-// lanes_below, the exclusive scan, the radix sort and the sort-and-dedupe front of a list (device_build.hip).  The front at depth
-// 15 behind vxrt_transform.h, vxrt_setops.h and vxrt_morph.h, and the scan with its total read back, are list_ops.h's key_list and
-// scan_total over these; api_device_edit.hip, api_voxelize.hip and api_solid.hip run the front at a depth of their own.
+// lanes_below, the exclusive scan, the radix sort, the holder of its two sides that every sorting site uses (KeySort) and the
+// sort-and-dedupe front of a list (device_build.hip).  The front at depth 15 behind the list operators, the scan with its total
+// read back and the run heads of sorted keys are list_ops.h's key_list, scan_total and run_heads over these; api_device_edit.hip,
+// api_voxelize.hip and api_solid.hip run the front at a depth of their own.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -62,17 +63,37 @@ size_t radix_hist_entries(size_t n);
 hipError_t radix_sort_pairs(uint64_t* keys[2], uint32_t* vals[2], uint32_t n, uint32_t bits, uint32_t* hist, uint32_t* totals,
                             hipStream_t stream, int* cur);
 
+// The buffers of one such sort and which side is which: keys() / vals() are the side the next launch writes before the sort and
+// the sorted side after it, spare_keys() / spare_vals() the other, free for the caller once the sort is enqueued.  vals() is null
+// without values, and the sort then moves keys only.
+struct KeySort {
+    ScratchBuffer key[2], val[2], hist, totals;
+    int at = 0;
+    // n entries a side (keys, and with_vals values) and the digit counts.  The names are what a failed allocation says.
+    int alloc(size_t n, bool with_vals, const char* who, const char* keys_name = "the keys", const char* vals_name = "the leaf words");
+    // The pieces, for a caller that wants other sizes: `entries` keys a side and no values; the digit counts of a sort of n entries.
+    int alloc_keys(size_t entries, const char* who, const char* name);
+    int alloc_counts(size_t n, const char* who);
+    uint64_t* keys() const { return key[at].as<uint64_t>(); }
+    uint32_t* vals() const { return val[at].as<uint32_t>(); }
+    uint64_t* spare_keys() const { return key[at ^ 1].as<uint64_t>(); }
+    uint32_t* spare_vals() const { return val[at ^ 1].as<uint32_t>(); }
+    // The spare side becomes keys() / vals(): for a caller that wrote its result there (sort_unique_list's dedupe, distance's tiles).
+    void flip() { at ^= 1; }
+    // radix_sort_pairs over the low `bits` bits of keys()[0 .. n); keys() / vals() are the result from then on.  Does not wait.
+    hipError_t sort(uint32_t n, uint32_t bits, hipStream_t stream);
+};
+
 // The front half the list builder and vxrt_edit_voxels_device share, behind their own key pass: the scratch of a list of n entries
-// (keys and, with_vals, leaf words, double-buffered; the digit counts; the scan partials: about 24 bytes per entry), then the stable
-// sort of keys[0] / vals[0] over the 3(depth + 1) key bits and the keep-last dedupe.  On return the m unique keys are ascending in
-// keys[*cur], keys[*cur ^ 1] is free, and with values *leaves holds their m leaf words (exactly sized); a list without values (vals
+// (a KeySort and the scan partials: about 24 bytes per entry), then the stable sort of keys() / vals() over the 3(depth + 1) key
+// bits and the keep-last dedupe into the spare side, which becomes keys().  On return the m unique keys are ascending in keys(),
+// spare_keys() is free, and with values *leaves holds their m leaf words (exactly sized); a list without values (vals
 // not allocated) leaves *leaves alone.  Waits for the count.  VXRT_E_DEVICE: an allocation failed.
-struct ListScratch {
-    ScratchBuffer keys[2], vals[2], hist, totals, part;
+struct ListScratch : KeySort {
+    ScratchBuffer part;
 };
 int alloc_list_scratch(size_t n, bool with_vals, const char* who, ListScratch* ls);
-int sort_unique_list(ListScratch* ls, uint32_t n, uint32_t depth, ScratchBuffer* leaves, hipStream_t stream, const char* who, size_t* m,
-                     int* cur);
+int sort_unique_list(ListScratch* ls, uint32_t n, uint32_t depth, ScratchBuffer* leaves, hipStream_t stream, const char* who, size_t* m);
 
 // The back half of both builders: the node levels over m > 0 unique path keys in ascending order (ukeys, m < 2^32) and their leaf
 // words (*leaves, exactly m int32, handed to *out on success) -> the records, one exact allocation.  ukeys is overwritten; spare

@@ -473,31 +473,46 @@ int build_empty_tree(hipStream_t s, const char* who, DeviceTree* out) {
     return VXRT_OK;
 }
 
-int alloc_list_scratch(size_t n, bool with_vals, const char* who, ListScratch* ls) {
-    const uint32_t blocks = tiles(n);
+int KeySort::alloc(size_t n, bool with_vals, const char* who, const char* keys_name, const char* vals_name) {
     for (int b = 0; b < 2; b++) {
-        if (int rc = alloc_scratch(&ls->keys[b], n * sizeof(uint64_t), who, "the keys")) return rc;
+        if (int rc = alloc_scratch(&key[b], n * sizeof(uint64_t), who, keys_name)) return rc;
         if (with_vals)
-            if (int rc = alloc_scratch(&ls->vals[b], n * sizeof(uint32_t), who, "the leaf words")) return rc;
+            if (int rc = alloc_scratch(&val[b], n * sizeof(uint32_t), who, vals_name)) return rc;
     }
-    if (int rc = alloc_scratch(&ls->hist, size_t(kDigits) * blocks * sizeof(uint32_t), who, "the digit counts")) return rc;
-    if (int rc = alloc_scratch(&ls->totals, kDigits * sizeof(uint32_t), who, "the digit counts")) return rc;
-    return alloc_scratch(&ls->part, (size_t(blocks) + 1) * sizeof(uint64_t), who, "the scan partials");
+    return alloc_counts(n, who);
 }
 
-int sort_unique_list(ListScratch* ls, uint32_t n, uint32_t depth, ScratchBuffer* leaves, hipStream_t s, const char* who, size_t* m_out,
-                     int* cur_out) {
-    const uint32_t blocks = tiles(n);
-    const bool with_vals = ls->vals[0].get() != nullptr;
-    // stable LSD radix sort over the key's 3(depth + 1) bits
-    uint64_t* kp[2] = {ls->keys[0].as<uint64_t>(), ls->keys[1].as<uint64_t>()};
-    uint32_t* vp[2] = {ls->vals[0].as<uint32_t>(), ls->vals[1].as<uint32_t>()};
-    int cur = 0;
-    HIP_TRY(radix_sort_pairs(kp, vp, n, 3u * (depth + 1u), ls->hist.as<uint32_t>(), ls->totals.as<uint32_t>(), s, &cur));
+int KeySort::alloc_keys(size_t entries, const char* who, const char* name) {
+    for (int b = 0; b < 2; b++)
+        if (int rc = alloc_scratch(&key[b], entries * sizeof(uint64_t), who, name)) return rc;
+    return VXRT_OK;
+}
 
-    // dedupe: the last entry of each key -> the leaf words (exactly sized) and the unique keys (keys[cur ^ 1])
+int KeySort::alloc_counts(size_t n, const char* who) {
+    if (int rc = alloc_scratch(&hist, radix_hist_entries(n) * sizeof(uint32_t), who, "the digit counts")) return rc;
+    return alloc_scratch(&totals, kDigits * sizeof(uint32_t), who, "the digit counts");
+}
+
+hipError_t KeySort::sort(uint32_t n, uint32_t bits, hipStream_t s) {
+    uint64_t* kp[2] = {key[0].as<uint64_t>(), key[1].as<uint64_t>()};
+    uint32_t* vp[2] = {val[0].as<uint32_t>(), val[1].as<uint32_t>()};
+    return radix_sort_pairs(kp, vp, n, bits, hist.as<uint32_t>(), totals.as<uint32_t>(), s, &at);
+}
+
+int alloc_list_scratch(size_t n, bool with_vals, const char* who, ListScratch* ls) {
+    if (int rc = ls->alloc(n, with_vals, who)) return rc;
+    return alloc_scratch(&ls->part, (size_t(tiles(n)) + 1) * sizeof(uint64_t), who, "the scan partials");
+}
+
+int sort_unique_list(ListScratch* ls, uint32_t n, uint32_t depth, ScratchBuffer* leaves, hipStream_t s, const char* who, size_t* m_out) {
+    const uint32_t blocks = tiles(n);
+    const bool with_vals = ls->vals() != nullptr;
+    // stable LSD radix sort over the key's 3(depth + 1) bits
+    HIP_TRY(ls->sort(n, 3u * (depth + 1u), s));
+
+    // dedupe: the last entry of each key -> the leaf words (exactly sized) and the unique keys (the spare side)
     uint64_t* part = ls->part.as<uint64_t>();
-    hipLaunchKernelGGL(flag_count_kernel<true>, dim3(blocks), dim3(kThreads), 0, s, kp[cur], n, part);
+    hipLaunchKernelGGL(flag_count_kernel<true>, dim3(blocks), dim3(kThreads), 0, s, ls->keys(), n, part);
     HIP_TRY(hipGetLastError());
     HIP_TRY(launch_exclusive_scan(part, blocks, s));
     uint64_t m = 0;
@@ -505,11 +520,11 @@ int sort_unique_list(ListScratch* ls, uint32_t n, uint32_t depth, ScratchBuffer*
     HIP_TRY(hipStreamSynchronize(s));
     if (with_vals)
         if (int rc = alloc_scratch(leaves, size_t(m) * sizeof(int32_t), who, "the leaf words")) return rc;
-    hipLaunchKernelGGL(dedupe_write_kernel, dim3(blocks), dim3(kThreads), 0, s, kp[cur], with_vals ? vp[cur] : nullptr, n, part, kp[cur ^ 1],
+    hipLaunchKernelGGL(dedupe_write_kernel, dim3(blocks), dim3(kThreads), 0, s, ls->keys(), ls->vals(), n, part, ls->spare_keys(),
                        with_vals ? leaves->as<int32_t>() : nullptr);
     HIP_TRY(hipGetLastError());
+    ls->flip();
     *m_out = size_t(m);
-    *cur_out = cur ^ 1;
     return VXRT_OK;
 }
 
@@ -543,13 +558,12 @@ int build_svo_device_list(const int16_t* pos, const uint8_t* mrgb, size_t n, hip
 
     const uint32_t words = (reinterpret_cast<uintptr_t>(mrgb) & 3u) == 0u ? 1u : 0u;
     hipLaunchKernelGGL(keys_kernel, dim3(uint32_t((n + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, pos, mrgb, n, depth, words,
-                       ls.keys[0].as<uint64_t>(), ls.vals[0].as<uint32_t>());
+                       ls.keys(), ls.vals());
     HIP_TRY(hipGetLastError());
 
     size_t m = 0;
-    int cur = 0;
-    if (int rc = sort_unique_list(&ls, nn, depth, &leaves, s, who, &m, &cur)) return rc;
-    return build_levels(ls.keys[cur].as<uint64_t>(), ls.keys[cur ^ 1].as<uint64_t>(), m, ls.part.as<uint64_t>(), bins.as<uint64_t>(), depth,
+    if (int rc = sort_unique_list(&ls, nn, depth, &leaves, s, who, &m)) return rc;
+    return build_levels(ls.keys(), ls.spare_keys(), m, ls.part.as<uint64_t>(), bins.as<uint64_t>(), depth,
                         &leaves, s, who, out);
 }
 

@@ -200,10 +200,11 @@ __device__ __forceinline__ uint32_t leaf_at(const SvoRecord* svo, const int32_t*
 hipError_t launch_tile_reduce(const TileStat* stats, uint32_t n, TileStat* part, TileStat* dst, hipStream_t stream);
 
 // The `active` active tiles of g's ntiles in path order (depth >= 4), enqueued on `stream`: the tiles keyed by tile_code, inactive
-// ones past every code, sorted (radix_sort_pairs); then their weights scanned in that order.  order[0 .. active): their indices,
+// ones past every code, sorted (KeySort); then their weights scanned in that order.  order[0 .. active): their indices,
 // offset[0 .. active): the exclusive prefix sums of their weights.  The buffers live as long as *out.  who: the API call.
 struct TileOrder {
-    ScratchBuffer keys[2], vals[2], hist, totals, part, offset;
+    KeySort sort;
+    ScratchBuffer part, offset;
     const uint32_t* order = nullptr;
 };
 int order_active_tiles(const GridDesc& g, const TileStat* stats, uint32_t ntiles, uint32_t active, uint32_t depth, hipStream_t stream,

@@ -182,22 +182,14 @@ hipError_t launch_tile_reduce(const TileStat* stats, uint32_t n, TileStat* part,
 int order_active_tiles(const GridDesc& g, const TileStat* stats, uint32_t ntiles, uint32_t active, uint32_t depth, hipStream_t s,
                        const char* who, TileOrder* out) {
     const uint32_t chunks = (active + kChunk - 1) / kChunk, bits = 3u * (depth - 3u);
-    for (int b = 0; b < 2; b++) {
-        if (int rc = alloc_scratch(&out->keys[b], size_t(ntiles) * sizeof(uint64_t), who, "the tile codes")) return rc;
-        if (int rc = alloc_scratch(&out->vals[b], size_t(ntiles) * sizeof(uint32_t), who, "the tile codes")) return rc;
-    }
-    if (int rc = alloc_scratch(&out->hist, radix_hist_entries(ntiles) * sizeof(uint32_t), who, "the digit counts")) return rc;
-    if (int rc = alloc_scratch(&out->totals, 256 * sizeof(uint32_t), who, "the digit counts")) return rc;
+    if (int rc = out->sort.alloc(ntiles, true, who, "the tile codes", "the tile codes")) return rc;
     if (int rc = alloc_scratch(&out->part, (size_t(chunks) + 1) * sizeof(uint64_t), who, "the tile offsets")) return rc;
     if (int rc = alloc_scratch(&out->offset, size_t(active) * sizeof(uint64_t), who, "the tile offsets")) return rc;
     hipLaunchKernelGGL(grid_tile_code_kernel, dim3((ntiles + kThreads - 1) / kThreads), dim3(kThreads), 0, s, g, stats, ntiles, depth, bits,
-                       out->keys[0].as<uint64_t>(), out->vals[0].as<uint32_t>());
+                       out->sort.keys(), out->sort.vals());
     HIP_TRY(hipGetLastError());
-    uint64_t* kp[2] = {out->keys[0].as<uint64_t>(), out->keys[1].as<uint64_t>()};
-    uint32_t* vp[2] = {out->vals[0].as<uint32_t>(), out->vals[1].as<uint32_t>()};
-    int cur = 0;
-    HIP_TRY(radix_sort_pairs(kp, vp, ntiles, bits + 1u, out->hist.as<uint32_t>(), out->totals.as<uint32_t>(), s, &cur));
-    out->order = vp[cur];
+    HIP_TRY(out->sort.sort(ntiles, bits + 1u, s));
+    out->order = out->sort.vals();
     hipLaunchKernelGGL(grid_chunk_sum_kernel, dim3(chunks), dim3(kThreads), 0, s, stats, out->order, active, out->part.as<uint64_t>());
     HIP_TRY(hipGetLastError());
     HIP_TRY(launch_exclusive_scan(out->part.as<uint64_t>(), chunks, s));

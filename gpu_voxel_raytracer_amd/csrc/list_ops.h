@@ -1,8 +1,9 @@
-// list_ops.h — the host pipeline behind the operators that take voxel lists in device memory and give one back (api_transform.hip,
-// api_setops.hip, api_morph.hip): a list keyed at depth 15, sorted and deduplicated; a scan's total read back; two sorted unique
-// sets merged under a set operation; the checks of the two output arrays and the decode into them.  api_mesh.hip, which gives a
-// mesh back, takes the front, the total and the input's checks from here.  Host code only: the kernels are device_edit.hip's,
-// device_build.hip's, setops.hip's and transform.hip's.  DESIGN.md §26.
+// list_ops.h — the host pipeline behind the operators on voxel lists in device memory (api_transform.hip, api_setops.hip,
+// api_morph.hip, api_mesh.hip, api_shape.hip, api_distance.hip): a list keyed at depth 15, sorted and deduplicated; a counting
+// kernel's partials and their scan's total read back; the run heads of sorted keys, counted and written; two sorted unique sets
+// merged under a set operation; the bits a sort of tile keys has to look at; the checks of the two output arrays and the decode
+// into them.  The double-buffered sort itself is device_build.h's KeySort.  Host code only: the kernels are device_edit.hip's,
+// device_build.hip's, run_heads.hip's, setops.hip's and transform.hip's.  DESIGN.md §26.
 #pragma once
 #include <utility>
 
@@ -19,6 +20,8 @@ namespace vxrt {
 
 // launch_exclusive_scan over part[0 .. blocks), then part[blocks] (the total) -> the host.  Waits.
 int scan_total(uint64_t* part, uint32_t blocks, hipStream_t s, uint64_t* total);
+// part[0 .. blocks] for a counting kernel of morph.h's geometry over `count` entries and the scan behind it.
+int alloc_part(ScratchBuffer* part, uint64_t count, const char* who);
 
 // One list through the front: keyed by the device editor's pass, sorted, one entry per position with the last entry's bytes.
 // with_vals == false leaves the leaf words behind (view.words == nullptr).  An empty list gets the 16 readable bytes of
@@ -44,6 +47,25 @@ struct OwnedSet {
 };
 // whose: "a step's", "the result's": whose keys and leaf words a failed allocation names.
 int alloc_set(OwnedSet* out, uint64_t count, bool with_vals, const char* who, const char* whose);
+
+// The run heads of keys[0 .. n), 0 < n < 2^32, sorted (run_heads.h: entry 0 and every entry that differs from the one before
+// above `shift`), in two phases.
+struct RunHeads {
+    const uint64_t* keys = nullptr;
+    uint32_t n = 0, shift = 0;
+    ScratchBuffer part;      // must outlive the emitting launch on the stream
+    uint64_t count = 0;
+};
+// Launches the counting kernel and the scan -> rh->count.  Waits.
+int run_heads_count(const uint64_t* keys, uint32_t n, uint32_t shift, hipStream_t s, const char* who, RunHeads* rh);
+// The heads' keys >> shift -> out_keys[0 .. rh->count) and, where both are given, their entries of `words` -> out_words.  Does not wait.
+int run_heads_emit(const RunHeads& rh, const uint32_t* words, uint64_t* out_keys, uint32_t* out_words, hipStream_t s);
+// Both, into *out, exactly sized (with_words: `words` come along).  Does not wait after the emitting launch; rh->part goes with *rh.
+int run_heads(const uint64_t* keys, const uint32_t* words, uint32_t n, uint32_t shift, bool with_words, hipStream_t s, const char* who,
+              const char* whose, RunHeads* rh, OwnedSet* out);
+
+// Morton keys of tiles whose coordinates lie in [first, last] per axis agree above these many bits: what a sort of them looks at.
+uint32_t tile_sort_bits(const uint32_t first[3], const uint32_t last[3]);
 
 // The merge of setops.hip over two sets, 0 < a.m + b.m < 2^32, in two phases.  b.words == nullptr beside a.words takes b as a mask.
 struct SetMerge {

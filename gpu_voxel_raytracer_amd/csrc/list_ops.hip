@@ -1,8 +1,10 @@
 // list_ops.hip — list_ops.h's host pipeline: no kernel of its own.
 #include "list_ops.h"
 
+#include <algorithm>
 #include <string>
 
+#include "run_heads.h"
 #include "scene_args.h"
 #include "transform.h"
 
@@ -15,26 +17,60 @@ int scan_total(uint64_t* part, uint32_t blocks, hipStream_t s, uint64_t* total) 
     return VXRT_OK;
 }
 
+int alloc_part(ScratchBuffer* part, uint64_t count, const char* who) {
+    return alloc_scratch(part, (size_t(morph_blocks(count)) + 1) * sizeof(uint64_t), who, "the block counts");
+}
+
+int run_heads_count(const uint64_t* keys, uint32_t n, uint32_t shift, hipStream_t s, const char* who, RunHeads* rh) {
+    rh->keys = keys;
+    rh->n = n;
+    rh->shift = shift;
+    if (int rc = alloc_part(&rh->part, n, who)) return rc;
+    HIP_TRY(launch_run_heads(keys, nullptr, n, shift, rh->part.as<uint64_t>(), nullptr, nullptr, s));
+    return scan_total(rh->part.as<uint64_t>(), morph_blocks(n), s, &rh->count);
+}
+
+int run_heads_emit(const RunHeads& rh, const uint32_t* words, uint64_t* out_keys, uint32_t* out_words, hipStream_t s) {
+    HIP_TRY(launch_run_heads(rh.keys, words, rh.n, rh.shift, rh.part.as<uint64_t>(), out_keys, out_words, s));
+    return VXRT_OK;
+}
+
+int run_heads(const uint64_t* keys, const uint32_t* words, uint32_t n, uint32_t shift, bool with_words, hipStream_t s, const char* who,
+              const char* whose, RunHeads* rh, OwnedSet* out) {
+    if (int rc = run_heads_count(keys, n, shift, s, who, rh)) return rc;
+    if (int rc = alloc_set(out, rh->count, with_words, who, whose)) return rc;
+    return run_heads_emit(*rh, words, out->keys.as<uint64_t>(), out->words.as<uint32_t>(), s);
+}
+
+uint32_t tile_sort_bits(const uint32_t first[3], const uint32_t last[3]) {
+    uint32_t bits = 0;
+    for (int ax = 0; ax < 3; ax++) {
+        uint32_t length = 0;      // the bit length of first ^ last
+        while ((first[ax] ^ last[ax]) >> length) length++;
+        bits = std::max(bits, 3u * length);
+    }
+    return bits;
+}
+
 int key_list(const int16_t (*pos)[3], const uint8_t (*mrgb)[4], size_t n, bool with_vals, hipStream_t s, const char* who, KeyedList* out,
              ListBounds* bounds) {
     if (n == 0) {
-        if (int rc = alloc_scratch(&out->ls.keys[0], 0, who, "the keys")) return rc;
+        if (int rc = alloc_scratch(&out->ls.key[0], 0, who, "the keys")) return rc;
         if (with_vals)
             if (int rc = alloc_scratch(&out->leaves, 0, who, "the leaf words")) return rc;
-        out->view = MorphSet{out->ls.keys[0].as<uint64_t>(), with_vals ? out->leaves.as<uint32_t>() : nullptr, 0u};
+        out->view = MorphSet{out->ls.keys(), with_vals ? out->leaves.as<uint32_t>() : nullptr, 0u};
         return VXRT_OK;
     }
     if (int rc = alloc_list_scratch(n, with_vals, who, &out->ls)) return rc;
     // keys at depth 15: every int16 position is inside that cube
     ListBounds lb;
     if (int rc = edit_keys_device(reinterpret_cast<const int16_t*>(pos), with_vals ? reinterpret_cast<const uint8_t*>(mrgb) : nullptr, n, 15u,
-                                  out->ls.keys[0].as<uint64_t>(), with_vals ? out->ls.vals[0].as<uint32_t>() : nullptr, s, who,
+                                  out->ls.keys(), out->ls.vals(), s, who,
                                   bounds ? bounds : &lb))
         return rc;
     size_t m = 0;
-    int cur = 0;
-    if (int rc = sort_unique_list(&out->ls, uint32_t(n), 15u, &out->leaves, s, who, &m, &cur)) return rc;
-    out->view = MorphSet{out->ls.keys[cur].as<uint64_t>(), with_vals ? out->leaves.as<uint32_t>() : nullptr, uint32_t(m)};      // 0 < m <= n
+    if (int rc = sort_unique_list(&out->ls, uint32_t(n), 15u, &out->leaves, s, who, &m)) return rc;
+    out->view = MorphSet{out->ls.keys(), with_vals ? out->leaves.as<uint32_t>() : nullptr, uint32_t(m)};      // 0 < m <= n
     return VXRT_OK;
 }
 

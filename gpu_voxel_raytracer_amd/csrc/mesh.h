@@ -33,9 +33,7 @@ hipError_t launch_mesh_heads(const uint64_t* faces, const uint32_t* words, uint3
 hipError_t launch_mesh_quad_corners(const uint64_t* faces, uint32_t count, const uint32_t* heads, uint32_t quads, uint64_t* out_corners,
                                     hipStream_t stream);
 
-// The distinct keys of `count` sorted corner keys.  Counting (out_keys == nullptr): part[b] = those that begin in block b.
-// Emitting: the keys at part[b] onward, ascending.
-hipError_t launch_mesh_unique(const uint64_t* corners, uint32_t count, uint64_t* part, uint64_t* out_keys, hipStream_t stream);
+// The vertices are the distinct keys among the sorted corner keys: their run heads at shift 0 (run_heads.h).
 
 // The output's writers.  Quad j's corners are looked up among verts[0 .. n_verts) (mesh_corner_index) and its triangles 2 j and
 // 2 j + 1 written to out_tris (4-byte aligned), with the quad's bytes to out_mrgb (any alignment) where out_mrgb != nullptr (words

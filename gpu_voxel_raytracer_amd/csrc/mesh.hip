@@ -1,7 +1,8 @@
 // mesh.hip — device side of vxrt_mesh.h: the exposed faces of a sorted unique key array counted and written as sortable face keys
 // (mesh_face_count_kernel, mesh_face_emit_kernel), the heads of the runs among the sorted faces (mesh_heads_kernel), each quad's
-// four corner keys (mesh_quad_corners_kernel), the distinct corners among the sorted corner keys (mesh_unique_kernel), and the two
-// kernels that write the caller's arrays (mesh_triangles_kernel, mesh_vertices_kernel).  The host side is api_mesh.hip; the face
+// four corner keys (mesh_quad_corners_kernel), and the two kernels that write the caller's arrays (mesh_triangles_kernel,
+// mesh_vertices_kernel); the distinct corners are the run heads of the sorted corner keys (run_heads.hip).  The thread's items
+// (item_beside, item_apart, at_of) are morph.h's, the compaction block_scan.h's.  The host side is api_mesh.hip; the face
 // key, the head test, the corners and the index walk are mesh_rule.h's, the kernels' contracts are in mesh.h and the argument in
 // DESIGN.md §27.
 //
@@ -17,14 +18,6 @@ namespace vxrt {
 namespace {
 
 constexpr uint32_t kWaves = kMorphThreads / 64;
-
-// The counting and compacting kernels take a thread's items side by side (entry base + 8 t + k), so that a block's output is in
-// the order of its input; the others take them a block's width apart (entry base + 256 k + t), so that a wave's loads and stores
-// are neighbours.  An entry's index is 64 bits wide: the last block of a count near 2^32 reaches past it.  at_of: the index clamped into an array of
-// `count` entries, for the loads that are issued whether or not their value is used.
-__device__ __forceinline__ uint64_t item_beside(uint32_t k) { return uint64_t(blockIdx.x) * kMorphSpan + threadIdx.x * kMorphItems + k; }
-__device__ __forceinline__ uint64_t item_apart(uint32_t k) { return uint64_t(blockIdx.x) * kMorphSpan + k * kMorphThreads + threadIdx.x; }
-__device__ __forceinline__ uint32_t at_of(uint64_t i, uint32_t count) { return morph_safe_index(i < count ? uint32_t(i) : count, count); }
 
 __global__ __launch_bounds__(kMorphThreads) void mesh_face_count_kernel(const uint32_t* __restrict__ masks, const uint32_t m,
                                                                         uint64_t* __restrict__ part) {
@@ -81,21 +74,7 @@ __global__ __launch_bounds__(kMorphThreads) void mesh_heads_kernel(const uint64_
         const uint32_t cur_word = words != nullptr ? words[at] : 0u, prev_word = words != nullptr ? words[before] : 0u;
         heads |= (i < count && mesh_is_head(prev, prev_word, cur, cur_word, i == 0u, mode, words != nullptr) ? 1u : 0u) << k;
     }
-    const uint32_t mine = uint32_t(__builtin_popcount(heads));
-    if (!kEmit) {
-        block_sum_to<kWaves>(mine, part + blockIdx.x);
-        return;
-    }
-    __shared__ uint32_t scan[kWaves];
-    uint32_t all;
-    uint64_t to = part[blockIdx.x] + block_exclusive<uint32_t, kWaves>(mine, scan, &all);
-#pragma unroll
-    for (uint32_t k = 0; k < kMorphItems; k++) {
-        if (heads >> k & 1u) {
-            out_heads[to] = uint32_t(item_beside(k));
-            to++;
-        }
-    }
+    block_compact<kWaves, kMorphItems, kEmit>(heads, part, [&](uint32_t k, uint64_t to) { out_heads[to] = uint32_t(item_beside(k)); });
 }
 
 // Quad j as its first face and its length: heads[j] and the distance to the next head (the last quad ends at `count`).
@@ -121,35 +100,6 @@ __global__ __launch_bounds__(kMorphThreads) void mesh_quad_corners_kernel(const 
         if (j < quads) {
 #pragma unroll
             for (uint32_t i = 0; i < 4u; i++) out_corners[4u * size_t(j) + i] = c.k[i];
-        }
-    }
-}
-
-template <bool kEmit>
-__global__ __launch_bounds__(kMorphThreads) void mesh_unique_kernel(const uint64_t* __restrict__ corners, const uint32_t count,
-                                                                    uint64_t* __restrict__ part, uint64_t* __restrict__ out_keys) {
-    uint64_t key[kMorphItems];
-    uint32_t firsts = 0;
-#pragma unroll
-    for (uint32_t k = 0; k < kMorphItems; k++) {
-        const uint64_t i = item_beside(k);
-        key[k] = corners[at_of(i, count)];
-        const uint64_t before = corners[at_of(i - 1u, count)];      // wraps at i == 0: clamped, and not used
-        firsts |= (i < count && (i == 0u || key[k] != before) ? 1u : 0u) << k;
-    }
-    const uint32_t mine = uint32_t(__builtin_popcount(firsts));
-    if (!kEmit) {
-        block_sum_to<kWaves>(mine, part + blockIdx.x);
-        return;
-    }
-    __shared__ uint32_t scan[kWaves];
-    uint32_t all;
-    uint64_t to = part[blockIdx.x] + block_exclusive<uint32_t, kWaves>(mine, scan, &all);
-#pragma unroll
-    for (uint32_t k = 0; k < kMorphItems; k++) {
-        if (firsts >> k & 1u) {
-            out_keys[to] = key[k];
-            to++;
         }
     }
 }
@@ -240,15 +190,6 @@ hipError_t launch_mesh_heads(const uint64_t* faces, const uint32_t* words, uint3
 hipError_t launch_mesh_quad_corners(const uint64_t* faces, uint32_t count, const uint32_t* heads, uint32_t quads, uint64_t* out_corners,
                                     hipStream_t stream) {
     hipLaunchKernelGGL(mesh_quad_corners_kernel, dim3(morph_blocks(quads)), dim3(kMorphThreads), 0, stream, faces, count, heads, quads, out_corners);
-    return hipGetLastError();
-}
-
-hipError_t launch_mesh_unique(const uint64_t* corners, uint32_t count, uint64_t* part, uint64_t* out_keys, hipStream_t stream) {
-    const dim3 grid(morph_blocks(count)), block(kMorphThreads);
-    if (out_keys != nullptr)
-        hipLaunchKernelGGL(mesh_unique_kernel<true>, grid, block, 0, stream, corners, count, part, out_keys);
-    else
-        hipLaunchKernelGGL(mesh_unique_kernel<false>, grid, block, 0, stream, corners, count, part, out_keys);
     return hipGetLastError();
 }
 

@@ -1,4 +1,5 @@
-// morph.h — what api_morph.hip (host side of vxrt_morph.h) and morph.hip (its kernels) share.  DESIGN.md §25.
+// morph.h — what api_morph.hip (host side of vxrt_morph.h) and morph.hip (its kernels) share, and the block geometry that
+// run_heads.hip and mesh.hip run too.  DESIGN.md §25.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -12,6 +13,13 @@ namespace vxrt {
 // Every kernel here runs blocks of kMorphThreads threads over kMorphSpan consecutive entries each, kMorphItems per thread
 // (morph_rule.h), so a grid has morph_blocks(count) <= 2^21 blocks for fewer than 2^32 entries.
 inline uint32_t morph_blocks(uint64_t count) { return uint32_t((count + kMorphSpan - 1) / kMorphSpan); }
+
+// A thread's item k.  The counting and compacting kernels take a thread's items side by side (entry base + 8 t + k), so that a
+// block's output is in the order of its input; the others take them a block's width apart (entry base + 256 k + t), so that a
+// wave's loads and stores are neighbours.  An entry's index is 64 bits wide: the last block of a count near 2^32 reaches past it;
+// at_of (morph_rule.h) clamps it into its array.
+__device__ __forceinline__ uint64_t item_beside(uint32_t k) { return uint64_t(blockIdx.x) * kMorphSpan + threadIdx.x * kMorphItems + k; }
+__device__ __forceinline__ uint64_t item_apart(uint32_t k) { return uint64_t(blockIdx.x) * kMorphSpan + k * kMorphThreads + threadIdx.x; }
 
 // The set a step works on: m > 0 unique path keys at depth 15, ascending, and their leaf words (nullptr: positions only).
 struct MorphSet {
@@ -31,13 +39,9 @@ hipError_t launch_morph_keep(const MorphSet& s, uint32_t c, const uint32_t* mask
                              uint32_t* out_words, hipStream_t stream);
 
 // DILATE's write: every offer (offer_key of the neighbour and the row, the source's leaf word) at part[b] onward, in no order
-// the caller may rely on but the same one every time.
+// the caller may rely on but the same one every time.  Sorted, the first offer of each cell is a run head above kMorphOfferShift
+// (run_heads.h), and its key there is the cell's (offer_cell).
 hipError_t launch_morph_offer(const MorphSet& s, uint32_t c, const uint32_t* masks, const uint64_t* part, uint64_t* out_offers,
-                              uint32_t* out_words, hipStream_t stream);
-
-// The first offer of each cell of `count` sorted offers.  Counting (out_keys == nullptr): part[b] = the cells that begin in block
-// b, morph_blocks(count) entries.  Emitting: their keys (offer_cell) and words at part[b] onward, ascending and unique.
-hipError_t launch_morph_first(const uint64_t* offers, const uint32_t* words, uint32_t count, uint64_t* part, uint64_t* out_keys,
                               uint32_t* out_words, hipStream_t stream);
 
 }  // namespace vxrt

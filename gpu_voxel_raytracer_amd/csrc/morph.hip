@@ -1,6 +1,6 @@
 // morph.hip — device side of vxrt_morph.h: the neighbour mask of every voxel of a sorted unique key array (morph_mask_kernel), the
-// two writes behind it (morph_keep_kernel for ERODE, morph_offer_kernel for DILATE) and the first offer of each new cell
-// (morph_first_kernel).  The host side is api_morph.hip; the offset table, the neighbour key, the two lookups and the ops' reading
+// two writes behind it (morph_keep_kernel for ERODE, morph_offer_kernel for DILATE); the first offer of each new cell is a run
+// head among the sorted offers (run_heads.hip).  The host side is api_morph.hip; the offset table, the neighbour key, the two lookups and the ops' reading
 // of a mask are morph_rule.h's, the kernels' contracts are in morph.h and the argument in DESIGN.md §25.
 //
 // Unique result: every word written is a function of the key array, its words and the connectivity alone; the counts are integer
@@ -150,17 +150,10 @@ __global__ __launch_bounds__(kMorphThreads) void morph_keep_kernel(const MorphSe
     uint32_t kept = 0;
 #pragma unroll
     for (uint32_t k = 0; k < kMorphItems; k++) kept |= ((it.live >> k & 1u) != 0u && keep_eroded(it.mask[k], c) ? 1u : 0u) << k;
-    __shared__ uint32_t scan[kWaves];
-    uint32_t all;
-    uint64_t to = part[blockIdx.x] + block_exclusive<uint32_t, kWaves>(uint32_t(__builtin_popcount(kept)), scan, &all);
-#pragma unroll
-    for (uint32_t k = 0; k < kMorphItems; k++) {
-        if (kept >> k & 1u) {
-            out_keys[to] = it.key[k];
-            if (out_words != nullptr) out_words[to] = it.word[k];
-            to++;
-        }
-    }
+    block_compact<kWaves, kMorphItems, true>(kept, part, [&](uint32_t k, uint64_t to) {
+        out_keys[to] = it.key[k];
+        if (out_words != nullptr) out_words[to] = it.word[k];
+    });
 }
 
 __global__ __launch_bounds__(kMorphThreads) void morph_offer_kernel(const MorphSet s, const uint32_t c, const uint32_t* __restrict__ masks,
@@ -190,39 +183,6 @@ __global__ __launch_bounds__(kMorphThreads) void morph_offer_kernel(const MorphS
     }
 }
 
-template <bool kEmit>
-__global__ __launch_bounds__(kMorphThreads) void morph_first_kernel(const uint64_t* __restrict__ offers, const uint32_t* __restrict__ words,
-                                                                    const uint32_t count, uint64_t* __restrict__ part,
-                                                                    uint64_t* __restrict__ out_keys, uint32_t* __restrict__ out_words) {
-    const uint32_t at = blockIdx.x * kMorphSpan + threadIdx.x * kMorphItems;
-    uint64_t cell[kMorphItems];
-    uint32_t word[kMorphItems], firsts = 0;
-#pragma unroll
-    for (uint32_t k = 0; k < kMorphItems; k++) {
-        const uint32_t i = at + k;
-        cell[k] = offer_cell(offers[morph_safe_index(i, count)]);
-        const uint64_t before = offer_cell(offers[morph_safe_index(i - 1u, count)]);     // wraps at i == 0: clamped, and not used
-        word[k] = kEmit && words != nullptr ? words[morph_safe_index(i, count)] : 0u;
-        firsts |= (i < count && (i == 0u || cell[k] != before) ? 1u : 0u) << k;
-    }
-    const uint32_t mine = uint32_t(__builtin_popcount(firsts));
-    if (!kEmit) {
-        block_sum_to<kWaves>(mine, part + blockIdx.x);
-        return;
-    }
-    __shared__ uint32_t scan[kWaves];
-    uint32_t all;
-    uint64_t to = part[blockIdx.x] + block_exclusive<uint32_t, kWaves>(mine, scan, &all);
-#pragma unroll
-    for (uint32_t k = 0; k < kMorphItems; k++) {
-        if (firsts >> k & 1u) {
-            out_keys[to] = cell[k];
-            if (out_words != nullptr) out_words[to] = word[k];
-            to++;
-        }
-    }
-}
-
 }  // namespace
 
 hipError_t launch_morph_mask(const MorphSet& s, uint32_t c, uint32_t op, bool tile, uint32_t* masks, uint64_t* part, hipStream_t stream) {
@@ -244,16 +204,6 @@ hipError_t launch_morph_keep(const MorphSet& s, uint32_t c, const uint32_t* mask
 hipError_t launch_morph_offer(const MorphSet& s, uint32_t c, const uint32_t* masks, const uint64_t* part, uint64_t* out_offers,
                               uint32_t* out_words, hipStream_t stream) {
     hipLaunchKernelGGL(morph_offer_kernel, dim3(morph_blocks(s.m)), dim3(kMorphThreads), 0, stream, s, c, masks, part, out_offers, out_words);
-    return hipGetLastError();
-}
-
-hipError_t launch_morph_first(const uint64_t* offers, const uint32_t* words, uint32_t count, uint64_t* part, uint64_t* out_keys,
-                              uint32_t* out_words, hipStream_t stream) {
-    const dim3 grid(morph_blocks(count)), block(kMorphThreads);
-    if (out_keys != nullptr)
-        hipLaunchKernelGGL(morph_first_kernel<true>, grid, block, 0, stream, offers, words, count, part, out_keys, out_words);
-    else
-        hipLaunchKernelGGL(morph_first_kernel<false>, grid, block, 0, stream, offers, words, count, part, out_keys, out_words);
     return hipGetLastError();
 }
 

@@ -78,6 +78,16 @@ VXRT_MORPH_FN uint32_t morph_safe_index(uint32_t at, uint32_t count) {
     return at < last ? at : last;
 }
 
+// The same for a 64-bit index, which the last block of a count near 2^32 needs: i clamped into an array of `count` entries.
+VXRT_MORPH_FN uint32_t at_of(uint64_t i, uint32_t count) { return morph_safe_index(i < count ? uint32_t(i) : count, count); }
+
+// The run heads of `count` sorted keys (run_heads.hip): entry i is one where it is the first, or differs above `shift` from the
+// entry before.  cur and before are loaded from at_of(i) and at_of(i - 1): at i == 0 the latter wraps, is
+// clamped, and its value is not used.
+VXRT_MORPH_FN bool run_is_head(uint64_t cur, uint64_t before, uint64_t i, uint32_t count, uint32_t shift) {
+    return i < count && (i == 0u || cur >> shift != before >> shift);
+}
+
 // Both lookups walk to the greatest index whose key is <= q, down from the top bit: with the walk at `at` and a step of `step`
 // (a power of two), the key at walk_probe is loaded, whatever q is, and walk_take moves on to it or stays.  The kernel loads the
 // probes of its kMorphItems walks side by side and takes them behind one wait.  `there`: the probe's index is inside the array.
@@ -144,7 +154,8 @@ VXRT_MORPH_FN uint32_t offer_rows(uint64_t key, uint32_t mask, uint32_t c) {
 
 // An offer as it is sorted: the new cell's key above the row at which that cell sees the source (the opposite row), so that the
 // first entry of a cell after the sort is its first_source.
-VXRT_MORPH_FN uint64_t offer_key(uint64_t cell, uint32_t row_from_source) { return cell << 5 | uint64_t(opposite_row(row_from_source)); }
-VXRT_MORPH_FN uint64_t offer_cell(uint64_t offer) { return offer >> 5; }
+constexpr uint32_t kMorphOfferShift = 5;
+VXRT_MORPH_FN uint64_t offer_key(uint64_t cell, uint32_t row_from_source) { return cell << kMorphOfferShift | uint64_t(opposite_row(row_from_source)); }
+VXRT_MORPH_FN uint64_t offer_cell(uint64_t offer) { return offer >> kMorphOfferShift; }
 
 }  // namespace vxrt

@@ -174,6 +174,14 @@ int vxrt_debug_dda_rays(vxrt_ctx* ctx, const float* origins, const float* dirs, 
  * bytes.  enable = 0 (the default) is the product's lookup, which asks the whole array at once: it measured faster. */
 int vxrt_debug_morph_tile_lookup(vxrt_ctx* ctx, uint32_t enable);
 
+/* Test hook: the run heads of n sorted keys in device memory, as the list operators take them (csrc/run_heads.h): entry i is a head
+ * where i == 0 or keys[i] >> shift differs from keys[i - 1] >> shift (shift 0 .. 63).  *n_out = their number.  out_keys (device, room
+ * for cap entries, or NULL to count): the heads' keys >> shift, in order; out_words (device, or NULL; needs words and out_keys): the
+ * heads' entries of words.  More heads than cap is refused with "N voxels, room for CAP" and nothing is written.  The arrays are
+ * aligned to their entries. */
+int vxrt_debug_run_heads(vxrt_ctx* ctx, const uint64_t* keys, const uint32_t* words, size_t n, uint32_t shift, uint64_t* out_keys,
+                         uint32_t* out_words, size_t cap, size_t* n_out);
+
 /* What this build of the library contains: VXRT_FEATURE_VARIANTS = it was compiled with -DVXRT_VARIANTS=1 and also holds the
  * schedules and the scene format that measured slower on MI355X and are kept for comparison (tracers 2, 3, 5; the wide scene
  * records).  The default build holds tracers 1 and 4 over the 8-byte records and refuses the others with VXRT_E_INVALID. */

@@ -55,9 +55,9 @@ combiner only where an equal pair lies across two blocks (3 hand-written tests; 
 range, the four one-byte pairs at 2048 j - 1, pairs-combine-6, -8, -10 and -12, and pairs-volumes-6) and otherwise through
 DILATE's merge.  14 (a wrong first source among the corner
 neighbours) changes bytes alone and only at 26.
-Not built: `i == 0u` dropped from mesh_unique_kernel's first test.  The load in front of entry 0 is clamped to the array's last
-entry, and the sorted corner keys of a mesh that is not empty hold at least 8 distinct values, so first and last always differ:
-no input changes the result.  Nor tile_decides' `<=` -> `<`: a key equal to the tile's last is then asked of the whole array,
+Not built: `i == 0u` dropped from run_is_head (morph_rule.h), the test behind the distinct corners.  The load in front of entry 0
+is clamped to the array's last entry, and the sorted corner keys of a mesh that is not empty hold at least 8 distinct values, so
+first and last always differ: no mesh notices it.  tests/test_gpu_run_heads.py does, with one key and with equal keys.  Nor tile_decides' `<=` -> `<`: a key equal to the tile's last is then asked of the whole array,
 which answers the same.
 """
 import ctypes as C
